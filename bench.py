@@ -7,8 +7,12 @@ One "step" = one such forward over one synthetic batch already resident in HBM.
 N>1 (launched by torch.distributed.run): tiles are independent, so every rank runs the same step
 on its own batch (weak scaling, no data-path collective); value = all ranks' HR-Mpix / max time.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, measured with HIP events on the
-launch stream) and `cpu_baseline` (the oracle restatement timed on the host cores, N=1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline
+(`value`, `ms_per_step`, ...).  `--full` adds everything that takes runs of its own: `roofline` and `kernels`
+(dominant kernel, measured with HIP events on the launch stream), the `fwd_bwd`, `train_step` and `gtrain`
+objects, `mfma_sustained_probe`, `cpu_baseline` (the oracle restatement timed on the host cores, N=1 only) and,
+at N>1, the `dp_train` / `dp_gtrain` objects.  `--dump-outputs DIR` writes the last timed step's output as
+DIR/sr.npy (float32) for output-for-output comparisons of two builds: the inputs and weights are seeded.
 """
 import argparse
 import json
@@ -207,6 +211,22 @@ def cpu_baseline(seconds_budget=25.0):
             'one_thread': {'value': round(128 ** 2 / 1e6 / t1, 4), 'unit': 'HR-Mpix/s',
                            'sample': 'one forward of a 1x3x32x32 LR tile, %.3f s' % t1},
             'cpu_model': model}
+
+
+DUMP_MAX_ELEMS = 15 * 2 ** 20           # --dump-outputs: at most ~63 MB of float32; a larger output is sampled
+
+
+def dump_outputs(path, **arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array; an array above DUMP_MAX_ELEMS is reduced to a fixed,
+    seeded sample of its flattened elements (the same indices in every run of the same shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 TRAIN_STEP_MAC = 1.515e12               # SURVEY.md §8a: conv/linear MACs of one batch-16 ESRGAN+ step (G + D + VGG, fwd + bwd)
@@ -628,7 +648,17 @@ def main():
     ap.add_argument('--precision', choices=['fp16', 'fp32'], default='fp16')
     ap.add_argument('--train-batch', type=int, default=16,
                     help="--mode train: LR tiles per GPU per step (the reference's config uses 16)")
+    ap.add_argument('--full', action='store_true',
+                    help='forward mode: also measure what takes runs of its own (roofline / kernels, fwd_bwd, train_step, '
+                         'gtrain, mfma_sustained_probe, cpu_baseline; dp_train / dp_gtrain at N > 1); the --no-* '
+                         'options above select among them')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='forward mode: write the output of the last timed step as DIR/sr.npy (float32, rank 0)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.mode != 'forward':
+        ap.error('--dump-outputs: forward mode only')
     GTRAIN_BUCKETS = tuple(tuple(int(v) for v in b.split('x')) for b in args.gtrain_buckets.split(','))
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -674,7 +704,7 @@ def main():
     # fwd+bwd passes below the same step measured 4 % slower (6.60 vs 6.31 ms, same box, same process; --train-last: A/B).
     # It is a light load (0.18 of the MFMA peak): it does not warm the chip for the headline that follows.
     train_first = None
-    if world == 1 and not args.no_train and not args.train_last:
+    if args.full and world == 1 and not args.no_train and not args.train_last:
         train_first, st_ = train_object(args, 1, 0, dev, None, steps=30, warmup=5)
         del st_
         torch.cuda.empty_cache()
@@ -705,6 +735,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         assert torch.isfinite(y).all()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, sr=y)
 
     ms_per_step = elapsed / args.steps * 1e3
     hr_mpix_per_step = world * args.batch * (4 * args.lr) ** 2 / 1e6
@@ -723,7 +755,7 @@ def main():
            'whole_net_tflops_per_gpu': round(step_flops / (elapsed / args.steps) / 1e12, 1),
            'whole_net_frac_of_f16_mfma_peak': round(step_flops / (elapsed / args.steps) / 1e12 / PEAK_F16_TFLOPS, 4)}
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: per-op HIP-event timing on the launch stream
         with torch.no_grad():
             plan = next(iter(net._plans.values()))
@@ -806,7 +838,7 @@ def main():
         res['dist'] = {'world_size': dist.get_world_size(), 'backend': dist.get_backend(),
                        'rccl_version': '.'.join(str(v) for v in torch.cuda.nccl.version()) if dist.get_backend() == 'nccl' else None,
                        'forced_one_rank': bool(dp_forced)}
-    if (world > 1 or dp_forced) and not args.no_train:
+    if args.full and (world > 1 or dp_forced) and not args.no_train:
         # BASELINE configs[3]: every rank runs the data-parallel train step (the collective path of this repo); the
         # forward headline above has no data-path collective (independent tiles)
         net = None

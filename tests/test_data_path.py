@@ -1,5 +1,6 @@
 """Data path: MATLAB-style bicubic imresize + augment against fixtures captured from
 the imported reference (oracle/gen_golden.py: gen_imresize; codes/data/util.py:94-106,213-412)."""
+import os
 import random
 
 import numpy as np
@@ -7,13 +8,14 @@ import pytest
 import torch
 
 from esrganplus_amd import synth
+from tests.conftest import GOLDEN
 
 CASES = 7
 
 
 @pytest.fixture(scope='module')
 def g():
-    return dict(np.load('tests/golden/imresize.npz'))
+    return dict(np.load(os.path.join(GOLDEN, 'imresize.npz')))
 
 
 def _case(g, i):

@@ -1,12 +1,14 @@
 """GPU parity of the RRDBNet backward (dgrad through the fused conv kernel with transposed weights,
 wgrad kernel, LeakyReLU/noise/residual backward in epilogues) against the golden gradients captured
 from the imported reference (oracle/gen_golden.py)."""
+import os
+
 import numpy as np
 import pytest
 import torch
 
 from esrganplus_amd import synth
-from tests.conftest import checks
+from tests.conftest import GOLDEN, checks
 
 pytestmark = pytest.mark.gpu
 
@@ -218,7 +220,7 @@ def test_full_depth_backward_at_bench_shape_vs_reference_golden(dev, golden, pre
     # ANY implementation there (LeakyReLU masks of pre-activations within fp16 rounding of zero flip).  The chains must
     # stay within 2x of that emulation's worst case and 1.5x of its means (measured: 0.041 / 0.262 / 0.264, means
     # 0.0064 / 0.067 / 0.048); each full tensor within 2x of the emulation's error on that tensor.
-    emu = dict(np.load('tests/golden/rrdbnet_full_grad_fp16emu.npz'))
+    emu = dict(np.load(os.path.join(GOLDEN, 'rrdbnet_full_grad_fp16emu.npz')))
     if prec == 'fp32':
         lim_w, lim_m = (4e-3, 2.5e-2, 2.5e-2), (8e-4, 4e-3, 3e-3)
     else:

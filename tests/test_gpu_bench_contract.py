@@ -1,6 +1,7 @@
 """The driver's command line end to end: `python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON line with
 the contract's keys (metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling /
-vs_baseline / dtype / data / config.workload) plus `roofline` and `cpu_baseline`; the train modes print theirs."""
+vs_baseline / dtype / data / config.workload) and nothing that takes runs of its own; with `--full` the line adds
+`roofline`, `cpu_baseline` and the other side measurements; the train modes print theirs."""
 import json
 import os
 import subprocess
@@ -21,7 +22,7 @@ def _run(*flags):
 
 
 def test_forward_line_follows_the_contract():
-    d = _run('--gpus', '1', '--steps', '3', '--warmup', '1')
+    d = _run('--gpus', '1', '--steps', '3', '--warmup', '1', '--full')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
               'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline', 'fwd_bwd'):
         assert k in d, k
@@ -48,6 +49,31 @@ def test_forward_line_follows_the_contract():
     gt = d['gtrain']
     assert gt['ms_per_step'] > 0 and set(gt['buckets']) == {'16x128^2', '8x192^2', '4x256^2'}
     assert abs(sum(b['ms'] for b in gt['buckets'].values()) - gt['ms_per_step']) <= 0.15 * gt['ms_per_step']
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes what the timed forward returned, and
+    that equals the same seeded forward run here (the forward is deterministic: test_gpu_forward)."""
+    import numpy as np
+    import torch
+    from esrganplus_amd import architecture as arch, synth
+    d = _run('--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path))
+    for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+              'vs_baseline', 'dtype', 'data', 'config'):
+        assert k in d, k
+    assert (d['n_gpus'], d['steps'], d['warmup'], d['unit'], d['dtype'], d['scaling']) == (1, 3, 1, 'HR-Mpix/s', 'f16', 'weak')
+    assert abs(d['value'] - 16 * 512 * 512 / 1e6 / (d['ms_per_step'] / 1e3)) <= 1e-2 * d['value']
+    for k in ('roofline', 'kernels', 'cpu_baseline', 'fwd_bwd', 'train_step', 'gtrain', 'mfma_sustained_probe'):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path)) == ['sr.npy']
+    got = np.load(str(tmp_path / 'sr.npy'))
+    assert got.dtype == np.float32 and got.shape == (16, 3, 512, 512) and got.nbytes <= 64e6
+    dev = torch.device('cuda:0')
+    net = arch.RRDBNet(3, 3, 64, 23).to(dev).eval().set_precision('fp16')
+    net.load_state_dict(synth.rrdbnet_state_dict(23, 0), strict=True)
+    with torch.no_grad():
+        want = net(synth.image_batch(100, 16, 3, 128, 128, name='bench.x').to(dev)).float().cpu().numpy()
+    assert np.array_equal(got, want)
 
 
 @pytest.mark.parametrize('mode', ['train', 'gtrain'])

@@ -253,7 +253,7 @@ def test_train_step_two_ranks_equals_global_batch_loss(dev, world):
 def test_bench_two_ranks_prints_the_dp_train_object(N):
     """`bench.py --gpus N` (2, and 8: the node BASELINE configs[3] / configs[4] name) as the driver launches it for the
     scaling runs, here with all ranks on cuda:0 and gloo in
-    place of RCCL (ESR_BENCH_BACKEND): at world > 1 the default line must carry a `dp_train` object — the configs[3]
+    place of RCCL (ESR_BENCH_BACKEND): at world > 1 the --full line must carry a `dp_train` object — the configs[3]
     step over the process group with its all-reduce volume, the exposed communication time and the same process's
     no-exchange step time — so that the multi-GPU run exercises the collective path, not only independent forwards."""
     import json
@@ -261,7 +261,7 @@ def test_bench_two_ranks_prints_the_dp_train_object(N):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, ESR_BENCH_BACKEND='gloo', MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY='0')
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(N), '--steps', '2', '--warmup', '1',
-                          '--batch', '2', '--lr', '32', '--train-batch', '2', '--dp-steps', '2', '--no-cpu-baseline',
+                          '--batch', '2', '--lr', '32', '--train-batch', '2', '--dp-steps', '2', '--full', '--no-cpu-baseline',
                           '--gtrain-buckets', '2x32,1x48,1x64'],
                          cwd=root, env=env, check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          timeout=1500).stdout.decode()
@@ -400,7 +400,7 @@ def test_forced_one_rank_rccl_step_equals_the_plain_step():
 
 
 def test_bench_forced_one_rank_rccl_prints_the_dp_objects():
-    """`ESR_DP_FORCE=1 python bench.py --gpus 1`: the dp_train / dp_gtrain objects over a one-rank RCCL group — n_ranks 1,
+    """`ESR_DP_FORCE=1 python bench.py --gpus 1 --full`: the dp_train / dp_gtrain objects over a one-rank RCCL group — n_ranks 1,
     backend nccl, the all-reduce volume of BASELINE configs[3] (125 MB) and configs[4] (3 x 67.4 MB) — and the `dist`
     object that proves which backend / RCCL version / world size a line was measured under."""
     import json
@@ -409,7 +409,7 @@ def test_bench_forced_one_rank_rccl_prints_the_dp_objects():
     env = dict(os.environ, ESR_DP_FORCE='1', MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY='0')
     env.pop('ESR_BENCH_BACKEND', None)
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '2',
-                          '--dp-steps', '4', '--no-cpu-baseline', '--no-fwd-bwd', '--no-mfma-probe'],
+                          '--dp-steps', '4', '--full', '--no-cpu-baseline', '--no-fwd-bwd', '--no-mfma-probe'],
                          cwd=root, env=env, check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          timeout=1500).stdout.decode()
     line = json.loads([l for l in out.splitlines() if l.startswith('{')][-1])

@@ -1,12 +1,15 @@
 """Device-side validation metrics (csrc/metrics.hip) against the reference's own outputs
 (tests/golden/psnr.npz: tensor2img images and PSNR values produced by the imported codes/utils/util.py) and
 against the host restatement in esrganplus_amd.metrics (itself pinned by tests/test_host.py / test_metrics.py)."""
+import os
+
 import numpy as np
 import pytest
 import torch
 
 from esrganplus_amd import metrics as M
 from esrganplus_amd import synth
+from tests.conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +21,7 @@ def dev():
 
 
 def test_device_tensor2img_and_psnr_match_reference_goldens(dev):
-    g = dict(np.load('tests/golden/psnr.npz'))
+    g = dict(np.load(os.path.join(GOLDEN, 'psnr.npz')))
     n = sum(1 for k in g if k.startswith('img_a'))
     assert n > 0
     for i in range(n):
@@ -62,7 +65,7 @@ def test_device_psnr_y_matches_reference_test_script(dev):
     """PSNR_Y under the golden captured from the reference's own flow (codes/test.py:69-90 with the imported
     utils/util.py + data/util.py; oracle/gen_golden.py: gen_metrics_y): the Y conversion runs on the FLOAT images,
     so the luma is not rounded to uint8."""
-    g = dict(np.load('tests/golden/metrics_y.npz'))
+    g = dict(np.load(os.path.join(GOLDEN, 'metrics_y.npz')))
     for i in range(3):
         h, w = (int(v) for v in g['shape%d' % i])
         crop = int(g['crop%d' % i])
@@ -78,7 +81,7 @@ def test_device_psnr_y_matches_reference_test_script(dev):
 def test_device_ssim_matches_reference_lines(dev):
     """SSIM / SSIM_Y on the device against the outputs of the reference's own ``calculate_ssim`` (codes/utils/util.py:
     117-158 over oracle/ref_import.cv2_shim; tests/golden/ssim.npz) in the validation flow of codes/test.py:69-90."""
-    g = dict(np.load('tests/golden/ssim.npz'))
+    g = dict(np.load(os.path.join(GOLDEN, 'ssim.npz')))
     for i in range(4):
         h, w = (int(v) for v in g['shape%d' % i])
         crop = int(g['crop%d' % i])

@@ -3,11 +3,14 @@
 against the per-conv training plan they replace (itself pinned to the imported reference's gradients by
 tests/test_gpu_backward.py) and against the fp32 path: outputs, input gradients, parameter gradients, with the
 GaussianNoise layers on (same Philox key), both module variants, ragged sizes; run-to-run bit identity."""
+import os
+
 import numpy as np
 import pytest
 import torch
 
 from esrganplus_amd import synth, _lib as L
+from tests.conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
@@ -175,7 +178,7 @@ def test_fp16_noise_on_training_chains_match_the_oracle(dev, monkeypatch, cls_na
         errs.append(e)
         if e > worst:
             worst, wk = e, k
-    emu = dict(np.load('tests/golden/rrdbnet_small_fp16emu.npz'))
+    emu = dict(np.load(os.path.join(GOLDEN, 'rrdbnet_small_fp16emu.npz')))
     lw, lm = 1.5 * float(emu[variant + '_worst']), 1.25 * float(emu[variant + '_mean'])
     print('%s rows/wave %s: output err / range %.2e, parameter-gradient rel L2 worst %.2e (%s; limit %.2e) mean %.2e (limit %.2e)'
           % (cls_name, rows, ey, worst, wk, lw, float(np.mean(errs)), lm))

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from esrganplus_amd import synth
-from tests.conftest import checks
+from tests.conftest import GOLDEN, checks
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +23,7 @@ def test_optimize_parameters_step_matches_reference():
     dev = torch.device('cuda:0')
     from esrganplus_amd import architecture as arch, train
     from oracle import ref_torch as RT
-    g = dict(np.load('tests/golden/train_step.npz'))
+    g = dict(np.load(os.path.join(GOLDEN, 'train_step.npz')))
     sdG, sdD = synth.rrdbnet_state_dict(nb=2, seed=30), synth.discriminator_state_dict(seed=31)
     netG = arch.RRDBNet(3, 3, 64, 2).to(dev).train()
     netD = arch.Discriminator_VGG_128(3, 64).to(dev).train()
@@ -77,7 +77,7 @@ def test_three_training_iterations_match_the_reference(monkeypatch, knobs):
     monkeypatch.setattr(arch._RRDBNetBase, 'flat_param_grads', knobs.get('ESR_FLAT_GRADS', '1') != '0')
     assert torch.cuda.is_available()
     dev = torch.device('cuda:0')
-    g = dict(np.load('tests/golden/train_steps3.npz'))
+    g = dict(np.load(os.path.join(GOLDEN, 'train_steps3.npz')))
     sdG, sdD = synth.rrdbnet_state_dict(nb=2, seed=32), synth.discriminator_state_dict(seed=33)
     netG = arch.RRDBNet(3, 3, 64, 2).to(dev).train()
     netD = arch.Discriminator_VGG_128(3, 64).to(dev).train()
@@ -269,7 +269,7 @@ def test_optimize_parameters_step_fp16_loss_scaled(dev, scale):
     the first Adam update agrees in sign with the reference's on >= 95 % of a weight tensor, everything finite."""
     from esrganplus_amd import train
     from oracle import ref_torch as RT
-    g = dict(np.load('tests/golden/train_step.npz'))
+    g = dict(np.load(os.path.join(GOLDEN, 'train_step.npz')))
     netG, netD, netF, sdG, sdD = _step_nets(dev, 'fp16')
     lr = synth.image_batch(30, 4, 3, 32, 32, name='step.lr').to(dev)
     hr = synth.image_batch(30, 4, 3, 128, 128, name='step.hr').to(dev)
@@ -544,7 +544,7 @@ def test_optimize_parameters_step_at_full_depth_matches_reference(dev, prec):
     update no worse than the emulation's minus 2 %."""
     from esrganplus_amd import architecture as arch, train
     from oracle import ref_torch as RT
-    g = dict(np.load('tests/golden/train_step_full.npz'))
+    g = dict(np.load(os.path.join(GOLDEN, 'train_step_full.npz')))
     nb = 23
     sdG, sdD = synth.rrdbnet_state_dict(nb=nb, seed=60, gain=0.5), synth.discriminator_state_dict(seed=61)
     netG = arch.RRDBNet(3, 3, 64, nb).to(dev).train().set_precision(prec)
@@ -714,7 +714,7 @@ def test_reference_call_pattern_over_the_drop_in_modules_matches_the_golden(dev)
     `num_batches_tracked` = 4."""
     from esrganplus_amd import architecture as arch
     from oracle import ref_torch as RT
-    g = dict(np.load('tests/golden/train_step.npz'))
+    g = dict(np.load(os.path.join(GOLDEN, 'train_step.npz')))
     sdG, sdD = synth.rrdbnet_state_dict(nb=2, seed=30), synth.discriminator_state_dict(seed=31)
     netG = arch.RRDBNet(3, 3, 64, 2).to(dev).train()
     netD = arch.Discriminator_VGG_128(3, 64).to(dev).train()

@@ -2,14 +2,17 @@
 (tests/golden/metrics.npz); SSIM against tests/golden/ssim.npz = the outputs of the reference's own ``ssim`` /
 ``calculate_ssim`` (codes/utils/util.py:117-158) run over a two-function cv2 shim (oracle/ref_import.py: cv2_shim;
 cv2 itself is not installed), plus a scipy restatement of `cv2.filter2D(...)[5:-5, 5:-5]` as a second opinion."""
+import os
+
 import numpy as np
 import pytest
 
 from esrganplus_amd import metrics as M
+from tests.conftest import GOLDEN
 
 
 def test_ycbcr_matches_reference():
-    g = dict(np.load('tests/golden/metrics.npz'))
+    g = dict(np.load(os.path.join(GOLDEN, 'metrics.npz')))
     for name, fn in (('bgr', M.bgr2ycbcr), ('rgb', M.rgb2ycbcr)):
         for only_y in (True, False):
             assert np.array_equal(fn(g['u8'], only_y), g['%s_u8_%d' % (name, only_y)])
@@ -55,7 +58,7 @@ def test_host_psnr_y_flow_matches_reference_test_script():
     """The host restatement of codes/test.py:69-90 (tensor2img, /255, bgr2ycbcr on the float image, crop, x255,
     PSNR) against the golden produced by the imported reference (oracle/gen_golden.py: gen_metrics_y)."""
     from esrganplus_amd import synth
-    g = dict(np.load('tests/golden/metrics_y.npz'))
+    g = dict(np.load(os.path.join(GOLDEN, 'metrics_y.npz')))
     for i in range(3):
         h, w = (int(v) for v in g['shape%d' % i])
         crop = int(g['crop%d' % i])
@@ -73,7 +76,7 @@ def test_host_ssim_matches_reference_lines():
     """tests/golden/ssim.npz: produced by the imported codes/utils/util.py (gen_golden.py: gen_ssim) — the validation
     flow of codes/test.py:69-90 on 3 channels and on the unrounded Y plane, grey images, raw float arrays."""
     from esrganplus_amd import synth
-    g = dict(np.load('tests/golden/ssim.npz'))
+    g = dict(np.load(os.path.join(GOLDEN, 'ssim.npz')))
     for i in range(4):
         h, w = (int(v) for v in g['shape%d' % i])
         crop = int(g['crop%d' % i])

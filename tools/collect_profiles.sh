@@ -1,6 +1,6 @@
 #!/bin/bash
 # After `gpurun -- bash tools/profile_all.sh <tag>`: copy what is judged from gpurun_out/ into profiles/ and re-stamp the
-# traffic rows.  Usage: tools/collect_profiles.sh r04   (then run bench.py once more on the GPU for the committed line:
+# traffic rows.  Usage: tools/collect_profiles.sh r04   (then run `bench.py --full` once more on the GPU for the committed line:
 # the bench quotes a traffic row only while its hash matches the tree)
 set -e
 TAG=${1:-r04}

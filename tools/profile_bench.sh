@@ -2,11 +2,12 @@
 # Run on the GPU box: rocprofv3 kernel-trace stats + PMC passes of the bench command.
 # Usage: tools/profile_bench.sh <tag>     (writes gpurun_out/prof_<tag>/...)
 set -u
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-r02}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-fwd-bwd --no-train"
+CMD="python $REPO/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-fwd-bwd --no-train"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $CMD > $OUT/trace.log 2>&1
 for C in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "TCC_HIT_sum TCC_MISS_sum"; do
   N=$(echo $C | tr ' ' '_' | cut -c1-40)
