@@ -368,7 +368,9 @@ def build_seq_plan(spec, wp, dp, pspec, want_wgrad, B, H, W, dtype, dev, trainin
                 gcur, masked = gx, bool(pl.relu_mask)
                 continue
             if r['kind'] == 'pool':
-                gx = g32q(r['ch'], r['h'] * 2, r['w'] * 2)
+                # sized as the pooled map's producer (odd maps: the row / column the pool drops get gradient 0, which
+                # the backward leaves untouched in this zeroed buffer; its geometry is the one the conv before reads)
+                gx = g32q(r['ch'], r['x'].H, r['x'].W)
                 pl = L.esr_pool()
                 pl.dtype, pl.mode, pl.B, pl.C, pl.H, pl.W = dt_e, 1, Bb, r['ch'], r['h'], r['w']
                 pl.x, pl.y, pl.g, pl.gx = r['x'].view(0, r['ch']), r['y'].view(0, r['ch']), gcur.view(0, r['ch']), gx.view(0, r['ch'])

@@ -255,7 +255,9 @@ __global__ __launch_bounds__(256) void pool_kernel(const esr_pool p) {
   for (int e = 0; e < CPG; ++e) {
     m[e] = v[0][e]; am[e] = 0;
 #pragma unroll
-    for (int q = 1; q < 4; ++q) if (v[q][e] > m[e]) { m[e] = v[q][e]; am[e] = q; }   // first max wins
+    // first max wins; a NaN beats every number and a later NaN an earlier one (torch's max_pool2d rule: without the
+    // isnan term a NaN past the window's first position was dropped, an overflowed fp16 activation became a finite loss)
+    for (int q = 1; q < 4; ++q) if (v[q][e] > m[e] || __builtin_isnan(v[q][e])) { m[e] = v[q][e]; am[e] = q; }
   }
   if (MODE == 0) {
     st16<T>((char*)p.y.ptr + pix_off(p.y, b, g, y, x), m);

@@ -1590,7 +1590,8 @@ def build_rrdbnet_train_plan(net, wp, dp, nb, in_nc, out_nc, B, H, W, dtype, dev
         if nsplit > 1 and _SIDE and bwd_follow() and spare_ >= 32:
             # Round 6: ONE chain launch and, launched with it on the side stream, the weight gradients of ALL blocks as
             # a follower pass on the CUs the chain leaves free — a block's tasks start when the chain has published the
-            # block (csrc/rdb_wgrad.hip: follow_wait), its partial sums are reduced by its last task.  Behind the chain
+            # block (csrc/rdb_wgrad.hip: follow_wait), its partial sums are reduced in slices by the tasks of the block a
+            # round of the grid later (delayed-slice reduction, rdb_wgrad_follow_kernel).  Behind the chain
             # only the last block's tasks are left (the two-launch form below left the second run's pass + reduction:
             # 0.4 + 0.08 ms of the step's critical path).
             warena = torch.empty(int(L.lib().esr_rdb_wgrad_workspace_elems(B, H, W, len(border))), dtype=torch.float32, device=device)

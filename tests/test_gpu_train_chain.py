@@ -191,8 +191,8 @@ def test_fp16_noise_on_training_chains_match_the_oracle(dev, monkeypatch, cls_na
 def test_backward_chain_split_into_runs_is_bit_identical(dev, monkeypatch, cls_name):
     """Training crops (16 x 32^2 LR: 128 four-row tiles) leave the fused backward half of the chip.  Round 6 (the
     default): ONE chain launch with the weight gradients of all blocks as a FOLLOWER pass launched with it on the side
-    stream — a block's tasks start when the chain has published the block, its partial sums are reduced by its last
-    task (ESR_OPF_FOLLOW, csrc/rdb_wgrad.hip).  Round 5 (ESR_BWD_FOLLOW=0 / an explicit ESR_BWD_SPLIT): several chain
+    stream — a block's tasks start when the chain has published the block, its partial sums are reduced in slices by
+    the tasks of the block a round of the grid later (ESR_OPF_FOLLOW, csrc/rdb_wgrad.hip: rdb_wgrad_follow_kernel).  Round 5 (ESR_BWD_FOLLOW=0 / an explicit ESR_BWD_SPLIT): several chain
     launches over runs of RRDBs, each followed by its weight-gradient pass under the next run's chain
     (engine.bwd_chain_split).  Neither launch boundaries nor the follower's schedule carry semantics: every gradient
     equals the one-launch, pass-behind-the-chain form bit for bit, noise on (same Philox key)."""
