@@ -54,8 +54,9 @@ typedef struct esr_g32 {
  * block.py:315-322 folded into the load).  Epilogue, per output element, in this order:
  *     v = acc + bias;  v = act(v);  [aux_out = v];  v += acc_1x1;
  *     v = v*alpha + res1;  v *= (1 + sigma*z1);  v = v*beta + res2;  v *= (1 + sigma*z2);  out = v
- * (each step skipped when its operand is absent; a residual / z view with fewer channel groups
- * than the output contributes zero to the channels it does not cover).  Backward chains add
+ * (each step skipped when its operand is absent, except alpha: without res1, alpha != 1 still
+ * scales, v = v*alpha, while beta without res2 is ignored; a residual / z view with fewer channel
+ * groups than the output contributes zero to the channels it does not cover).  Backward chains add
  *     out2 = v * act'(mask)      for cout blocks >= mask_cb_begin (act' = 1 if mask>0 else 0.2 / 0)
  *     out3 = v * gamma * (1 + sigma*z3)
  * which is how dgrad launches also apply the LeakyReLU / GaussianNoise / residual-scale backward
