@@ -447,7 +447,7 @@ class _PlannedModule(nn.Module):
 
     def _eye_operand(self, device):
         # 1x1 identity kernel: carries the incoming gradient of a stand-alone block through the conv
-        # epilogue's noise / scale stages (engine.build_rrdbnet_train_plan, kind 'rdb' / 'rrdb')
+        # epilogue's noise / scale stages (engine.TrainBuilder.backward_entry_block)
         eye = getattr(self, '_eye64', None)
         if eye is None or eye.device != torch.device(device):
             eye = torch.eye(64, device=device).view(64, 64, 1, 1).contiguous()

@@ -7,8 +7,8 @@ block.py:260-268 / 287-291) into a recorded list of fused-conv launches over G32
 
 torch is used here for device memory (buffers are torch tensors) and the stream handle only.
 """
+import collections
 import ctypes as C
-
 import os
 
 import torch
@@ -412,6 +412,43 @@ def _conv(dtype_e, B, H, W, src, src_ch, dst, cw, act=L.ACT_NONE, ks=None, strid
     return c
 
 
+def set_nchw(op, ptr):
+    """Bind the caller's NCHW tensor to an op that reads or writes one: a conv with an NCHW epilogue or a layout op."""
+    if op.kind == L.OP_CONV:
+        op.u.conv.nchw_out = ptr
+    else:
+        op.u.layout.nchw = ptr
+
+
+def upload_table(table, device):
+    """A ctypes array as a device tensor (the caller keeps it alive as long as an op points at it)."""
+    return torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(device)
+
+
+class NoiseLayers:
+    """Ids of the GaussianNoise layers in execution order (the Philox stream and explicit z tensors are indexed by
+    them): per RRDB its three dense blocks, then — test_image/block.py:250,256 — the RRDB's own stage.  kind 'net':
+    nb RRDBs; 'rrdb': one; 'rdb': a single dense block.  on=False (eval mode): no layers, every id is None."""
+
+    def __init__(self, variant, kind, nb, on=True):
+        self.on = bool(on)
+        self.extra = variant == 'test_image' and kind != 'rdb'
+        self.per = 4 if variant == 'test_image' else 3
+        self.total = 0 if not on else (1 if kind == 'rdb' else self.per * (nb if kind == 'net' else 1))
+
+    def rdb(self, i, j):
+        """Dense block j of RRDB i."""
+        return self.per * i + j if self.on else None
+
+    def rrdb(self, i):
+        """The extra stage behind RRDB i's residual (test_image only)."""
+        return self.per * i + 3 if self.on and self.extra else None
+
+
+def _layer(lid):
+    return L.NO_LAYER if lid is None else lid
+
+
 class Plan:
     """A recorded forward pass for one (module, input shape, dtype, mode)."""
 
@@ -423,21 +460,19 @@ class Plan:
         self.out_shape = None
         self.noise_ops = []      # (op index, which) of convs carrying a noise epilogue
         self.chain_ops = []      # indices of OP_RDB_CHAIN ops (noise mode / seed set per run)
+        self.chain_ws = None     # workspace of the chain ops (word 1: a bounded spin of the chain kernel timed out)
         self.streams = None      # RdbStreams feeding the chain ops
         self.z_ops = []          # layout ops that import explicit z tensors, in noise-layer order
         self.wgen = None
         self.chain_noise = False
+        self.graph_bound = False   # TrainPlan.enable_graph: the chain ops read their seed from the device
 
     def run(self, x, out, stream, seed=0, zs=None):
         arr = self.ops.array()
         arr[self.in_op].u.layout.nchw = x.data_ptr()
-        o = arr[self.out_op]
-        if o.kind == L.OP_CONV:
-            o.u.conv.nchw_out = out.data_ptr()
-        else:
-            o.u.layout.nchw = out.data_ptr()
+        set_nchw(arr[self.out_op], out.data_ptr())
         mode = L.NOISE_OFF
-        if not getattr(self, 'graph_bound', False):
+        if not self.graph_bound:
             for i in self.chain_ops:
                 ch = arr[i].u.rdb_chain
                 ch.noise_mode = L.NOISE_PHILOX if self.chain_noise else L.NOISE_OFF
@@ -467,7 +502,7 @@ class Plan:
 class Builder:
     """Emits the fused-conv sequence of RDB / RRDB / RRDBNet into a Plan."""
 
-    def __init__(self, wp, B, H, W, dtype, device, noise, variant):
+    def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1):
         self.wp = wp
         self.B, self.H, self.W = B, H, W
         self.dt_e, self.tdtype, self.cpg = _dt(dtype)
@@ -475,54 +510,58 @@ class Builder:
         self.device = device
         self.noise = noise            # bool: emit noise epilogues (training mode)
         self.variant = variant        # 'codes' | 'test_image'
+        self.kind = kind              # 'net' | 'rrdb' | 'rdb'
+        self.nb = nb                  # RRDBs
+        self.layers = NoiseLayers(variant, kind, nb, noise)
         self.plan = Plan()
-        self.n_noise = 0
+        self.bufs = self.plan.bufs    # everything the ops point at stays alive with the plan
         self.zbufs = []
 
     def buf(self, C_, H=None, W=None):
         b = G32(self.B, C_, H or self.H, W or self.W, self.dtype, self.device)
-        self.plan.bufs.append(b)
+        self.bufs.append(b)
         return b
 
-    def import_nchw(self, dst, C_, affine=None):
+    def upload(self, table):
+        t = upload_table(table, self.device)
+        self.bufs.append(t)
+        return t
+
+    def layout(self, ops, g, C_, to_g32):
+        """NCHW -> G32 (to_g32 = 1) or G32 -> NCHW layout op over channels [0, C_) of buffer g, appended to `ops`."""
         lo = L.esr_layout()
-        lo.dtype, lo.to_g32 = self.dt_e, 1
-        lo.B, lo.C, lo.H, lo.W = self.B, C_, dst.H, dst.W
-        lo.g32 = dst.view(0, C_)
-        return self.plan.ops.add(L.OP_LAYOUT, 'layout', lo)
+        lo.dtype, lo.to_g32 = self.dt_e, to_g32
+        lo.B, lo.C, lo.H, lo.W = self.B, C_, g.H, g.W
+        lo.g32 = g.view(0, C_)
+        return ops.add(L.OP_LAYOUT, 'layout', lo)
+
+    def import_nchw(self, dst, C_):
+        return self.layout(self.plan.ops, dst, C_, 1)
 
     def export_nchw(self, src, C_):
-        lo = L.esr_layout()
-        lo.dtype, lo.to_g32 = self.dt_e, 0
-        lo.B, lo.C, lo.H, lo.W = self.B, C_, src.H, src.W
-        lo.g32 = src.view(0, C_)
-        return self.plan.ops.add(L.OP_LAYOUT, 'layout', lo)
+        return self.layout(self.plan.ops, src, C_, 0)
 
-    def alloc_z(self, n):
+    def alloc_z(self, explicit_z):
         """Explicit-z staging: one 64-channel G32 buffer + import op per noise layer."""
         self.zbufs = []
-        for _ in range(n):
+        for _ in range(self.layers.total if explicit_z else 0):
             zb = self.buf(64)
             self.plan.z_ops.append(self.import_nchw(zb, 64))
             self.zbufs.append(zb)
 
-    def _noise(self, c, which):
-        """Attach noise layer (next id) to conv c as z1 (which=1) or z2 (which=2)."""
-        lid = self.n_noise
-        self.n_noise += 1
-        zb = self.zbufs[lid] if lid < len(self.zbufs) else None
-        if which == 1:
-            c.layer1 = lid
-            if zb is not None:
-                c.z1 = zb.view(0, 64)
-        else:
-            c.layer2 = lid
-            if zb is not None:
-                c.z2 = zb.view(0, 64)
+    def set_noise(self, c, slot, lid):
+        """Stage `slot` (1 / 2 / 3) of conv c multiplies by (1 + sigma * z[lid]); lid None: no noise there."""
+        if lid is None:
+            return
+        setattr(c, 'layer%d' % slot, lid)
+        if self.zbufs:
+            setattr(c, 'z%d' % slot, self.zbufs[lid].view(0, 64))
 
-    def rdb(self, prefix, bf, bn, rrdb_x=None, rrdb_noise=False):
+    def rdb(self, prefix, bf, bn, layer1=None, rrdb_x=None, layer2=None, aux=None):
         """ResidualDenseBlock_5C (block.py:260-268) over concat buffer ``bf`` (x in ch 0..63);
-        result -> ``bn`` channels 0..63.  ``rrdb_x``: fuse the RRDB tail (block.py:291)."""
+        result -> ``bn`` channels 0..63, through noise layer ``layer1``.  ``rrdb_x``: fuse the RRDB tail
+        (block.py:291) and its noise layer ``layer2``.  ``aux`` (training): 64-channel buffer that keeps the
+        pre-residual activations of conv2 / conv4, whose signs are the LeakyReLU masks of the backward."""
         e = self.wp.entries
         B, H, W, d = self.B, self.H, self.W, self.dt_e
         add = self.plan.ops.add_conv
@@ -532,78 +571,94 @@ class Builder:
         c = _conv(d, B, H, W, bf.view(0), 96, bf.view(96, 32), e[prefix + '.conv2.0'], L.ACT_LRELU)
         c.w1x1 = e[prefix + '.conv1x1'].w_ptr
         c.n1x1_groups = 64 // self.cpg
+        if aux is not None:
+            c.aux_out = aux.view(0, 32)
         add(c)
         # x3 = lrelu(conv3([x,x1,x2]))
         add(_conv(d, B, H, W, bf.view(0), 128, bf.view(128, 32), e[prefix + '.conv3.0'], L.ACT_LRELU))
         # x4 = lrelu(conv4([x..x3])) + x2                     (block.py:265-266)
         c = _conv(d, B, H, W, bf.view(0), 160, bf.view(160, 32), e[prefix + '.conv4.0'], L.ACT_LRELU)
         c.res1, c.alpha = bf.view(96, 32), 1.0
+        if aux is not None:
+            c.aux_out = aux.view(32, 32)
         add(c)
         # out = noise(conv5([x..x4]) * 0.2 + x)               (block.py:267-268)
         c = _conv(d, B, H, W, bf.view(0), 192, bn.view(0, 64), e[prefix + '.conv5.0'], L.ACT_NONE)
         c.res1, c.alpha = bf.view(0, 64), 0.2
-        if self.noise:
-            self._noise(c, 1)
+        self.set_noise(c, 1, layer1)
         if rrdb_x is not None:                                 # RRDB: out*0.2 + x (block.py:291)
             c.res2, c.beta = rrdb_x.view(0, 64), 0.2
-            if self.noise and rrdb_noise:                      # test_image/block.py:256
-                self._noise(c, 2)
+            self.set_noise(c, 2, layer2)                       # test_image/block.py:256
         i = add(c)
         if self.noise:
             self.plan.noise_ops.append(i)
 
-    def rrdb(self, prefix, x0, x1, x2):
-        """RRDB (block.py:287-291): x0 -> x1 -> x2 -> back into x0 (in place, pixel-local)."""
-        self.rdb(prefix + '.RDB1', x0, x1)
-        self.rdb(prefix + '.RDB2', x1, x2)
-        self.rdb(prefix + '.RDB3', x2, x0, rrdb_x=x0, rrdb_noise=(self.variant == 'test_image'))
+    def rrdb(self, prefix, i, x0, x1, x2):
+        """RRDB i (block.py:287-291): x0 -> x1 -> x2 -> back into x0 (in place, pixel-local)."""
+        ly = self.layers
+        self.rdb(prefix + '.RDB1', x0, x1, ly.rdb(i, 0))
+        self.rdb(prefix + '.RDB2', x1, x2, ly.rdb(i, 1))
+        self.rdb(prefix + '.RDB3', x2, x0, ly.rdb(i, 2), rrdb_x=x0, layer2=ly.rrdb(i))
+
+    def rrdb_chain_specs(self, prefix, i, xa, xb):
+        """RRDB i as three rdb_chain specs over two 64-channel slots: RDB1 xa -> xb, RDB2 xb -> xb (in place), RDB3
+        xb -> xa with the RRDB tail reading xa."""
+        ly = self.layers
+        return [(prefix + '.RDB1', xa, xb, None, ly.rdb(i, 0), None), (prefix + '.RDB2', xb, xb, None, ly.rdb(i, 1), None),
+                (prefix + '.RDB3', xb, xa, xa, ly.rdb(i, 2), ly.rrdb(i))]
+
+    def chain_workspace(self, B, H, W):
+        """The flag / counter workspace of chain launches over B images of H x W (zeroed once; the kernel leaves it
+        clean).  Returns (tensor, bytes)."""
+        ws_bytes = L.lib().esr_rdb_workspace_bytes(B, H, W)
+        ws = torch.zeros((ws_bytes + 3) // 4, dtype=torch.int32, device=self.device)
+        self.bufs.append(ws)
+        return ws, ws_bytes
+
+    def chain(self, ws, blk_t, k0, k1, dense, geom=None, mode=0, save_dense=0, bands=None):
+        """esr_rdb_chain over blocks [k0, k1) of the uploaded esr_rdb_block table blk_t.  geom: (B, H, W) of the launch
+        (default: the plan's); mode 0 / 1 / 2 = inference / training forward / backward; bands: (band_rows,
+        band_margin, img_H) of the banded form.  noise_mode and seed are set per run."""
+        ch = L.esr_rdb_chain()
+        ch.dtype = self.dt_e
+        ch.B, ch.H, ch.W = geom or (self.B, self.H, self.W)
+        ch.mode, ch.save_dense = mode, save_dense
+        ch.n_blocks, ch.noise_mode, ch.sigma = k1 - k0, L.NOISE_OFF, SIGMA
+        ch.dense = dense
+        ch.blocks = blk_t.data_ptr() + k0 * C.sizeof(L.esr_rdb_block)
+        ch.workspace, ch.workspace_bytes = ws[0].data_ptr(), ws[1]
+        if bands is not None:
+            ch.band_rows, ch.band_margin, ch.img_H = bands
+        return ch
 
     def rdb_chain(self, specs):
-        """ONE fused launch for a chain of dense blocks.  specs: list of (prefix, x_in, x_out, res2 or None,
-        rrdb_noise) over 64-channel G32 buffers; the 128-channel dense scratch is shared."""
+        """ONE fused launch for a chain of dense blocks.  specs: list of (prefix, x_in, x_out, res2 or None, layer1,
+        layer2) over 64-channel G32 buffers; the 128-channel dense scratch is shared."""
         P = self.plan
-        if P.streams is None:
-            P.streams = RdbStreams(self.wp, [s[0] for s in specs])
-            base = 0
-        else:
-            base = len(P.streams.prefixes)
+        if P.streams is not None:
             raise NotImplementedError('one chain per plan')
+        P.streams = RdbStreams(self.wp, [s[0] for s in specs])
         dense = self.buf(128)
         blocks = (L.esr_rdb_block * len(specs))()
-        ent = self.wp.entries
-        for i, (prefix, xi, xo, r2, rrdb_noise) in enumerate(specs):
+        for i, (prefix, xi, xo, r2, layer1, layer2) in enumerate(specs):
             b = blocks[i]
-            b.w = P.streams.w_ptr(base + i)
-            b.bias = P.streams.bias_ptr(base + i)
+            b.w, b.bias = P.streams.w_ptr(i), P.streams.bias_ptr(i)
             b.x_in, b.x_out = xi.view(0, 64), xo.view(0, 64)
             if r2 is not None:
                 b.res2 = r2.view(0, 64)
-            b.layer1 = b.layer2 = L.NO_LAYER
+            b.layer1, b.layer2 = _layer(layer1), _layer(layer2)
             # the output must be complete in memory when it is the chain's result or a later RRDB input
             later_res2 = any(s[3] is xo for s in specs[i + 1:])
             b.flags = L.RDB_FULL_OUT if (i == len(specs) - 1 or later_res2) else 0
-            if self.noise:
-                b.layer1 = self.n_noise
-                self.n_noise += 1
-                if r2 is not None and rrdb_noise:
-                    b.layer2 = self.n_noise
-                    self.n_noise += 1
-        blk_t = torch.frombuffer(bytearray(bytes(blocks)), dtype=torch.uint8).to(self.device)
-        ws_bytes = L.lib().esr_rdb_workspace_bytes(self.B, self.H, self.W)
-        ws = torch.zeros((ws_bytes + 3) // 4, dtype=torch.int32, device=self.device)
-        P.bufs.extend([blk_t, ws])
-        ch = L.esr_rdb_chain()
-        ch.dtype, ch.B, ch.H, ch.W = self.dt_e, self.B, self.H, self.W
-        ch.n_blocks, ch.noise_mode, ch.sigma = len(specs), L.NOISE_OFF, SIGMA
-        ch.dense = dense.view(0, 128)
-        ch.blocks, ch.workspace, ch.workspace_bytes = blk_t.data_ptr(), ws.data_ptr(), ws_bytes
-        i = P.ops.add(L.OP_RDB_CHAIN, 'rdb_chain', ch)
+        blk_t = self.upload(blocks)
+        ws = self.chain_workspace(self.B, self.H, self.W)
+        i = P.ops.add(L.OP_RDB_CHAIN, 'rdb_chain', self.chain(ws, blk_t, 0, len(specs), dense.view(0, 128)))
         P.chain_ops.append(i)
         P.chain_noise = self.noise
-        P.chain_ws = ws
+        P.chain_ws = ws[0]
         return i
 
-    def rdb_chain_banded(self, nb, geom, head):
+    def rdb_chain_banded(self, geom, head):
         """The trunk of an image too large for one chain launch: per RRDB (and per image of the batch) one launch
         over row bands.  RRDB i reads the 64-channel buffer xs[i % 2] and writes xs[(i + 1) % 2] — out of place: a
         band's margin rows are its neighbours' own rows, so nothing a band reads may change during the launch —
@@ -612,16 +667,14 @@ class Builder:
         P = self.plan
         S, m, nbands = geom
         hb = S + 2 * m
-        B, H, W = self.B, self.H, self.W
+        B, H, W, nb = self.B, self.H, self.W, self.nb
         tall = [G32(B, 64, nbands * S + 2 * m, W, self.dtype, self.device) for _ in range(2)]
         mid = G32(nbands, 64, hb, W, self.dtype, self.device)
         dense = G32(nbands, 128, hb, W, self.dtype, self.device)
-        P.bufs.extend(tall + [mid, dense])
+        self.bufs.extend(tall + [mid, dense])
         prefixes = ['model.1.sub.%d.RDB%d' % (i, j + 1) for i in range(nb) for j in range(3)]
         P.streams = RdbStreams(self.wp, prefixes)
-        ws_bytes = L.lib().esr_rdb_workspace_bytes(nbands, hb, W)
-        ws = torch.zeros((ws_bytes + 3) // 4, dtype=torch.int32, device=self.device)
-        P.bufs.append(ws)
+        ws = self.chain_workspace(nbands, hb, W)
         head(tall[0].view(0, 64, m))
 
         def band(buf, bi):
@@ -642,84 +695,89 @@ class Builder:
                     b.flags = 0
                 blocks[2].res2 = band(src, bi)
                 blocks[2].flags = L.RDB_FULL_OUT | L.RDB_BAND_OWN
-                blk_t = torch.frombuffer(bytearray(bytes(blocks)), dtype=torch.uint8).to(self.device)
-                P.bufs.append(blk_t)
-                ch = L.esr_rdb_chain()
-                ch.dtype, ch.B, ch.H, ch.W = self.dt_e, nbands, hb, W
-                ch.n_blocks, ch.noise_mode, ch.sigma = 3, L.NOISE_OFF, SIGMA
-                ch.dense = dense.view(0, 128)
-                ch.blocks, ch.workspace, ch.workspace_bytes = blk_t.data_ptr(), ws.data_ptr(), ws_bytes
-                ch.band_rows, ch.band_margin, ch.img_H = S, m, H
+                ch = self.chain(ws, self.upload(blocks), 0, 3, dense.view(0, 128), geom=(nbands, hb, W), bands=(S, m, H))
                 P.chain_ops.append(P.ops.add(L.OP_RDB_CHAIN, 'rdb_chain', ch))
         P.chain_noise = False
-        P.chain_ws = ws
+        P.chain_ws = ws[0]
         return tall[nb % 2].view(0, 64, m)
 
-    def n_noise_layers(self, nb):
-        return (4 if self.variant == 'test_image' else 3) * nb if self.noise else 0
+    def head(self, xin, in_nc, dst, fea):
+        """fea_conv (model.0) into the view dst, with a copy in fea for the trunk shortcut (block.py:84-86)."""
+        c = _conv(self.dt_e, self.B, self.H, self.W, xin.view(0), in_nc, dst, self.wp.entries['model.0'])
+        c.aux_out = fea.view(0, 64)
+        self.plan.ops.add_conv(c)
 
-    def rrdbnet(self, nb, in_nc, out_nc, explicit_z):
-        """RRDBNet x4 (architecture.py:47-78): fea_conv, nb x RRDB, LR_conv + trunk shortcut,
-        2 x (nearest x2 + conv + lrelu), HR_conv0 + lrelu, HR_conv1."""
+    def tail(self, x, fea, t, out_nc):
+        """LR_conv + trunk shortcut from the view x into t (None: a new buffer), 2 x (nearest x2 + conv + lrelu),
+        HR_conv0 + lrelu, HR_conv1 -> NCHW (architecture.py:66-78).  Returns the buffers the backward reads:
+        (T, U1, U2, U3)."""
         e = self.wp.entries
         B, H, W, d = self.B, self.H, self.W, self.dt_e
         P = self.plan
-        self.zbufs = []
-        if explicit_z and self.noise:
-            self.alloc_z(self.n_noise_layers(nb))
-        xin = self.buf(in_nc)
-        fea = self.buf(64)
-        P.in_op = self.import_nchw(xin, in_nc)
-        if nb and rdb_chain_ok(B, H, W, self.noise, explicit_z):
-            # fused trunk: two 64-channel slots + the chain's 128-channel dense scratch.  Per RRDB:
-            # RDB1 xa -> xb, RDB2 xb -> xb (in place), RDB3 xb -> xa with the RRDB tail reading xa.
-            xa, xb = self.buf(64), self.buf(64)
-            c = _conv(d, B, H, W, xin.view(0), in_nc, xa.view(0, 64), e['model.0'])
-            c.aux_out = fea.view(0, 64)
-            P.ops.add_conv(c)
-            specs = []
-            for i in range(nb):
-                pre = 'model.1.sub.%d' % i
-                specs.append((pre + '.RDB1', xa, xb, None, False))
-                specs.append((pre + '.RDB2', xb, xb, None, False))
-                specs.append((pre + '.RDB3', xb, xa, xa, self.variant == 'test_image'))
-            self.rdb_chain(specs)
-            x0, x1 = xa, xb
-        elif nb and not self.noise and use_rdb_bands(self.dt_e, H, W):
-            # more tiles than CUs (a DIV2K-sized LR image): the fused trunk in row bands, one launch per RRDB
-            def head(dst):
-                c = _conv(d, B, H, W, xin.view(0), in_nc, dst, e['model.0'])
-                c.aux_out = fea.view(0, 64)
-                P.ops.add_conv(c)
-            res, x1 = self.rdb_chain_banded(nb, rdb_band_geometry(H, W), head), self.buf(64)
-            c = _conv(d, B, H, W, res, 64, x1.view(0, 64), e['model.1.sub.%d' % nb])
-            c.res1, c.alpha = fea.view(0, 64), 1.0
-            P.ops.add_conv(c)
-            x0 = None
-        else:
-            x0, x1, x2 = self.buf(192), self.buf(192), self.buf(192)
-            c = _conv(d, B, H, W, xin.view(0), in_nc, x0.view(0, 64), e['model.0'])
-            c.aux_out = fea.view(0, 64)          # keep fea for the trunk shortcut (block.py:84-86)
-            P.ops.add_conv(c)
-            for i in range(nb):
-                self.rrdb('model.1.sub.%d' % i, x0, x1, x2)
-        if x0 is not None:
-            c = _conv(d, B, H, W, x0.view(0), 64, x1.view(0, 64), e['model.1.sub.%d' % nb])
-            c.res1, c.alpha = fea.view(0, 64), 1.0
-            P.ops.add_conv(c)
-        u1 = self.buf(64, 2 * H, 2 * W)
-        P.ops.add_conv(_conv(d, B, 2 * H, 2 * W, x1.view(0), 64, u1.view(0, 64), e['model.3'],
-                             L.ACT_LRELU, upsample=1))
-        u2 = self.buf(64, 4 * H, 4 * W)
-        P.ops.add_conv(_conv(d, B, 4 * H, 4 * W, u1.view(0), 64, u2.view(0, 64), e['model.6'],
-                             L.ACT_LRELU, upsample=1))
-        u3 = self.buf(64, 4 * H, 4 * W)
-        P.ops.add_conv(_conv(d, B, 4 * H, 4 * W, u2.view(0), 64, u3.view(0, 64), e['model.8'],
-                             L.ACT_LRELU))
+        t = self.buf(64) if t is None else t
+        c = _conv(d, B, H, W, x, 64, t.view(0, 64), e['model.1.sub.%d' % self.nb])
+        c.res1, c.alpha = fea.view(0, 64), 1.0
+        P.ops.add_conv(c)
+        u1, u2, u3 = self.buf(64, 2 * H, 2 * W), self.buf(64, 4 * H, 4 * W), self.buf(64, 4 * H, 4 * W)
+        P.ops.add_conv(_conv(d, B, 2 * H, 2 * W, t.view(0), 64, u1.view(0, 64), e['model.3'], L.ACT_LRELU, upsample=1))
+        P.ops.add_conv(_conv(d, B, 4 * H, 4 * W, u1.view(0), 64, u2.view(0, 64), e['model.6'], L.ACT_LRELU, upsample=1))
+        P.ops.add_conv(_conv(d, B, 4 * H, 4 * W, u2.view(0), 64, u3.view(0, 64), e['model.8'], L.ACT_LRELU))
         c = _conv(d, B, 4 * H, 4 * W, u3.view(0), 64, None, e['model.10'])
         c.nchw_out_c = out_nc
         P.out_op = P.ops.add_conv(c)
         P.out_shape = (B, out_nc, 4 * H, 4 * W)
+        return t, u1, u2, u3
+
+    def rrdbnet(self, in_nc, out_nc, explicit_z):
+        """RRDBNet x4 (architecture.py:47-78): fea_conv, nb x RRDB, LR_conv + trunk shortcut,
+        2 x (nearest x2 + conv + lrelu), HR_conv0 + lrelu, HR_conv1."""
+        B, H, W, nb = self.B, self.H, self.W, self.nb
+        P = self.plan
+        self.alloc_z(explicit_z)
+        xin = self.buf(in_nc)
+        fea = self.buf(64)
+        P.in_op = self.import_nchw(xin, in_nc)
+        if nb and rdb_chain_ok(B, H, W, self.noise, explicit_z):
+            # fused trunk: two 64-channel slots + the chain's 128-channel dense scratch
+            xa, xb = self.buf(64), self.buf(64)
+            self.head(xin, in_nc, xa.view(0, 64), fea)
+            self.rdb_chain([s for i in range(nb) for s in self.rrdb_chain_specs('model.1.sub.%d' % i, i, xa, xb)])
+            x, t = xa.view(0), xb
+        elif nb and not self.noise and use_rdb_bands(self.dt_e, H, W):
+            # more tiles than CUs (a DIV2K-sized LR image): the fused trunk in row bands, one launch per RRDB
+            x = self.rdb_chain_banded(rdb_band_geometry(H, W), lambda dst: self.head(xin, in_nc, dst, fea))
+            t = None
+        else:
+            x0, x1, x2 = self.buf(192), self.buf(192), self.buf(192)
+            self.head(xin, in_nc, x0.view(0, 64), fea)
+            for i in range(nb):
+                self.rrdb('model.1.sub.%d' % i, i, x0, x1, x2)
+            x, t = x0.view(0), x1
+        self.tail(x, fea, t, out_nc)
+        return P
+
+    def block_plan(self, explicit_z):
+        """Stand-alone ResidualDenseBlock_5C ('rdb') or RRDB ('rrdb') pass: NCHW in -> NCHW out."""
+        P = self.plan
+        self.alloc_z(explicit_z)
+        if rdb_chain_ok(self.B, self.H, self.W, self.noise, explicit_z):
+            xa, xb = self.buf(64), self.buf(64)
+            P.in_op = self.import_nchw(xa, 64)
+            if self.kind == 'rdb':
+                self.rdb_chain([('rdb', xa, xb, None, self.layers.rdb(0, 0), None)])
+            else:
+                self.rdb_chain(self.rrdb_chain_specs('rrdb', 0, xa, xb))
+            res = xb if self.kind == 'rdb' else xa
+        else:
+            x0, x1 = self.buf(192), self.buf(192)
+            P.in_op = self.import_nchw(x0, 64)
+            if self.kind == 'rdb':
+                self.rdb('rdb', x0, x1, self.layers.rdb(0, 0))
+            else:
+                self.rrdb('rrdb', 0, x0, x1, self.buf(192))
+            res = x1 if self.kind == 'rdb' else x0
+        P.out_op = self.export_nchw(res, 64)
+        P.out_shape = (self.B, 64, self.H, self.W)
         return P
 
 
@@ -736,6 +794,27 @@ def deterministic_wgrad():
     return os.environ.get('ESR_WGRAD_DET', '1') != '0'
 
 
+def _own_wgrad_regions(oplist, device, pick):
+    """A partial region of its own for every OP_WGRAD op of the list that pick(op) selects.  Returns the tensor that
+    holds the regions (or None)."""
+    arr = oplist.array()
+    needs = []
+    for i, o in enumerate(oplist.ops):
+        if o.kind == L.OP_WGRAD and pick(o):
+            n = L.lib().esr_wgrad_workspace_elems(C.cast(C.byref(arr[i]), C.c_void_p), 1)
+            needs.append((o, (int(n) + 63) // 64 * 64))
+    total = sum(n for _, n in needs)
+    if total <= 0:
+        return None
+    arena = torch.empty(total, dtype=torch.float32, device=device)
+    off = 0
+    for o, n in needs:
+        o.u.wgrad.partial, o.u.wgrad.partial_elems = (arena.data_ptr() + 4 * off, n) if n else (None, 0)
+        off += n
+    oplist._arr = None
+    return arena
+
+
 def attach_wgrad_arena(oplist, device, exclusive=False):
     """Give every fp16 weight-gradient op of a backward list the partial arena of the deterministic reduction
     (one arena per list: a slot only lives inside one esr_run_ops launch group, and the list's wgrad runs are
@@ -747,22 +826,7 @@ def attach_wgrad_arena(oplist, device, exclusive=False):
     if not wops:
         return None
     if exclusive:
-        arr = oplist.array()
-        needs = []
-        for i, o in enumerate(oplist.ops):
-            if o.kind == L.OP_WGRAD:
-                n = L.lib().esr_wgrad_workspace_elems(C.cast(C.byref(arr[i]), C.c_void_p), 1)
-                needs.append((o, (int(n) + 63) // 64 * 64))
-        total = sum(n for _, n in needs)
-        if total <= 0:
-            return None
-        arena = torch.empty(total, dtype=torch.float32, device=device)
-        off = 0
-        for o, n in needs:
-            o.u.wgrad.partial, o.u.wgrad.partial_elems = (arena.data_ptr() + 4 * off, n) if n else (None, 0)
-            off += n
-        oplist._arr = None
-        return arena
+        return _own_wgrad_regions(oplist, device, lambda o: True)
     need = L.lib().esr_wgrad_workspace_elems(C.cast(oplist.array(), C.c_void_p), len(oplist.ops))
     if need <= 0:
         return None
@@ -778,22 +842,7 @@ def attach_free_wgrad_regions(oplist, device):
     are in flight together, so each gets a partial region of its own.  Returns the tensor that holds them (or None)."""
     if not deterministic_wgrad():
         return None
-    arr = oplist.array()
-    needs = []
-    for i, o in enumerate(oplist.ops):
-        if o.kind == L.OP_WGRAD and (o.flags & L.OPF_SIDE_FREE):
-            n = L.lib().esr_wgrad_workspace_elems(C.cast(C.byref(arr[i]), C.c_void_p), 1)
-            needs.append((o, (int(n) + 63) // 64 * 64))
-    total = sum(n for _, n in needs)
-    if total <= 0:
-        return None
-    arena = torch.empty(total, dtype=torch.float32, device=device)
-    off = 0
-    for o, n in needs:
-        o.u.wgrad.partial, o.u.wgrad.partial_elems = (arena.data_ptr() + 4 * off, n) if n else (None, 0)
-        off += n
-    oplist._arr = None
-    return arena
+    return _own_wgrad_regions(oplist, device, lambda o: o.flags & L.OPF_SIDE_FREE)
 
 
 def current_stream():
@@ -905,6 +954,11 @@ def env_int(name, default, lo, hi):
     return n
 
 
+def spare_cus(B, H, W):
+    """CUs that a backward-chain launch over 4-row tiles leaves free."""
+    return L.lib().esr_rdb_max_tiles_per_image() - B * ((H + 3) // 4) * ((W + 31) // 32)
+
+
 def bwd_chain_split(B, H, W, nb):
     """Launches the fused backward chain of a training plan is cut into (runs of whole RRDBs; 1 = one launch).  More
     than one only when the chain's grid leaves at least half of the CUs idle (4-row tiles, at most cus / 2 of them):
@@ -912,9 +966,8 @@ def bwd_chain_split(B, H, W, nb):
     env = env_int('ESR_BWD_SPLIT', None, 1, max(1, nb))
     if env is not None:
         return env
-    cus = L.lib().esr_rdb_max_tiles_per_image()
-    tiles4 = B * ((H + 3) // 4) * ((W + 31) // 32)
-    return min(2, nb) if 2 * tiles4 <= cus else 1      # (train step, same box: 1 run 7.09 ms, 2 runs 7.01, 4 runs 7.06)
+    half_idle = 2 * spare_cus(B, H, W) >= L.lib().esr_rdb_max_tiles_per_image()
+    return min(2, nb) if half_idle else 1      # (train step, same box: 1 run 7.09 ms, 2 runs 7.01, 4 runs 7.06)
 
 
 def bwd_follow():
@@ -934,41 +987,11 @@ def use_rdb_wgrad():
 
 def build_block_plan(kind, wp, B, H, W, dtype, device, noise, variant, explicit_z):
     """Stand-alone ResidualDenseBlock_5C ('rdb') or RRDB ('rrdb') pass: NCHW in -> NCHW out."""
-    bld = Builder(wp, B, H, W, dtype, device, noise, variant)
-    P = bld.plan
-    n_noise = 0
-    if noise:
-        n_noise = 1 if kind == 'rdb' else (4 if variant == 'test_image' else 3)
-    if explicit_z and noise:
-        bld.alloc_z(n_noise)
-    if rdb_chain_ok(B, H, W, noise, explicit_z):
-        xa, xb = bld.buf(64), bld.buf(64)
-        P.in_op = bld.import_nchw(xa, 64)
-        if kind == 'rdb':
-            bld.rdb_chain([('rdb', xa, xb, None, False)])
-            P.out_op = bld.export_nchw(xb, 64)
-        else:
-            bld.rdb_chain([('rrdb.RDB1', xa, xb, None, False), ('rrdb.RDB2', xb, xb, None, False),
-                           ('rrdb.RDB3', xb, xa, xa, variant == 'test_image')])
-            P.out_op = bld.export_nchw(xa, 64)
-        P.out_shape = (B, 64, H, W)
-        return P
-    x0, x1 = bld.buf(192), bld.buf(192)
-    P.in_op = bld.import_nchw(x0, 64)
-    if kind == 'rdb':
-        bld.rdb('rdb', x0, x1)
-        P.out_op = bld.export_nchw(x1, 64)
-    else:
-        x2 = bld.buf(192)
-        bld.rrdb('rrdb', x0, x1, x2)
-        P.out_op = bld.export_nchw(x0, 64)
-    P.out_shape = (B, 64, H, W)
-    return P
+    return Builder(wp, B, H, W, dtype, device, noise, variant, kind).block_plan(explicit_z)
 
 
 def build_rrdbnet_plan(wp, nb, in_nc, out_nc, B, H, W, dtype, device, noise, variant, explicit_z):
-    bld = Builder(wp, B, H, W, dtype, device, noise, variant)
-    return bld.rrdbnet(nb, in_nc, out_nc, explicit_z)
+    return Builder(wp, B, H, W, dtype, device, noise, variant, 'net', nb).rrdbnet(in_nc, out_nc, explicit_z)
 
 
 # =================================================================================================
@@ -1120,8 +1143,7 @@ class TapMajorGrads:
             arr[i].cout, arr[i].cin, arr[i].ntap, arr[i].pair_begin = r[3], r[4], r[5], pairs
             begin += r[3] * r[4] * r[5]
             pairs += r[3] * r[4]
-        raw = bytes(arr)
-        table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.flat.device)
+        table = upload_table(arr, self.flat.device)
         self.tables = getattr(self, 'tables', []) + [table]
         up = L.esr_unpermute()
         up.table, up.n, up.total = table.data_ptr(), len(rows), begin
@@ -1137,6 +1159,7 @@ class TrainPlan:
         self.fwd = Plan()
         self.bwd = L.OpList()
         self.bufs = []
+        self.packs = None            # (WeightPack, DgradPack) the lists point into: kept alive with the plan (functional._train_plan)
         self.busy = False
         self.gy_op = None            # layout op importing dL/dy (NCHW fp32) in the backward list
         self.bwd_noise_ops = []      # backward conv ops that need (noise_mode, seed)
@@ -1144,15 +1167,20 @@ class TrainPlan:
         self.grad_views = None
         self.tapmajor = None
         self.gx_op = None            # op exporting dL/dx (NCHW fp32): a layout op (stand-alone blocks) or fea_conv's dgrad
+        self.gx_shape = None         # shape of dL/dx
         self.gx_begin = None         # whole generator: ops [gx_begin, end) produce dL/dx and run only when it is wanted
         self.segments = None         # segmented backward: [(op_end, elem_lo, elem_hi)] — after ops [.., op_end) the
-                                     # gradients in flat[elem_lo:elem_hi] are final (see build_rrdbnet_train_plan)
-        self.graph = False           # hipGraph replay with I/O bound to the static tensors below
+                                     # gradients in flat[elem_lo:elem_hi] are final (see TrainBuilder.close_segment)
         self.follow_op = None        # index of the ESR_OPF_FOLLOW weight-gradient op of the backward list (follow_spare: the CUs its
         self.follow_spare = 0        # chain leaves free; follow_wgs: the plan's default grid)
         self.follow_wgs = 0
         self.bwd_chain_ops = []      # indices of OP_RDB_CHAIN_BWD ops in the backward list (noise mode / seed per run)
+        self.bwd_chain_ws = None     # their workspace
         self.bwd_streams = None      # RdbBwdStreams feeding them
+        self.wgrad_arena = None      # partial sums of the deterministic weight-gradient reduction (attach_wgrad_arena)
+        self.wgrad_free_arena = None   # the same for the free-running runs (attach_free_wgrad_regions)
+        self.graph = False           # hipGraph replay with I/O bound to the static tensors below
+        self.x_static = self.out_static = self.gy_static = self.gx_static = self.seed_t = None
 
     def enable_graph(self, in_shape, device):
         """Bind every per-step pointer / scalar of both launch lists to fixed device buffers so the
@@ -1167,313 +1195,322 @@ class TrainPlan:
         self.gy_static = torch.empty(P.out_shape, **f32)
         self.gx_static = torch.empty(in_shape, **f32) if self.gx_op is not None else None
         self.seed_t = torch.zeros(1, dtype=torch.int64, device=device)
-        arr = P.ops.array()
+        chain_mode = L.NOISE_PHILOX if P.chain_noise else L.NOISE_OFF
+        arr, barr = P.ops.array(), self.bwd.array()
         arr[P.in_op].u.layout.nchw = self.x_static.data_ptr()
-        o = arr[P.out_op]
-        if o.kind == L.OP_CONV:
-            o.u.conv.nchw_out = self.out_static.data_ptr()
-        else:
-            o.u.layout.nchw = self.out_static.data_ptr()
-        for i in P.noise_ops:
-            arr[i].u.conv.noise_mode = L.NOISE_PHILOX
-            arr[i].u.conv.seed_dev = self.seed_t.data_ptr()
-        for i in P.chain_ops:
-            arr[i].u.rdb_chain.noise_mode = L.NOISE_PHILOX if P.chain_noise else L.NOISE_OFF
-            arr[i].u.rdb_chain.seed_dev = self.seed_t.data_ptr()
-        P.graph_bound = True         # Plan.run keeps its hands off the chain ops from here on
-        barr = self.bwd.array()
+        set_nchw(arr[P.out_op], self.out_static.data_ptr())
         barr[self.gy_op].u.layout.nchw = self.gy_static.data_ptr()
         if self.gx_op is not None:
-            if barr[self.gx_op].kind == L.OP_CONV:
-                barr[self.gx_op].u.conv.nchw_out = self.gx_static.data_ptr()
-            else:
-                barr[self.gx_op].u.layout.nchw = self.gx_static.data_ptr()
-        for i in self.bwd_noise_ops:
-            barr[i].u.conv.noise_mode = L.NOISE_PHILOX
-            barr[i].u.conv.seed_dev = self.seed_t.data_ptr()
-        for i in self.bwd_chain_ops:
-            barr[i].u.rdb_chain.noise_mode = L.NOISE_PHILOX if P.chain_noise else L.NOISE_OFF
-            barr[i].u.rdb_chain.seed_dev = self.seed_t.data_ptr()
+            set_nchw(barr[self.gx_op], self.gx_static.data_ptr())
+        for a, noise_ops, chain_ops in ((arr, P.noise_ops, P.chain_ops), (barr, self.bwd_noise_ops, self.bwd_chain_ops)):
+            for i in noise_ops:
+                a[i].u.conv.noise_mode = L.NOISE_PHILOX
+                a[i].u.conv.seed_dev = self.seed_t.data_ptr()
+            for i in chain_ops:
+                a[i].u.rdb_chain.noise_mode = chain_mode
+                a[i].u.rdb_chain.seed_dev = self.seed_t.data_ptr()
+        P.graph_bound = True         # Plan.run keeps its hands off the chain ops from here on
         self.graph = True
 
 
-def build_rrdbnet_train_plan(net, wp, dp, nb, in_nc, out_nc, B, H, W, dtype, device, noise, variant,
-                             explicit_z, kind='net', segmented=False):
-    """RRDBNet forward keeping every RDB concat buffer (+ pre-residual activations of conv2/conv4,
-    whose signs are the LeakyReLU masks) and the backward pass:
-      * input gradients = the same fused conv kernel over transposed/rotated weights, with the
-        LeakyReLU-mask / noise / residual-scale backward applied in its epilogue;
-      * weight/bias gradients = esr_conv_wgrad.
-    kind 'net' = the whole generator; 'rrdb' / 'rdb' = a stand-alone RRDB / ResidualDenseBlock_5C
-    (64-channel NCHW in and out, gradient w.r.t. the input returned): same block code, no head/tail.
-    segmented ('net' only): the backward list records, per RRDB (and for the tail / the first conv), the op
-    index after which that slice of the flat gradient buffer is final — data-parallel runs start its
-    all-reduce there, under the rest of the backward (TrainPlan.segments, functional._train_backward)."""
-    dt_e, tdtype, cpg = _dt(dtype)
-    block = kind != 'net'
-    nj = 1 if kind == 'rdb' else 3                 # dense blocks per RRDB
-    if block:
-        nb = 1
+# Where the input gradient of a dense block goes (TrainBuilder.block_exit).  dst: the buffer whose channels [0, 64) take
+# what runs on — the g_t of the block below it, dL/dx of a stand-alone block, or dL/dfea — through noise layer dst_layer;
+# skip_in: the RRDB's skip gradient, added when the block is RDB1; skip_out: the sum becomes the skip gradient of the
+# RRDB below it, through noise layer skip_layer — dst then takes 0.2 x that sum (the scaled third output of a conv).
+BlockExit = collections.namedtuple('BlockExit', 'dst dst_layer skip_in skip_out skip_layer', defaults=(None,) * 4)
 
-    def pkey(i, j):
-        if kind == 'rdb':
+
+class TrainBuilder(Builder):
+    """Emits the training forward of RRDBNet — every RDB concat buffer kept, + the pre-residual activations of conv2 /
+    conv4 or the chain's LeakyReLU masks — and the matching backward list into a TrainPlan.  One method per step;
+    build_rrdbnet_train_plan calls them in order."""
+
+    def __init__(self, wp, dp, nb, B, H, W, dtype, device, noise, variant, explicit_z, kind, segmented):
+        self.block = kind != 'net'                  # stand-alone RRDB / dense block: no head / tail, dL/dx returned
+        super().__init__(wp, B, H, W, dtype, device, noise, variant, kind, 1 if self.block else nb)
+        self.tp = TrainPlan()
+        self.plan, self.bwd, self.bufs = self.tp.fwd, self.tp.bwd, self.tp.bufs
+        self.dp = dp
+        self.nj = 1 if kind == 'rdb' else 3         # dense blocks per RRDB
+        self.explicit_z = explicit_z
+        self.segmented = bool(segmented) and not self.block
+        self.chained = self.nb > 0 and use_train_chain(self.dt_e, B, H, W, explicit_z)
+        self.fused_wgrad = self.dt_e == L.ESR_F16 and use_rdb_wgrad() and self.nb > 0
+
+    def pkey(self, i, j):
+        if self.kind == 'rdb':
             return 'rdb'
-        return ('rrdb.RDB%d' % (j + 1)) if kind == 'rrdb' else 'model.1.sub.%d.RDB%d' % (i, j + 1)
-    TP = TrainPlan()
-    P = TP.fwd
-    e = wp.entries
-    d = dt_e
-    per = 4 if variant == 'test_image' else 3
-    n_noise = ((1 if kind == 'rdb' else per * nb) if noise else 0)
+        return ('rrdb.RDB%d' % (j + 1)) if self.kind == 'rrdb' else 'model.1.sub.%d.RDB%d' % (i, j + 1)
 
-    def buf(C_, h=H, w=W):
-        b = G32(B, C_, h, w, dtype, device)
-        TP.bufs.append(b)
-        return b
+    def x_out(self, i, j):
+        """The buffer whose channels [0, 64) take the output of dense block (i, j): the next block's concat buffer, or
+        XF behind the last one.  (-1, nj - 1): what feeds the first block."""
+        if j < self.nj - 1:
+            return self.S[i][j + 1]
+        return self.S[i + 1][0] if i + 1 < self.nb else self.XF
 
-    def imp(ops, dst, C_):
-        lo = L.esr_layout()
-        lo.dtype, lo.to_g32 = dt_e, 1
-        lo.B, lo.C, lo.H, lo.W = B, C_, dst.H, dst.W
-        lo.g32 = dst.view(0, C_)
-        return ops.add(L.OP_LAYOUT, 'layout', lo)
-
-    zb = []
-    if noise and explicit_z:
-        for _ in range(n_noise):
-            z = buf(64)
-            P.z_ops.append(imp(P.ops, z, 64))
-            zb.append(z)
-
-    def set_noise(c, slot, lid):
-        """slot 1/2/3 of conv c multiplies by (1 + sigma * z[lid])."""
-        if not noise or lid is None:
-            return
-        setattr(c, 'layer%d' % slot, lid)
-        if zb:
-            setattr(c, 'z%d' % slot, zb[lid].view(0, 64))
+    def rrdb_x(self, i, j):
+        """The RRDB input that block (i, j) adds to its output when it closes an RRDB (block.py:291), else None."""
+        return self.S[i][0] if j == 2 and self.kind != 'rdb' else None
 
     # ------------------------------------------------------------------ forward
-    chain = nb > 0 and use_train_chain(dt_e, B, H, W, explicit_z)
-    S = [[buf(192) for _ in range(nj)] for _ in range(nb)]
-    AUX = [[buf(64) for _ in range(nj)] for _ in range(nb)] if not chain else None
-    XF = buf(64)                                   # output of the last RRDB
-    if block:
-        P.in_op = imp(P.ops, S[0][0], 64)          # x straight into the concat buffer's first slice
-    else:
-        xin, fea = buf(in_nc), buf(64)
-        P.in_op = imp(P.ops, xin, in_nc)
-        c = _conv(d, B, H, W, xin.view(0), in_nc, (S[0][0] if nb else XF).view(0, 64), e['model.0'])
-        c.aux_out = fea.view(0, 64)
-        P.ops.add_conv(c)
-    MASKS = None
-    if chain:
-        # ---- fused training forward: ONE esr_rdb_forward launch (mode 1) over all dense blocks; every block keeps
-        # its concat buffer S[i][j] = [x | x1..x4], its output (the next block's x) and its LeakyReLU masks
-        order = [(i, j) for i in range(nb) for j in range(nj)]
-        P.streams = RdbStreams(wp, [pkey(i, j) for i, j in order])
-        mbytes = int(L.lib().esr_rdb_mask_bytes(B, H, W))
-        MASKS = {ij: torch.empty(mbytes, dtype=torch.uint8, device=device) for ij in order}
-        TP.bufs.append(MASKS)
-        cblocks = (L.esr_rdb_block * len(order))()
+    def forward_head(self, in_nc):
+        P, nb, nj = self.plan, self.nb, self.nj
+        self.alloc_z(self.explicit_z)
+        self.S = [[self.buf(192) for _ in range(nj)] for _ in range(nb)]
+        self.AUX = [[self.buf(64) for _ in range(nj)] for _ in range(nb)] if not self.chained else None
+        self.XF = self.buf(64)                              # output of the last RRDB
+        if self.block:
+            P.in_op = self.import_nchw(self.S[0][0], 64)    # x straight into the concat buffer's first slice
+        else:
+            self.xin, self.fea = self.buf(in_nc), self.buf(64)
+            P.in_op = self.import_nchw(self.xin, in_nc)
+            self.head(self.xin, in_nc, self.x_out(-1, nj - 1).view(0, 64), self.fea)
+
+    def forward_blocks_chain(self):
+        """ONE esr_rdb_forward launch (mode 1) over all dense blocks; every block keeps its concat buffer S[i][j] =
+        [x | x1..x4], its output (the next block's x) and its LeakyReLU masks."""
+        P, ly = self.plan, self.layers
+        order = [(i, j) for i in range(self.nb) for j in range(self.nj)]
+        P.streams = RdbStreams(self.wp, [self.pkey(i, j) for i, j in order])
+        mbytes = int(L.lib().esr_rdb_mask_bytes(self.B, self.H, self.W))
+        self.masks = {ij: torch.empty(mbytes, dtype=torch.uint8, device=self.device) for ij in order}
+        self.bufs.append(self.masks)
+        blocks = (L.esr_rdb_block * len(order))()
         for n, (i, j) in enumerate(order):
-            bf = S[i][j]
-            bn = S[i][j + 1] if j < nj - 1 else (S[i + 1][0] if i + 1 < nb else XF)
-            b = cblocks[n]
+            bf, b = self.S[i][j], blocks[n]
             b.w, b.bias = P.streams.w_ptr(n), P.streams.bias_ptr(n)
-            b.x_in, b.x_out, b.dense = bf.view(0, 64), bn.view(0, 64), bf.view(64, 128)
-            b.mask = MASKS[(i, j)].data_ptr()
-            b.layer1 = (per * i + j) if noise else L.NO_LAYER
-            b.layer2 = L.NO_LAYER
-            if j == 2 and kind != 'rdb':
-                b.res2 = S[i][0].view(0, 64)
-                if noise and variant == 'test_image':
-                    b.layer2 = per * i + 3
+            b.x_in, b.x_out, b.dense = bf.view(0, 64), self.x_out(i, j).view(0, 64), bf.view(64, 128)
+            b.mask = self.masks[(i, j)].data_ptr()
+            b.layer1, b.layer2 = _layer(ly.rdb(i, j)), L.NO_LAYER
+            if self.rrdb_x(i, j) is not None:
+                b.res2, b.layer2 = self.rrdb_x(i, j).view(0, 64), _layer(ly.rrdb(i))
             b.flags = L.RDB_FULL_OUT
-        cblk_t = torch.frombuffer(bytearray(bytes(cblocks)), dtype=torch.uint8).to(device)
-        ws_bytes = L.lib().esr_rdb_workspace_bytes(B, H, W)
-        cws = torch.zeros((ws_bytes + 3) // 4, dtype=torch.int32, device=device)
-        TP.bufs.extend([cblk_t, cws])
-        ch = L.esr_rdb_chain()
-        ch.dtype, ch.B, ch.H, ch.W, ch.mode = dt_e, B, H, W, 1
-        ch.n_blocks, ch.noise_mode, ch.sigma, ch.save_dense = len(order), L.NOISE_OFF, SIGMA, 0
-        ch.dense = S[0][0].view(64, 128)                    # (geometry of every view; blocks carry their own)
-        ch.blocks, ch.workspace, ch.workspace_bytes = cblk_t.data_ptr(), cws.data_ptr(), ws_bytes
+        blk_t, ws = self.upload(blocks), self.chain_workspace(self.B, self.H, self.W)
+        # (dense: the geometry of every view; blocks carry their own)
+        ch = self.chain(ws, blk_t, 0, len(order), self.S[0][0].view(64, 128), mode=1)
         P.chain_ops.append(P.ops.add(L.OP_RDB_CHAIN, 'rdb_chain', ch))
-        P.chain_noise = bool(noise)
-        P.chain_ws = cws
-    for i in range(nb if not chain else 0):
-        for j in range(nj):
-            bf, ax = S[i][j], AUX[i][j]
-            bn = S[i][j + 1] if j < nj - 1 else (S[i + 1][0] if i + 1 < nb else XF)
-            p = pkey(i, j)
-            P.ops.add_conv(_conv(d, B, H, W, bf.view(0), 64, bf.view(64, 32), e[p + '.conv1.0'], L.ACT_LRELU))
-            c = _conv(d, B, H, W, bf.view(0), 96, bf.view(96, 32), e[p + '.conv2.0'], L.ACT_LRELU)
-            c.w1x1, c.n1x1_groups = e[p + '.conv1x1'].w_ptr, 64 // cpg
-            c.aux_out = ax.view(0, 32)
-            P.ops.add_conv(c)
-            P.ops.add_conv(_conv(d, B, H, W, bf.view(0), 128, bf.view(128, 32), e[p + '.conv3.0'], L.ACT_LRELU))
-            c = _conv(d, B, H, W, bf.view(0), 160, bf.view(160, 32), e[p + '.conv4.0'], L.ACT_LRELU)
-            c.res1, c.alpha = bf.view(96, 32), 1.0
-            c.aux_out = ax.view(32, 32)
-            P.ops.add_conv(c)
-            c = _conv(d, B, H, W, bf.view(0), 192, bn.view(0, 64), e[p + '.conv5.0'], L.ACT_NONE)
-            c.res1, c.alpha = bf.view(0, 64), 0.2
-            set_noise(c, 1, per * i + j)
-            if j == 2 and kind != 'rdb':
-                c.res2, c.beta = S[i][0].view(0, 64), 0.2
-                if variant == 'test_image':
-                    set_noise(c, 2, per * i + 3)
-            k = P.ops.add_conv(c)
-            if noise:
-                P.noise_ops.append(k)
-    if block:
-        lo = L.esr_layout()
-        lo.dtype, lo.to_g32 = dt_e, 0
-        lo.B, lo.C, lo.H, lo.W = B, 64, H, W
-        lo.g32 = XF.view(0, 64)
-        P.out_op = P.ops.add(L.OP_LAYOUT, 'layout', lo)
-        P.out_shape = (B, 64, H, W)
-    T_ = buf(64) if not block else None
-    if not block:
-        c = _conv(d, B, H, W, XF.view(0), 64, T_.view(0, 64), e['model.1.sub.%d' % nb])
-        c.res1, c.alpha = fea.view(0, 64), 1.0
-        P.ops.add_conv(c)
-        U1, U2, U3 = buf(64, 2 * H, 2 * W), buf(64, 4 * H, 4 * W), buf(64, 4 * H, 4 * W)
-        P.ops.add_conv(_conv(d, B, 2 * H, 2 * W, T_.view(0), 64, U1.view(0, 64), e['model.3'], L.ACT_LRELU, upsample=1))
-        P.ops.add_conv(_conv(d, B, 4 * H, 4 * W, U1.view(0), 64, U2.view(0, 64), e['model.6'], L.ACT_LRELU, upsample=1))
-        P.ops.add_conv(_conv(d, B, 4 * H, 4 * W, U2.view(0), 64, U3.view(0, 64), e['model.8'], L.ACT_LRELU))
-        c = _conv(d, B, 4 * H, 4 * W, U3.view(0), 64, None, e['model.10'])
-        c.nchw_out_c = out_nc
-        P.out_op = P.ops.add_conv(c)
-        P.out_shape = (B, out_nc, 4 * H, 4 * W)
+        P.chain_noise = bool(self.noise)
+        P.chain_ws = ws[0]
+
+    def forward_blocks_convs(self):
+        ly = self.layers
+        for i in range(self.nb):
+            for j in range(self.nj):
+                self.rdb(self.pkey(i, j), self.S[i][j], self.x_out(i, j), ly.rdb(i, j), rrdb_x=self.rrdb_x(i, j),
+                         layer2=ly.rrdb(i), aux=self.AUX[i][j])
+
+    def forward_exit(self, out_nc):
+        if self.block:
+            self.plan.out_op = self.export_nchw(self.XF, 64)
+            self.plan.out_shape = (self.B, 64, self.H, self.W)
+        else:
+            self.T, self.U1, self.U2, self.U3 = self.tail(self.XF.view(0), self.fea, None, out_nc)
 
     # ------------------------------------------------------------------ gradient storage
-    plist = [(k, w, b_) for k, w, b_ in net._conv_list()]
-    sizes = []
-    for k, w, b_ in plist:
-        sizes.append(w.numel())
-        if b_ is not None:
-            sizes.append(b_.numel())
-    TP.grad_flat = torch.zeros(sum(sizes), dtype=torch.float32, device=device)
-    views, off, gptr, goff = [], 0, {}, {}
-    TP.tapmajor = TapMajorGrads(TP.grad_flat) if dt_e == L.ESR_F16 else None
-    for k, w, b_ in plist:
-        gw = TP.grad_flat[off:off + w.numel()].view_as(w)
-        goff[k] = off
-        off += w.numel()
-        gb = None
-        if b_ is not None:
-            gb = TP.grad_flat[off:off + b_.numel()].view_as(b_)
-            off += b_.numel()
-        views.append((gw, gb))
-        gptr[k] = (gw.data_ptr(), gb.data_ptr() if gb is not None else None)
-    TP.grad_views = views
-    segmented = bool(segmented) and not block
-    gend = {}
-    for k, w, b_ in plist:
-        gend[k] = goff[k] + w.numel() + (b_.numel() if b_ is not None else 0)
-    segs = []
+    def grad_store(self, net):
+        """The flat fp32 gradient buffer with one view per parameter, in net._conv_list() order, and the tap-major
+        staging of the fp16 weight gradients."""
+        tp = self.tp
+        self.plist = list(net._conv_list())
+        total = sum(w.numel() + (b_.numel() if b_ is not None else 0) for _, w, b_ in self.plist)
+        tp.grad_flat = torch.zeros(total, dtype=torch.float32, device=self.device)
+        tp.tapmajor = TapMajorGrads(tp.grad_flat) if self.dt_e == L.ESR_F16 else None
+        tp.grad_views, self.gptr, self.goff, self.gend, off = [], {}, {}, {}, 0
+        for k, w, b_ in self.plist:
+            gw = tp.grad_flat[off:off + w.numel()].view_as(w)
+            self.goff[k] = off
+            off += w.numel()
+            gb = None
+            if b_ is not None:
+                gb = tp.grad_flat[off:off + b_.numel()].view_as(b_)
+                off += b_.numel()
+            self.gend[k] = off
+            tp.grad_views.append((gw, gb))
+            self.gptr[k] = (gw.data_ptr(), gb.data_ptr() if gb is not None else None)
+        self.segs = []
 
-    def close_segment(prefixes):
-        """Everything the ops so far produce for the parameters whose key starts with one of `prefixes` is
-        final: rewrite the tap-major pieces of that span, record the boundary."""
-        if not segmented:
+    def close_segment(self, prefixes):
+        """Segmented backward (data-parallel runs start a slice's all-reduce under the rest of the backward): everything
+        the ops so far produce for the parameters whose key starts with one of `prefixes` is final: rewrite the
+        tap-major pieces of that span, record the boundary."""
+        if not self.segmented:
             return
-        ks_ = [k for k, _, _ in plist if any(k == p_ or k.startswith(p_ + '.') for p_ in prefixes)]
+        goff, gend = self.goff, self.gend
+        ks_ = [k for k, _, _ in self.plist if any(k == p_ or k.startswith(p_ + '.') for p_ in prefixes)]
         lo, hi = min(goff[k] for k in ks_), max(gend[k] for k in ks_)
         assert hi - lo == sum(gend[k] - goff[k] for k in ks_), 'segment parameters must tile one span'
-        if TP.tapmajor is not None:
-            up = TP.tapmajor.op(lo, hi)
-            if up is not None:
-                Bk.add(L.OP_UNPERMUTE, 'unpermute', up)
-        segs.append((len(Bk.ops), lo, hi))
+        self.unpermute(lo, hi)
+        self.segs.append((len(self.bwd.ops), lo, hi))
 
-    # ------------------------------------------------------------------ backward
-    Bk = TP.bwd
-    de = dp.entries
+    def unpermute(self, lo=None, hi=None):
+        up = self.tp.tapmajor.op(lo, hi) if self.tp.tapmajor is not None else None
+        if up is not None:
+            self.bwd.add(L.OP_UNPERMUTE, 'unpermute', up)
 
-    def dconv(Ho, Wo, src, src_ch, dst, key, **kw):
-        c = _conv(d, B, Ho, Wo, src, src_ch, dst, de[key], L.ACT_NONE, **kw)
+    # ------------------------------------------------------------------ backward: pieces
+    def dconv(self, Ho, Wo, src, src_ch, dst, key, **kw):
+        c = _conv(self.dt_e, self.B, Ho, Wo, src, src_ch, dst, self.dp.entries[key], L.ACT_NONE, **kw)
         c.bias = None
         return c
 
-    def add_b(c, noisy=False):
-        k = Bk.add_conv(c)
-        if noisy and noise:
-            TP.bwd_noise_ops.append(k)
+    def add_b(self, c, noisy=False):
+        k = self.bwd.add_conv(c)
+        if noisy and self.noise:
+            self.tp.bwd_noise_ops.append(k)
         return k
 
-    deferred = None
-
-    def wgrad(key, g, gin, Hh, Ww, cout, cin, ks=3, ups=0, scale=1.0):
+    def wgrad(self, key, g, gin, Hh, Ww, cout, cin, ks=3, ups=0, scale=1.0):
+        """The esr_wgrad of conv `key`: gradient view g, saved input view gin."""
+        tm = self.tp.tapmajor
         wg = L.esr_wgrad()
-        wg.dtype, wg.ks, wg.stride, wg.upsample = dt_e, ks, 1, ups
-        wg.B, wg.H, wg.W = B, Hh, Ww
+        wg.dtype, wg.ks, wg.stride, wg.upsample = self.dt_e, ks, 1, ups
+        wg.B, wg.H, wg.W = self.B, Hh, Ww
         wg.cout, wg.cin = cout, cin
         wg.g, wg.in_ = g, gin
-        wg.dw, wg.dbias = gptr[key]
-        if TP.tapmajor is not None and ks == 3:
-            wg.dw, wg.tap_major = TP.tapmajor.slot(goff[key], cout, cin), 1
+        wg.dw, wg.dbias = self.gptr[key]
+        if tm is not None and ks == 3:
+            wg.dw, wg.tap_major = tm.slot(self.goff[key], cout, cin), 1
         wg.scale = scale
-        if deferred is not None:
-            deferred.append(wg)      # emitted as one run at the end of the block (one batched launch)
-        else:
-            # head / tail convs: their gradient and input buffers are written once per backward pass and their slots of
-            # the gradient buffer are read only behind the list's unpermute, so these launches run next to the main
-            # chain WITHOUT ordering among themselves (ESR_OPF_SIDE_FREE: up to three in flight, each with its own
-            # partial region — attach_free_wgrad_regions).  Round 5: as ordered side runs the main stream waited for
-            # run k - 1 before forking run k — at training crops a 70 us weight gradient per 25 us dgrad conv, i.e.
-            # the tail's backward took 0.4 ms of the step's critical path instead of 0.15
-            Bk.add(L.OP_WGRAD, 'wgrad', wg, flags=(_SIDE | _SIDE_FREE) if _SIDE else 0)
+        return wg
 
-    if block:
-        GY = buf(64)
-        TP.gy_op = imp(Bk, GY, 64)
-        GTt = None
-    else:
-        GY = buf(out_nc, 4 * H, 4 * W)
-        TP.gy_op = imp(Bk, GY, out_nc)
-        GA8, GA6 = buf(64, 4 * H, 4 * W), buf(64, 4 * H, 4 * W)
-        GA3 = buf(64, 2 * H, 2 * W)
-        GTt = buf(64)                               # dL/dT (trunk output)
-    gA = [buf(64), buf(64)]                         # RRDB skip gradient A(i), ping-pong
-    # The six weight gradients of a block run on the side stream, concurrently with the NEXT block's
-    # dgrad chain (both are latency-bound, ~64-workgroup launches at training sizes), and are joined
-    # before the block after that starts: what they read (g_t, GA, G[96:128]) rotates so that the
-    # chain running next to them writes other buffers — g_t through 3, G/GA through 2.
-    # Gather-form dgrad (block._rdb_gathers): per block one 224-channel gradient concat
-    #   Q = [g_t (64) | g_a4 | g_a3 | g_a2 | g_a1 | g_x2 raw]   (32 each)
-    # that the slice convs read as a growing prefix and each fills one slice of — the dense
-    # connectivity mirrored, no read-modify-write of an accumulator.  Q rotates through 3 buffers: the
-    # block's weight gradients read it on the side stream while the next block runs, and the block
-    # after that is the first to overwrite it (its predecessor already writes ITS g_t into slot 0).
-    # The side runs are forked once per RRDB (its three blocks' 18 weight gradients in one run: every fork costs the
-    # main stream an event record + wait, ~11 us of idle chip at LR sizes) and joined at the next fork, so a block's
-    # Q has to survive two groups: 2 * nj + 1 buffers.
-    NQ = 2 * nj + 1 if not chain else nb * nj       # fused backward: every block keeps its Q for the weight gradients
-    Qs = [buf(224) for _ in range(NQ)]
-    gT = [q for q in Qs]                            # g_t of a block = channels [0,64) of its Q
-    X4 = buf(32) if not chain else None             # raw g_x4 (identity path x4 = lrelu(a4) + x2)
-    GF = buf(64)                                    # dL/dfea
+    def free_wgrad(self, *a, **kw):
+        """Weight gradient of a head / tail conv.  Their gradient and input buffers are written once per backward pass
+        and their slots of the gradient buffer are read only behind the list's unpermute, so these launches run next
+        to the main chain WITHOUT ordering among themselves (ESR_OPF_SIDE_FREE: up to three in flight, each with its
+        own partial region — attach_free_wgrad_regions).  Round 5: as ordered side runs the main stream waited for
+        run k - 1 before forking run k — at training crops a 70 us weight gradient per 25 us dgrad conv, i.e. the
+        tail's backward took 0.4 ms of the step's critical path instead of 0.15."""
+        self.bwd.add(L.OP_WGRAD, 'wgrad', self.wgrad(*a, **kw), flags=(_SIDE | _SIDE_FREE) if _SIDE else 0)
 
-    if block:
-        # Entry of the chain: the incoming gradient through the block's own tail.
-        #   rdb : y = (0.2 x5 + x) n            -> g_t = g_y n
-        #   rrdb: y = ((t3 n2) 0.2 + x) [n3']   -> skip gradient A = g_y [n3'],  g_t3 = 0.2 A n2
-        # = a 1x1 identity "conv" (key '__eye') whose epilogue applies the noise / scale stages.
-        c = dconv(H, W, GY.view(0), 64, None, '__eye')
-        if kind == 'rdb':
-            c.out = gT[0].view(0, 64)
-            set_noise(c, 2, 0)
+    def rdb_wgrad_block(self, i, j, Q):
+        """The six weight gradients of dense block (i, j) from its saved concat buffer and its gradient concat Q."""
+        p = self.pkey(i, j)
+        wb = L.esr_rdb_wgrad_block()
+        wb.in_, wb.q = self.S[i][j].view(0, 192), Q.view(0, 224)
+        for k in range(5):
+            key = p + '.conv%d.0' % (k + 1)
+            wb.dw[k] = self.tp.tapmajor.slot(self.goff[key], 64 if k == 4 else 32, 64 + 32 * k)
+            wb.db[k] = self.gptr[key][1]
+        wb.dw[5] = self.gptr[p + '.conv1x1'][0]
+        return wb
+
+    def rdb_wgrad_arena(self, *n_blocks):
+        """Per-task partial sums of the deterministic two-stage reduction of esr_rdb_wgrad passes over n_blocks blocks
+        (several counts: one arena that fits each; the need is not monotonic in the block count: fewer blocks -> fewer
+        images per task -> more slots)."""
+        need = max(int(L.lib().esr_rdb_wgrad_workspace_elems(self.B, self.H, self.W, n)) for n in n_blocks)
+        arena = torch.empty(need, dtype=torch.float32, device=self.device)
+        self.bufs.append(arena)
+        return arena
+
+    def add_rdb_wgrad(self, grp, arena, flags=0, max_wg=0):
+        """ONE esr_rdb_wgrad pass over the esr_rdb_wgrad_blocks of grp."""
+        rw = L.esr_rdb_wgrad()
+        rw.dtype, rw.B, rw.H, rw.W = self.dt_e, self.B, self.H, self.W
+        rw.n_blocks, rw.tap_major, rw.scale5, rw.scale = len(grp), 1, 0.2, 1.0
+        rw.blocks = self.upload((L.esr_rdb_wgrad_block * len(grp))(*grp)).data_ptr()
+        rw.partial, rw.partial_elems = arena.data_ptr(), arena.numel()
+        rw.max_workgroups = max_wg
+        return self.bwd.add(L.OP_RDB_WGRAD, 'rdb_wgrad', rw, flags=flags)
+
+    def bwd_index(self, i, j):
+        """Position of dense block (i, j) in backward order."""
+        return (self.nb - 1 - i) * self.nj + (self.nj - 1 - j)
+
+    def Q(self, n):
+        """The gradient concat of the n-th block in backward order (the fused backward keeps one per block, the
+        per-conv backward rotates: backward_buffers)."""
+        return self.Qs[n % len(self.Qs)]
+
+    def block_exit(self, i, j):
+        """Where the input gradient of dense block (i, j) goes.  The RRDB skip gradient A(i) ping-pongs through gA,
+        starting with gA[0] for the last RRDB."""
+        ly, below = self.layers, self.Q(self.bwd_index(i, j) + 1)
+        if j > 0:                       # g_x = g_y of RDB j - 1 -> its g_t = g_y * n
+            return BlockExit(below, ly.rdb(i, j - 1))
+        if self.kind == 'rdb':
+            return BlockExit(self.GX)
+        skip_in = self.gA[(self.nb - 1 - i) % 2]
+        if self.block:
+            return BlockExit(self.GX, skip_in=skip_in)
+        if i > 0:                       # through the tail of RRDB i - 1: A(i - 1) = g [n3'], g_t3 = 0.2 A n2
+            return BlockExit(below, ly.rdb(i - 1, 2), skip_in, self.gA[(self.nb - i) % 2], ly.rrdb(i - 1))
+        return BlockExit(self.GF, skip_in=skip_in)
+
+    def exit_to_block(self, x, b):
+        """BlockExit -> esr_rdb_block of the fused backward (its kernel scales x_out when there is an out_a)."""
+        b.x_out, b.layer1 = x.dst.view(0, 64), _layer(x.dst_layer)
+        b.layer2 = _layer(x.skip_layer)
+        if x.skip_in is not None:
+            b.res2 = x.skip_in.view(0, 64)
+        if x.skip_out is not None:
+            b.out_a = x.skip_out.view(0, 64)
+
+    def exit_to_conv(self, x, c):
+        """BlockExit -> the slice-x conv that closes a block of the per-conv backward."""
+        if x.skip_in is not None:
+            c.res2, c.beta = x.skip_in.view(0, 64), 1.0
+        if x.skip_out is None:
+            c.out = x.dst.view(0, 64)
+            self.set_noise(c, 2, x.dst_layer)
         else:
-            c.out = gA[0].view(0, 64)
-            if variant == 'test_image':
-                set_noise(c, 2, 3)
-            c.out3, c.gamma = gT[0].view(0, 64), 0.2
-            set_noise(c, 3, 2)
-        add_b(c, noisy=True)
-    else:
+            c.out = x.skip_out.view(0, 64)
+            self.set_noise(c, 2, x.skip_layer)
+            c.out3, c.gamma = x.dst.view(0, 64), 0.2
+            self.set_noise(c, 3, x.dst_layer)
+
+    # ------------------------------------------------------------------ backward: steps
+    def backward_buffers(self, out_nc):
+        H, W = self.H, self.W
+        if self.block:
+            self.GY = self.buf(64)
+            self.tp.gy_op = self.layout(self.bwd, self.GY, 64, 1)
+        else:
+            self.GY = self.buf(out_nc, 4 * H, 4 * W)
+            self.tp.gy_op = self.layout(self.bwd, self.GY, out_nc, 1)
+            self.GA8, self.GA6 = self.buf(64, 4 * H, 4 * W), self.buf(64, 4 * H, 4 * W)
+            self.GA3 = self.buf(64, 2 * H, 2 * W)
+            self.GTt = self.buf(64)                     # dL/dT (trunk output)
+        # The six weight gradients of a block run on the side stream, concurrently with the NEXT block's
+        # dgrad chain (both are latency-bound, ~64-workgroup launches at training sizes), and are joined
+        # before the block after that starts: what they read (g_t, GA, G[96:128]) rotates so that the
+        # chain running next to them writes other buffers — g_t through 3, G/GA through 2.
+        # Gather-form dgrad (block._rdb_gathers): per block one 224-channel gradient concat
+        #   Q = [g_t (64) | g_a4 | g_a3 | g_a2 | g_a1 | g_x2 raw]   (32 each)
+        # that the slice convs read as a growing prefix and each fills one slice of — the dense
+        # connectivity mirrored, no read-modify-write of an accumulator.  Q rotates through 3 buffers: the
+        # block's weight gradients read it on the side stream while the next block runs, and the block
+        # after that is the first to overwrite it (its predecessor already writes ITS g_t into slot 0).
+        # The side runs are forked once per RRDB (its three blocks' 18 weight gradients in one run: every fork costs the
+        # main stream an event record + wait, ~11 us of idle chip at LR sizes) and joined at the next fork, so a block's
+        # Q has to survive two groups: 2 * nj + 1 buffers.
+        # Fused backward: every block keeps its Q for the weight gradients.
+        nj = self.nj
+        self.gA = [self.buf(64), self.buf(64)]          # RRDB skip gradient A(i), ping-pong
+        self.Qs = [self.buf(224) for _ in range(2 * nj + 1 if not self.chained else self.nb * nj)]
+        self.X4 = self.buf(32) if not self.chained else None     # raw g_x4 (identity path x4 = lrelu(a4) + x2)
+        self.GF = self.buf(64)                          # dL/dfea
+
+    def backward_entry_block(self):
+        """Entry of a stand-alone block: the incoming gradient through the block's own tail.
+          rdb : y = (0.2 x5 + x) n            -> g_t = g_y n
+          rrdb: y = ((t3 n2) 0.2 + x) [n3']   -> skip gradient A = g_y [n3'],  g_t3 = 0.2 A n2
+        = a 1x1 identity "conv" (key '__eye') whose epilogue applies the noise / scale stages."""
+        ly = self.layers
+        c = self.dconv(self.H, self.W, self.GY.view(0), 64, None, '__eye')
+        if self.kind == 'rdb':
+            self.exit_to_conv(BlockExit(self.Q(0), ly.rdb(0, 0)), c)
+        else:
+            self.exit_to_conv(BlockExit(self.Q(0), ly.rdb(0, 2), None, self.gA[0], ly.rrdb(0)), c)
+        self.add_b(c, noisy=True)
+
+    def backward_tail(self, out_nc):
+        """HR_conv1 .. LR_conv backwards: dL/dy -> the skip gradient and g_t of the last RRDB (nb = 0: dL/dfea)."""
+        H, W, nb, ly = self.H, self.W, self.nb, self.layers
+        dconv, add_b, wgrad = self.dconv, self.add_b, self.free_wgrad
+        T_, U1, U2, U3 = self.T, self.U1, self.U2, self.U3
+        GY, GA8, GA6, GA3, GTt = self.GY, self.GA8, self.GA6, self.GA3, self.GTt
         # HR_conv1 (model.10): u3 -> y
         wgrad('model.10', GY.view(0, out_nc), U3.view(0, 64), 4 * H, 4 * W, out_nc, 64)
         c = dconv(4 * H, 4 * W, GY.view(0), out_nc, None, 'model.10')
@@ -1494,275 +1531,228 @@ def build_rrdbnet_train_plan(net, wp, dp, nb, in_nc, out_nc, B, H, W, dtype, dev
         add_b(dconv(H, W, GA3.view(0), 64, GTt.view(0, 64), 'model.3', ks=4, stride=2))
         # LR_conv (model.1.sub.nb): XF -> T - fea
         lrk = 'model.1.sub.%d' % nb
-        wgrad(lrk, GTt.view(0, 64), XF.view(0, 64), H, W, 64, 64)
-        c = dconv(H, W, GTt.view(0), 64, gA[0].view(0, 64) if nb else GF.view(0, 64), lrk)
+        wgrad(lrk, GTt.view(0, 64), self.XF.view(0, 64), H, W, 64, 64)
+        c = dconv(H, W, GTt.view(0), 64, None, lrk)
         if nb:
-            if variant == 'test_image':
-                set_noise(c, 2, per * (nb - 1) + 3)
-            c.out3, c.gamma = gT[0].view(0, 64), 0.2
-            set_noise(c, 3, per * (nb - 1) + 2)
+            self.exit_to_conv(BlockExit(self.Q(0), ly.rdb(nb - 1, 2), None, self.gA[0], ly.rrdb(nb - 1)), c)
         else:
+            c.out = self.GF.view(0, 64)
             c.res1 = GTt.view(0, 64)                    # fea feeds both the trunk and the shortcut
         add_b(c, noisy=bool(nb))
-        close_segment(['model.1.sub.%d' % nb, 'model.3', 'model.6', 'model.8', 'model.10'])
-    ca, ct = 0, 0
-    fused_wgrad = dt_e == L.ESR_F16 and use_rdb_wgrad() and nb > 0
-    if fused_wgrad and not chain:
-        # per-task partial sums of the deterministic two-stage reduction: one arena, reused by every RRDB's pass
-        # (the passes are ordered on the side stream; a slot only lives inside one pass)
-        rdbw_arena = torch.empty(int(L.lib().esr_rdb_wgrad_workspace_elems(B, H, W, nj)), dtype=torch.float32, device=device)
-        TP.bufs.append(rdbw_arena)
-    GX = buf(64) if block else None                 # dL/dx of a stand-alone block
-    if chain:
-        # ---- fused backward: ONE esr_rdb_backward launch over the dense blocks in backward order (block n reads its
-        # g_t from Qs[n][0:64], leaves g_a4..g_a1 and the raw g_x2 in Qs[n][64:224], and writes the next block's g_t),
-        # then the weight gradients of all blocks in esr_rdb_wgrad passes over (S, Q)
+        self.close_segment([lrk, 'model.3', 'model.6', 'model.8', 'model.10'])
+
+    def backward_blocks(self):
+        if self.fused_wgrad and not self.chained:
+            # per-RRDB passes of the per-conv backward: one arena, reused by every pass (the passes are ordered on the
+            # side stream; a slot only lives inside one pass)
+            self.rdbw_arena = self.rdb_wgrad_arena(self.nj)
+        self.GX = self.buf(64) if self.block else None      # dL/dx of a stand-alone block
+        if self.chained:
+            self.backward_blocks_chain()
+        else:
+            self.backward_blocks_convs()
+
+    def backward_blocks_chain(self):
+        """Fused backward: esr_rdb_backward over the dense blocks in backward order (block n reads its g_t from
+        Qs[n][0:64], leaves g_a4..g_a1 and the raw g_x2 in Qs[n][64:224], and writes the next block's g_t), and the
+        weight gradients of all blocks in esr_rdb_wgrad passes over (S, Q), in one of three schedules."""
+        tp, nb, nj = self.tp, self.nb, self.nj
         border = [(i, j) for i in range(nb - 1, -1, -1) for j in range(nj - 1, -1, -1)]
-        TP.bwd_streams = RdbBwdStreams(dp, [pkey(i, j) for i, j in border])
-        bblocks = (L.esr_rdb_block * len(border))()
+        tp.bwd_streams = RdbBwdStreams(self.dp, [self.pkey(i, j) for i, j in border])
+        blocks = (L.esr_rdb_block * len(border))()
         wblocks = []
         for n, (i, j) in enumerate(border):
-            Q, bf, p = Qs[n], S[i][j], pkey(i, j)
-            b = bblocks[n]
-            b.w = TP.bwd_streams.w_ptr(n)
+            Q, b = self.Q(n), blocks[n]
+            b.w = tp.bwd_streams.w_ptr(n)
             b.x_in, b.dense, b.aux = Q.view(0, 64), Q.view(64, 128), Q.view(192, 32)
-            b.mask = MASKS[(i, j)].data_ptr()
-            b.layer1 = b.layer2 = L.NO_LAYER
+            b.mask = self.masks[(i, j)].data_ptr()
             b.flags = L.RDB_FULL_OUT
-            if j > 0:
-                # g_x = g_y of RDB j - 1 -> its g_t = g_y * n
-                b.x_out = Qs[n + 1].view(0, 64)
-                if noise:
-                    b.layer1 = per * i + j - 1
-            elif kind == 'rdb':
-                b.x_out = GX.view(0, 64)
-            else:
-                b.res2 = gA[ca].view(0, 64)
-                if block:
-                    b.x_out = GX.view(0, 64)
-                elif i > 0:
-                    b.out_a = gA[ca ^ 1].view(0, 64)
-                    if noise and variant == 'test_image':
-                        b.layer2 = per * (i - 1) + 3
-                    b.x_out = Qs[n + 1].view(0, 64)
-                    if noise:
-                        b.layer1 = per * (i - 1) + 2
-                    ca ^= 1
-                else:
-                    b.x_out = GF.view(0, 64)
-            wb = L.esr_rdb_wgrad_block()
-            wb.in_, wb.q = bf.view(0, 192), Q.view(0, 224)
-            for k in range(5):
-                key = p + '.conv%d.0' % (k + 1)
-                wb.dw[k] = TP.tapmajor.slot(goff[key], 64 if k == 4 else 32, 64 + 32 * k)
-                wb.db[k] = gptr[key][1]
-            wb.dw[5] = gptr[p + '.conv1x1'][0]
-            wblocks.append(wb)
-        bblk_t = torch.frombuffer(bytearray(bytes(bblocks)), dtype=torch.uint8).to(device)
-        ws_bytes = L.lib().esr_rdb_workspace_bytes(B, H, W)
-        bws = torch.zeros((ws_bytes + 3) // 4, dtype=torch.int32, device=device)
-        TP.bufs.extend([bblk_t, bws])
-        def chain_op(k0, k1):
-            ch = L.esr_rdb_chain()
-            ch.dtype, ch.B, ch.H, ch.W, ch.mode = dt_e, B, H, W, 2
-            ch.n_blocks, ch.noise_mode, ch.sigma, ch.save_dense = k1 - k0, L.NOISE_OFF, SIGMA, 1
-            ch.dense = Qs[k0].view(64, 128)
-            ch.blocks = bblk_t.data_ptr() + k0 * C.sizeof(L.esr_rdb_block)
-            ch.workspace, ch.workspace_bytes = bws.data_ptr(), ws_bytes
-            TP.bwd_chain_ops.append(Bk.add(L.OP_RDB_CHAIN_BWD, 'rdb_chain', ch))
-
-        def wgrad_op(grp, arena, flags=0, max_wg=0):
-            arr_ = (L.esr_rdb_wgrad_block * len(grp))(*grp)
-            wt = torch.frombuffer(bytearray(bytes(arr_)), dtype=torch.uint8).to(device)
-            TP.bufs.append(wt)
-            rw = L.esr_rdb_wgrad()
-            rw.dtype, rw.B, rw.H, rw.W = dt_e, B, H, W
-            rw.n_blocks, rw.tap_major, rw.scale5, rw.scale = len(grp), 1, 0.2, 1.0
-            rw.blocks = wt.data_ptr()
-            rw.partial, rw.partial_elems = arena.data_ptr(), arena.numel()
-            rw.max_workgroups = max_wg
-            Bk.add(L.OP_RDB_WGRAD, 'rdb_wgrad', rw, flags=flags)
-
-        TP.bwd_chain_ws = bws
-        nsplit = 1 if segmented else bwd_chain_split(B, H, W, nb)
-        cus_ = L.lib().esr_rdb_max_tiles_per_image()
-        spare_ = cus_ - B * ((H + 3) // 4) * ((W + 31) // 32)           # CUs a 4-row-tile launch leaves free
-        if nsplit > 1 and _SIDE and bwd_follow() and spare_ >= 32:
-            # Round 6: ONE chain launch and, launched with it on the side stream, the weight gradients of ALL blocks as
-            # a follower pass on the CUs the chain leaves free — a block's tasks start when the chain has published the
-            # block (csrc/rdb_wgrad.hip: follow_wait), its partial sums are reduced in slices by the tasks of the block a
-            # round of the grid later (delayed-slice reduction, rdb_wgrad_follow_kernel).  Behind the chain
-            # only the last block's tasks are left (the two-launch form below left the second run's pass + reduction:
-            # 0.4 + 0.08 ms of the step's critical path).
-            warena = torch.empty(int(L.lib().esr_rdb_wgrad_workspace_elems(B, H, W, len(border))), dtype=torch.float32, device=device)
-            TP.bufs.append(warena)
-            chain_op(0, len(border))
-            # (the follower's workgroups each hold a whole CU's LDS for the length of the chain: what else runs next to
-            # the G backward — the D step on the caller's second stream — needs CUs too.  Train step, same box, two runs
-            # each: round-5 form 6.52 ms; follower on 40 / 48 / 56 / 64 / 72 / 80 / 88 / 96 / 128 workgroups 7.33 / 6.86 /
-            # 6.52 / 6.28 / 6.29 / 6.26 / 6.27 / 6.23* / 6.57* (* another box: 6.42 without).  ESR_BWD_FOLLOW_WGS: A/B knob)
-            wgrad_op(wblocks, warena, flags=_SIDE | L.OPF_FOLLOW, max_wg=env_int('ESR_BWD_FOLLOW_WGS', min(spare_, 80), 32, max(32, spare_)))
-            # (functional._train_backward: a caller may size the follower per run — the train step's logging form)
-            TP.follow_op, TP.follow_spare = len(Bk.ops) - 1, spare_
-            TP.follow_wgs = Bk.ops[TP.follow_op].u.rdb_wgrad.max_workgroups
+            self.exit_to_block(self.block_exit(i, j), b)
+            wblocks.append(self.rdb_wgrad_block(i, j, Q))
+        self.bwd_blk_t = self.upload(blocks)
+        self.bwd_ws = self.chain_workspace(self.B, self.H, self.W)
+        tp.bwd_chain_ws = self.bwd_ws[0]
+        nsplit = 1 if self.segmented else bwd_chain_split(self.B, self.H, self.W, nb)
+        spare = spare_cus(self.B, self.H, self.W)
+        if nsplit > 1 and _SIDE and bwd_follow() and spare >= 32:
+            self.chain_with_follower(wblocks, spare)
         elif nsplit > 1:
-            # Small grids (the reference's training crops: 16 x 32^2 LR = 128 four-row tiles on 256 CUs): the chain leaves
-            # half of the chip idle and the weight gradients — 0.7 ms behind a 1.9 ms chain — sit on the step's critical
-            # path.  The chain runs as `nsplit` launches over runs of whole RRDBs, and the weight gradients of a run go
-            # to the SIDE stream right behind its chain launch: they execute on the idle CUs under the next run's chain
-            # (block n reads its g_t from Qs[n], which the previous launch's last block wrote: launch boundaries are
-            # free of semantics).  Only the last run's weight gradients are left behind the chain.
-            per_run = (nb + nsplit - 1) // nsplit
-            # run boundaries (RRDB indices).  ESR_BWD_SPLIT_FIRST = n: two runs, the first of n RRDBs (A/B: the LAST run's
-            # weight gradients are the ones left behind the chain, the first run's must fit under the second chain)
-            first = env_int('ESR_BWD_SPLIT_FIRST', 0, 0, nb)          # 0 / nb: equal runs
-            bounds = list(range(0, nb, per_run)) + [nb]
-            if nsplit == 2 and 0 < first < nb:
-                bounds = [0, first, nb]
-            # (the arena of a pass is not monotonic in its block count: fewer blocks -> fewer images per task -> more slots)
-            need = max(int(L.lib().esr_rdb_wgrad_workspace_elems(B, H, W, (b1 - b0) * nj)) for b0, b1 in zip(bounds[:-1], bounds[1:]))
-            warena = torch.empty(need, dtype=torch.float32, device=device)
-            TP.bufs.append(warena)
-            cus = L.lib().esr_rdb_max_tiles_per_image()
-            spare = max(32, cus - B * ((H + 3) // 4) * ((W + 31) // 32))     # CUs the chain's grid leaves free
-            for r0, r1 in zip(bounds[:-1], bounds[1:]):
-                k0, k1 = r0 * nj, r1 * nj
-                chain_op(k0, k1)
-                # every run but the last shares the chip with the next run's chain: its pass keeps to the spare CUs
-                # (a persistent grid of that many workgroups) so that the chain's workgroups find theirs free
-                wgrad_op(wblocks[k0:k1], warena, flags=_SIDE, max_wg=spare if k1 < len(border) else 0)
+            self.chain_in_runs(wblocks, nsplit, max(32, spare))
         else:
-            chain_op(0, len(border))
-            # weight gradients: one pass over all blocks — or, data-parallel, one per RRDB so that each RRDB's slice of the
-            # flat gradient buffer goes to its all-reduce while the next pass runs
-            groups = [wblocks] if not segmented else [wblocks[k:k + nj] for k in range(0, len(wblocks), nj)]
-            n_max = max(len(g_) for g_ in groups)
-            warena = torch.empty(int(L.lib().esr_rdb_wgrad_workspace_elems(B, H, W, n_max)), dtype=torch.float32, device=device)
-            TP.bufs.append(warena)
-            for gi, grp in enumerate(groups):
-                wgrad_op(grp, warena)
-                if segmented:
-                    close_segment(['model.1.sub.%d' % (nb - 1 - gi)])
-    for i in range(nb - 1 if not chain else -1, -1, -1):
-        for j in range(nj - 1, -1, -1):
-            bf, ax = S[i][j], AUX[i][j]
-            p = pkey(i, j)
-            Q = Qs[ct]                              # Q[0:64] already holds this block's g_t
-            # the block's six weight gradients read Q and the saved input, intact until the group after next
+            self.chain_then_wgrads(wblocks)
+
+    def add_bwd_chain(self, k0, k1):
+        """Blocks [k0, k1) (backward order) of the fused backward as one launch."""
+        ch = self.chain(self.bwd_ws, self.bwd_blk_t, k0, k1, self.Q(k0).view(64, 128), mode=2, save_dense=1)
+        self.tp.bwd_chain_ops.append(self.bwd.add(L.OP_RDB_CHAIN_BWD, 'rdb_chain', ch))
+
+    def chain_with_follower(self, wblocks, spare):
+        """Round 6: ONE chain launch and, launched with it on the side stream, the weight gradients of ALL blocks as a
+        follower pass on the CUs the chain leaves free — a block's tasks start when the chain has published the block
+        (csrc/rdb_wgrad.hip: follow_wait), its partial sums are reduced in slices by the tasks of the block a round of
+        the grid later (delayed-slice reduction, rdb_wgrad_follow_kernel).  Behind the chain only the last block's
+        tasks are left (the two-launch form, chain_in_runs, left the second run's pass + reduction: 0.4 + 0.08 ms of
+        the step's critical path)."""
+        tp = self.tp
+        arena = self.rdb_wgrad_arena(len(wblocks))
+        self.add_bwd_chain(0, len(wblocks))
+        # (the follower's workgroups each hold a whole CU's LDS for the length of the chain: what else runs next to
+        # the G backward — the D step on the caller's second stream — needs CUs too.  Train step, same box, two runs
+        # each: round-5 form 6.52 ms; follower on 40 / 48 / 56 / 64 / 72 / 80 / 88 / 96 / 128 workgroups 7.33 / 6.86 /
+        # 6.52 / 6.28 / 6.29 / 6.26 / 6.27 / 6.23* / 6.57* (* another box: 6.42 without).  ESR_BWD_FOLLOW_WGS: A/B knob)
+        wgs = env_int('ESR_BWD_FOLLOW_WGS', min(spare, 80), 32, max(32, spare))
+        # (functional._train_backward: a caller may size the follower per run — the train step's logging form)
+        tp.follow_op = self.add_rdb_wgrad(wblocks, arena, flags=_SIDE | L.OPF_FOLLOW, max_wg=wgs)
+        tp.follow_spare, tp.follow_wgs = spare, wgs
+
+    def chain_in_runs(self, wblocks, nsplit, spare):
+        """Small grids (the reference's training crops: 16 x 32^2 LR = 128 four-row tiles on 256 CUs): the chain leaves
+        half of the chip idle and the weight gradients — 0.7 ms behind a 1.9 ms chain — sit on the step's critical
+        path.  The chain runs as `nsplit` launches over runs of whole RRDBs, and the weight gradients of a run go to
+        the SIDE stream right behind its chain launch: they execute on the idle CUs under the next run's chain (block n
+        reads its g_t from Qs[n], which the previous launch's last block wrote: launch boundaries are free of
+        semantics).  Only the last run's weight gradients are left behind the chain."""
+        nb, nj = self.nb, self.nj
+        per_run = (nb + nsplit - 1) // nsplit
+        # run boundaries (RRDB indices).  ESR_BWD_SPLIT_FIRST = n: two runs, the first of n RRDBs (A/B: the LAST run's
+        # weight gradients are the ones left behind the chain, the first run's must fit under the second chain)
+        first = env_int('ESR_BWD_SPLIT_FIRST', 0, 0, nb)          # 0 / nb: equal runs
+        bounds = list(range(0, nb, per_run)) + [nb]
+        if nsplit == 2 and 0 < first < nb:
+            bounds = [0, first, nb]
+        runs = list(zip(bounds[:-1], bounds[1:]))
+        arena = self.rdb_wgrad_arena(*[(r1 - r0) * nj for r0, r1 in runs])
+        for r0, r1 in runs:
+            k0, k1 = r0 * nj, r1 * nj
+            self.add_bwd_chain(k0, k1)
+            # every run but the last shares the chip with the next run's chain: its pass keeps to the spare CUs
+            # (a persistent grid of that many workgroups) so that the chain's workgroups find theirs free
+            self.add_rdb_wgrad(wblocks[k0:k1], arena, flags=_SIDE, max_wg=spare if k1 < len(wblocks) else 0)
+
+    def chain_then_wgrads(self, wblocks):
+        """One chain launch, then the weight gradients: one pass over all blocks — or, data-parallel, one per RRDB so
+        that each RRDB's slice of the flat gradient buffer goes to its all-reduce while the next pass runs."""
+        nj = self.nj
+        self.add_bwd_chain(0, len(wblocks))
+        groups = [wblocks] if not self.segmented else [wblocks[k:k + nj] for k in range(0, len(wblocks), nj)]
+        arena = self.rdb_wgrad_arena(max(len(g_) for g_ in groups))
+        for gi, grp in enumerate(groups):
+            self.add_rdb_wgrad(grp, arena)
+            if self.segmented:
+                self.close_segment(['model.1.sub.%d' % (self.nb - 1 - gi)])
+
+    def backward_blocks_convs(self):
+        """Per-conv backward of the dense blocks: five gather-form slice convs per block over its Q, the weight
+        gradients of an RRDB as one side run behind its last dgrad conv."""
+        H, W, dconv, add_b = self.H, self.W, self.dconv, self.add_b
+        X4 = self.X4
+        for i in range(self.nb - 1, -1, -1):
+            # a block's six weight gradients read Q and the saved input, intact until the group after next
             # starts -> emitted together with the rest of the RRDB's after its last dgrad chain (one side run)
-            if deferred is None:
-                deferred = []
-            if fused_wgrad:
-                # one esr_rdb_wgrad pass per RRDB over (saved concat buffer, Q) of its blocks (rdb_wgrad.hip)
-                wb = L.esr_rdb_wgrad_block()
-                wb.in_, wb.q = bf.view(0, 192), Q.view(0, 224)
-                for k in range(5):
-                    key = p + '.conv%d.0' % (k + 1)
-                    wb.dw[k] = TP.tapmajor.slot(goff[key], 64 if k == 4 else 32, 64 + 32 * k)
-                    wb.db[k] = gptr[key][1]
-                wb.dw[5] = gptr[p + '.conv1x1'][0]
-                deferred.append(wb)
-            else:
-                wgrad(p + '.conv5.0', Q.view(0, 64), bf.view(0, 192), H, W, 64, 192, scale=0.2)
-                wgrad(p + '.conv4.0', Q.view(64, 32), bf.view(0, 160), H, W, 32, 160)
-                wgrad(p + '.conv3.0', Q.view(96, 32), bf.view(0, 128), H, W, 32, 128)
-                wgrad(p + '.conv2.0', Q.view(128, 32), bf.view(0, 96), H, W, 32, 96)
-                wgrad(p + '.conv1x1', Q.view(192, 32), bf.view(0, 64), H, W, 32, 64, ks=1)
-                wgrad(p + '.conv1.0', Q.view(160, 32), bf.view(0, 64), H, W, 32, 64)
-            # slice x4: g_x4 = conv5^T[x4](0.2 g_t)  -> raw to X4, masked (lrelu'(a4)) to Q[64:96]
-            c = dconv(H, W, Q.view(0), 64, X4.view(0, 32), p + '.g4')
-            c.mask, c.out2, c.mask_cb_begin = ax.view(32, 32), Q.view(64, 32), 0
-            add_b(c)
-            # slice x3 -> g_a3 = masked into Q[96:128]
-            c = dconv(H, W, Q.view(0), 96, None, p + '.g3')
-            c.mask, c.out2, c.mask_cb_begin = bf.view(128, 32), Q.view(96, 32), 0
-            add_b(c)
-            # slice x2 (+ g_x4: x4 = lrelu(a4) + x2) -> raw to Q[192:224] (feeds the 1x1), masked to Q[128:160]
-            c = dconv(H, W, Q.view(0), 128, Q.view(192, 32), p + '.g2')
-            c.res1 = X4.view(0, 32)
-            c.mask, c.out2, c.mask_cb_begin = ax.view(0, 32), Q.view(128, 32), 0
-            add_b(c)
-            # slice x1 -> g_a1 = masked into Q[160:192]
-            c = dconv(H, W, Q.view(0), 160, None, p + '.g1')
-            c.mask, c.out2, c.mask_cb_begin = bf.view(64, 32), Q.view(160, 32), 0
-            add_b(c)
-            # slice x closes the block: g_x = sum_k conv_k^T[x](g_ak) + conv1x1^T(g_x2) + g_t
-            # (d(0.2 x5 + x)/dx)  (+ RRDB skip for RDB1)
-            c = dconv(H, W, Q.view(0), 224, None, p + '.g0')
-            c.res1 = Q.view(0, 64)
-            if j > 0:
-                # g_x = g_y of RDB j (previous in forward order) -> its g_t = g_y * n
-                c.out = gT[(ct + 1) % NQ].view(0, 64)
-                set_noise(c, 2, per * i + j - 1)
-                ct = (ct + 1) % NQ
-            elif kind == 'rdb':
-                c.out = GX.view(0, 64)
-            else:
-                c.res2, c.beta = gA[ca].view(0, 64), 1.0
-                if block:
-                    c.out = GX.view(0, 64)
-                elif i > 0:
-                    c.out = gA[ca ^ 1].view(0, 64)
-                    if variant == 'test_image':
-                        set_noise(c, 2, per * (i - 1) + 3)
-                    c.out3, c.gamma = gT[(ct + 1) % NQ].view(0, 64), 0.2
-                    set_noise(c, 3, per * (i - 1) + 2)
-                    ca ^= 1
-                    ct = (ct + 1) % NQ
+            deferred = []
+            for j in range(self.nj - 1, -1, -1):
+                bf, ax, p = self.S[i][j], self.AUX[i][j], self.pkey(i, j)
+                Q = self.Q(self.bwd_index(i, j))            # Q[0:64] already holds this block's g_t
+                if self.fused_wgrad:
+                    # one esr_rdb_wgrad pass per RRDB over (saved concat buffer, Q) of its blocks (rdb_wgrad.hip)
+                    deferred.append(self.rdb_wgrad_block(i, j, Q))
                 else:
-                    c.out = GF.view(0, 64)
-            add_b(c, noisy=True)
-        if fused_wgrad:
-            arr = (L.esr_rdb_wgrad_block * len(deferred))(*deferred)
-            blk_t = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
-            TP.bufs.append(blk_t)
-            rw = L.esr_rdb_wgrad()
-            rw.dtype, rw.B, rw.H, rw.W = dt_e, B, H, W
-            rw.n_blocks, rw.tap_major, rw.scale5, rw.scale = len(deferred), 1, 0.2, 1.0
-            rw.blocks = blk_t.data_ptr()
-            rw.partial, rw.partial_elems = rdbw_arena.data_ptr(), rdbw_arena.numel()
-            Bk.add(L.OP_RDB_WGRAD, 'rdb_wgrad', rw, flags=_SIDE)
+                    deferred += [self.wgrad(p + '.conv5.0', Q.view(0, 64), bf.view(0, 192), H, W, 64, 192, scale=0.2),
+                                 self.wgrad(p + '.conv4.0', Q.view(64, 32), bf.view(0, 160), H, W, 32, 160),
+                                 self.wgrad(p + '.conv3.0', Q.view(96, 32), bf.view(0, 128), H, W, 32, 128),
+                                 self.wgrad(p + '.conv2.0', Q.view(128, 32), bf.view(0, 96), H, W, 32, 96),
+                                 self.wgrad(p + '.conv1x1', Q.view(192, 32), bf.view(0, 64), H, W, 32, 64, ks=1),
+                                 self.wgrad(p + '.conv1.0', Q.view(160, 32), bf.view(0, 64), H, W, 32, 64)]
+                # slice x4: g_x4 = conv5^T[x4](0.2 g_t)  -> raw to X4, masked (lrelu'(a4)) to Q[64:96]
+                c = dconv(H, W, Q.view(0), 64, X4.view(0, 32), p + '.g4')
+                c.mask, c.out2, c.mask_cb_begin = ax.view(32, 32), Q.view(64, 32), 0
+                add_b(c)
+                # slice x3 -> g_a3 = masked into Q[96:128]
+                c = dconv(H, W, Q.view(0), 96, None, p + '.g3')
+                c.mask, c.out2, c.mask_cb_begin = bf.view(128, 32), Q.view(96, 32), 0
+                add_b(c)
+                # slice x2 (+ g_x4: x4 = lrelu(a4) + x2) -> raw to Q[192:224] (feeds the 1x1), masked to Q[128:160]
+                c = dconv(H, W, Q.view(0), 128, Q.view(192, 32), p + '.g2')
+                c.res1 = X4.view(0, 32)
+                c.mask, c.out2, c.mask_cb_begin = ax.view(0, 32), Q.view(128, 32), 0
+                add_b(c)
+                # slice x1 -> g_a1 = masked into Q[160:192]
+                c = dconv(H, W, Q.view(0), 160, None, p + '.g1')
+                c.mask, c.out2, c.mask_cb_begin = bf.view(64, 32), Q.view(160, 32), 0
+                add_b(c)
+                # slice x closes the block: g_x = sum_k conv_k^T[x](g_ak) + conv1x1^T(g_x2) + g_t
+                # (d(0.2 x5 + x)/dx)  (+ RRDB skip for RDB1)
+                c = dconv(H, W, Q.view(0), 224, None, p + '.g0')
+                c.res1 = Q.view(0, 64)
+                self.exit_to_conv(self.block_exit(i, j), c)
+                add_b(c, noisy=True)
+            if self.fused_wgrad:
+                self.add_rdb_wgrad(deferred, self.rdbw_arena, flags=_SIDE)
+            else:
+                for wg in deferred:
+                    self.bwd.add(L.OP_WGRAD, 'wgrad', wg, flags=_SIDE)
+            if not self.block:
+                self.close_segment(['model.1.sub.%d' % i])
+
+    def backward_exit(self, in_nc):
+        """dL/dfea -> fea_conv's weight gradient, the unpermute of the tap-major gradients, and dL/dx."""
+        tp, H, W = self.tp, self.H, self.W
+        GF = self.GF
+        if not self.block:
+            if self.nb:
+                # trunk shortcut (fea feeds T directly as well): dL/dfea = chain result + dL/dT
+                GF = self.buf(64)
+                c = self.dconv(H, W, self.GF.view(0), 64, GF.view(0, 64), '__eye')
+                c.res1 = self.GTt.view(0, 64)
+                self.add_b(c)
+            # fea_conv (model.0): weight gradient only (the LR input image needs no gradient)
+            self.free_wgrad('model.0', GF.view(0, 64), self.xin.view(0, in_nc), H, W, 64, in_nc)
+            self.close_segment(['model.0'])
+        if self.segmented:
+            segs = self.segs
+            assert sorted((lo, hi) for _, lo, hi in segs)[0][0] == 0 and sum(hi - lo for _, lo, hi in segs) == tp.grad_flat.numel()
+            tp.segments = segs
         else:
-            for wg in deferred:
-                Bk.add(L.OP_WGRAD, 'wgrad', wg, flags=_SIDE)
-        deferred = None
-        if not block:
-            close_segment(['model.1.sub.%d' % i])
-    if block:
-        lo = L.esr_layout()
-        lo.dtype, lo.to_g32 = dt_e, 0
-        lo.B, lo.C, lo.H, lo.W = B, 64, H, W
-        lo.g32 = GX.view(0, 64)
-        TP.gx_op = None                             # bound after the unpermute op is appended
-        gx_layout = lo
+            self.unpermute()
+        if self.block:
+            tp.gx_op, tp.gx_shape = self.layout(self.bwd, self.GX, 64, 0), (self.B, 64, H, W)
+        else:
+            # dL/dx of the whole generator (autograd through architecture.py:76-78 when the LR input requires a gradient):
+            # fea_conv's input gradient, written straight into the caller's NCHW tensor.  Recorded at the END of the list
+            # and only run on request (TrainPlan.gx_begin: functional._train_backward stops there otherwise).
+            tp.gx_begin = len(self.bwd.ops)
+            c = self.dconv(H, W, GF.view(0), 64, None, 'model.0')
+            c.nchw_out_c = in_nc
+            tp.gx_op, tp.gx_shape = self.add_b(c), (self.B, in_nc, H, W)
+        tp.wgrad_arena = attach_wgrad_arena(self.bwd, self.device)
+        tp.wgrad_free_arena = attach_free_wgrad_regions(self.bwd, self.device)
+
+
+def build_rrdbnet_train_plan(net, wp, dp, nb, in_nc, out_nc, B, H, W, dtype, device, noise, variant,
+                             explicit_z, kind='net', segmented=False):
+    """RRDBNet forward keeping every RDB concat buffer (+ pre-residual activations of conv2/conv4,
+    whose signs are the LeakyReLU masks) and the backward pass:
+      * input gradients = the same fused conv kernel over transposed/rotated weights, with the
+        LeakyReLU-mask / noise / residual-scale backward applied in its epilogue;
+      * weight/bias gradients = esr_conv_wgrad.
+    kind 'net' = the whole generator; 'rrdb' / 'rdb' = a stand-alone RRDB / ResidualDenseBlock_5C
+    (64-channel NCHW in and out, gradient w.r.t. the input returned): same block code, no head/tail.
+    segmented ('net' only): the backward list records, per RRDB (and for the tail / the first conv), the op
+    index after which that slice of the flat gradient buffer is final — data-parallel runs start its
+    all-reduce there, under the rest of the backward (TrainPlan.segments, functional._train_backward)."""
+    bld = TrainBuilder(wp, dp, nb, B, H, W, dtype, device, noise, variant, explicit_z, kind, segmented)
+    bld.forward_head(in_nc)
+    if bld.chained:
+        bld.forward_blocks_chain()
     else:
-        if nb:
-            # trunk shortcut (fea feeds T directly as well): dL/dfea = chain result + dL/dT
-            GF2 = buf(64)
-            c = dconv(H, W, GF.view(0), 64, GF2.view(0, 64), '__eye')
-            c.res1 = GTt.view(0, 64)
-            add_b(c)
-            GF = GF2
-        # fea_conv (model.0): weight gradient only (the LR input image needs no gradient)
-        wgrad('model.0', GF.view(0, 64), xin.view(0, in_nc), H, W, 64, in_nc)
-        close_segment(['model.0'])
-    if TP.tapmajor is not None and not segmented:
-        up = TP.tapmajor.op()
-        if up is not None:
-            Bk.add(L.OP_UNPERMUTE, 'unpermute', up)
-    if segmented:
-        assert sorted((lo, hi) for _, lo, hi in segs)[0][0] == 0 and sum(hi - lo for _, lo, hi in segs) == TP.grad_flat.numel()
-        TP.segments = segs
-    if block:
-        TP.gx_op = Bk.add(L.OP_LAYOUT, 'layout', gx_layout)
+        bld.forward_blocks_convs()
+    bld.forward_exit(out_nc)
+    bld.grad_store(net)
+    bld.backward_buffers(out_nc)
+    if bld.block:
+        bld.backward_entry_block()
     else:
-        # dL/dx of the whole generator (autograd through architecture.py:76-78 when the LR input requires a gradient):
-        # fea_conv's input gradient, written straight into the caller's NCHW tensor.  Recorded at the END of the list
-        # and only run on request (TrainPlan.gx_begin: functional._train_backward stops there otherwise).
-        TP.gx_begin = len(Bk.ops)
-        c = dconv(H, W, GF.view(0), 64, None, 'model.0')
-        c.nchw_out_c = in_nc
-        TP.gx_op = add_b(c)
-    TP.wgrad_arena = attach_wgrad_arena(Bk, device)
-    TP.wgrad_free_arena = attach_free_wgrad_regions(Bk, device)
-    return TP
+        bld.backward_tail(out_nc)
+    bld.backward_blocks()
+    bld.backward_exit(in_nc)
+    return bld.tp

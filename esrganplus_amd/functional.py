@@ -64,7 +64,7 @@ def run_block(mod, kind, x, z=None):
             raise ValueError('expected 64 input channels, got %d' % C_)
         has_noise = getattr(mod, 'noise', None) is not None if kind == 'rdb' else True
         noise = bool(mod.training and has_noise)
-        n_noise = 0 if not noise else (1 if kind == 'rdb' else (4 if mod.variant == 'test_image' else 3))
+        n_noise = E.NoiseLayers(mod.variant, kind, 1, noise).total
         zs = _zs_list(z, n_noise, (B, 64, H, W), x.device) if noise else None
         return _BlockFn.apply(x, mod, kind, noise, zs, *mod._convs()[1])
     xin = _prep_input(x, 'input')
@@ -76,7 +76,7 @@ def run_block(mod, kind, x, z=None):
     wp = mod._weights(xin.device)
     has_noise = getattr(mod, 'noise', None) is not None if kind == 'rdb' else True
     noise = bool(mod.training and has_noise)
-    n_noise = 0 if not noise else (1 if kind == 'rdb' else (4 if mod.variant == 'test_image' else 3))
+    n_noise = E.NoiseLayers(mod.variant, kind, 1, noise).total
     zs = _zs_list(z, n_noise, (B, 64, H, W), xin.device) if noise else None
     key = (kind, B, H, W, mod.precision, noise, zs is not None, wp.generation)
     plan = mod._plans.get(key)
@@ -126,14 +126,8 @@ def _train_backward(tp, gy, st, noise, explicit, seed, want_gx, sync=None, prepa
     if tp.gx_begin is not None and not want_gx:
         n_ops = tp.gx_begin                         # whole generator: fea_conv's input gradient only on request
     elif tp.gx_op is not None:
-        if arr[tp.gx_op].kind == L.OP_CONV:
-            cv = arr[tp.gx_op].u.conv
-            gx = torch.empty((cv.B, cv.nchw_out_c, cv.H, cv.W), dtype=torch.float32, device=gy.device)
-            cv.nchw_out = gx.data_ptr()
-        else:
-            lo = arr[tp.gx_op].u.layout
-            gx = torch.empty((lo.B, lo.C, lo.H, lo.W), dtype=torch.float32, device=gy.device)
-            lo.nchw = gx.data_ptr()
+        gx = torch.empty(tp.gx_shape, dtype=torch.float32, device=gy.device)
+        E.set_nchw(arr[tp.gx_op], gx.data_ptr())
     mode = L.NOISE_OFF
     if noise:
         mode = L.NOISE_EXPLICIT if explicit else L.NOISE_PHILOX
@@ -318,8 +312,7 @@ def rrdbnet_train_forward(net, x, z=None):
     dev = xin.device
     st = E.current_stream()
     noise = bool(net.training)
-    per = 4 if net.variant == 'test_image' else 3
-    zs = _zs_list(z, per * net.nb, (B, 64, H, W), dev) if noise else None
+    zs = _zs_list(z, E.NoiseLayers(net.variant, 'net', net.nb).total, (B, 64, H, W), dev) if noise else None
     wp = net._weights(dev)
     dp = net._dgrad_weights(dev)
     n_packs = getattr(dp, 'pack_count', 0)
@@ -442,8 +435,7 @@ def run_rrdbnet(net, x, z=None):
         B, C_, H, W = x.shape
         if C_ != net.in_nc:
             raise ValueError('expected %d input channels, got %d' % (net.in_nc, C_))
-        per = 4 if net.variant == 'test_image' else 3
-        zs = _zs_list(z, per * net.nb, (B, 64, H, W), x.device) if net.training else None
+        zs = _zs_list(z, E.NoiseLayers(net.variant, 'net', net.nb).total, (B, 64, H, W), x.device) if net.training else None
         params = net._convs()[1]
         # the flat route assigns `.grad` itself, which only means something on LEAF parameters: under a multi-device
         # nn.DataParallel (networks.py:105-107) a replica's weights are Broadcast outputs, and their gradient has to
@@ -463,8 +455,7 @@ def run_rrdbnet(net, x, z=None):
     cur = order.enter()
     wp = net._weights(xin.device)
     noise = bool(net.training)
-    per = 4 if net.variant == 'test_image' else 3
-    zs = _zs_list(z, per * net.nb, (B, 64, H, W), xin.device) if noise else None
+    zs = _zs_list(z, E.NoiseLayers(net.variant, 'net', net.nb).total, (B, 64, H, W), xin.device) if noise else None
     key = (B, H, W, net.precision, noise, zs is not None, wp.generation)
     plan = net._plans.get(key)
     if plan is None:

@@ -137,7 +137,8 @@ def test_net_interp_and_network_roundtrip(tmp_path):
     ck.save_network(torch.nn.DataParallel(net), str(tmp_path / 'n.pth'))
     net2 = arch.RRDBNet(3, 3, 64, 1)
     ck.load_network(str(tmp_path / 'n.pth'), net2)
-    assert all(torch.equal(v, net2.state_dict()[kk]) for kk, v in net.state_dict().items())
+    # (nn.DataParallel moves `net` to the first GPU where there is one: compare on the host)
+    assert all(torch.equal(v.cpu(), net2.state_dict()[kk].cpu()) for kk, v in net.state_dict().items())
 
 
 def test_data_parallel_replica_does_not_inherit_caches():
