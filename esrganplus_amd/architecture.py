@@ -142,10 +142,36 @@ class _SeqNet(B._PlannedModule):
         # by attribute access (`_pspec`), not `parameters()`: that is empty on a nn.DataParallel replica
         return any(t.requires_grad for _, t in self._pspec())
 
+    def _plan_for(self, wp, dp, shape, dev, *, training, need_bwd, want_w, groups=1, bwd_B=None, dual=None, own=False):
+        """A free plan of this configuration's pool, built on first use.  own: the plan gets an input-gradient pack and
+        head weights of its own (see _run_forward)."""
+        Bn, _, H, W = shape
+        key = ('seq', Bn, H, W, self.precision, training, need_bwd, want_w, wp.generation, str(dev), groups, bwd_B, dual)
+        pool = self._plans.setdefault(key, [])
+        plan = next((p for p in pool if not p.busy), None)
+        if plan is None:
+            head = self._head()
+            if own:
+                dp = self._new_dgrad_pack(dev)
+                head = {k: torch.empty_like(v) for k, v in head.items()} if head is not None else None
+            plan = CN.build_seq_plan(self._spec(), wp, dp, self._pspec(), want_w, Bn, H, W, self.precision,
+                                     dev, training, need_bwd, self._input_affine(), head,
+                                     groups=groups, bwd_B=bwd_B if need_bwd else None, dual=dual)
+            if own:
+                plan.own_dp, plan.own_head = dp, head
+            if E.use_graphs() and dual is None:
+                # hipGraph replay: the input lands in a fixed staging tensor (everything else these
+                # plans touch — outputs, upstream gradients, BN sums — already lives in fixed buffers)
+                plan.x_static = torch.empty(shape, dtype=torch.float32, device=dev)
+                plan.fwd.array()[plan.in_op].u.layout.nchw = plan.x_static.data_ptr()
+                plan.graph = True
+            pool.append(plan)
+        plan.packs = (wp, dp)            # the lists hold raw pointers into the packs; a DataParallel replica dies before its backward
+        return plan
+
     def _run_forward(self, x, need_bwd, groups=1, bwd_B=None, dual=None):
         E.require_cuda(x, 'input')
         xin = x.detach().contiguous().float()
-        Bn, C_, H, W = xin.shape
         dev = xin.device
         order = E.StreamOrder.of(self) if not need_bwd else None      # inference calls: one at a time per module
         cur = order.enter() if order else None
@@ -163,26 +189,8 @@ class _SeqNet(B._PlannedModule):
                       and not self._dgrad_fresh())
         training = bool(self.training) and self._has_bn
         groups = groups if training else 1
-        key = ('seq', Bn, H, W, self.precision, training, need_bwd, want_w, wp.generation, str(dev), groups, bwd_B, dual)
-        pool = self._plans.setdefault(key, [])
-        plan = next((p for p in pool if not p.busy), None)
-        if plan is None:
-            head = self._head()
-            if own:
-                dp = self._new_dgrad_pack(dev)
-                head = {k: torch.empty_like(v) for k, v in head.items()} if head is not None else None
-            plan = CN.build_seq_plan(self._spec(), wp, dp, self._pspec(), want_w, Bn, H, W, self.precision,
-                                     dev, training, need_bwd, self._input_affine(), head,
-                                     groups=groups, bwd_B=bwd_B if need_bwd else None, dual=dual)
-            plan.own_dp, plan.own_head = (dp, head) if own else (None, None)
-            if E.use_graphs() and dual is None:
-                # hipGraph replay: the input lands in a fixed staging tensor (everything else these
-                # plans touch — outputs, upstream gradients, BN sums — already lives in fixed buffers)
-                plan.x_static = torch.empty_like(xin)
-                plan.fwd.array()[plan.in_op].u.layout.nchw = plan.x_static.data_ptr()
-                plan.graph = True
-            pool.append(plan)
-        plan.packs = (wp, dp)            # the lists hold raw pointers into the packs; a DataParallel replica dies before its backward
+        plan = self._plan_for(wp, dp, tuple(xin.shape), dev, training=training, need_bwd=need_bwd, want_w=want_w,
+                              groups=groups, bwd_B=bwd_B, dual=dual, own=own)
         lease = CN._Lease(plan) if need_bwd else None
         if own:
             plan.own_dp.ensure(st, force=True)
@@ -192,7 +200,7 @@ class _SeqNet(B._PlannedModule):
                         plan.own_head[k].copy_(v)
         if training:
             plan.sums_f.zero_()
-        if getattr(plan, 'graph', False):
+        if plan.graph:
             plan.x_static.copy_(xin)
             plan.fwd.graph_launch(st)
         else:
@@ -221,17 +229,9 @@ class _SeqNet(B._PlannedModule):
         training = bool(self.training) and self._has_bn
         if not training or getattr(self, '_per_call_weights', False) or E.use_graphs():
             raise L.HipExtensionError('_pair_begin: BatchNorm network in train mode only')
-        key = ('seq', 2 * n, H, W, self.precision, training, True, True, wp.generation, str(dev), 2, None, n)
-        pool = self._plans.setdefault(key, [])
-        plan = next((p for p in pool if not p.busy), None)
-        if plan is None:
-            plan = CN.build_seq_plan(self._spec(), wp, dp, self._pspec(), True, 2 * n, H, W, self.precision,
-                                     dev, training, True, self._input_affine(), self._head(), groups=2, bwd_B=None, dual=n)
-            plan.own_dp, plan.own_head = None, None
-            pool.append(plan)
-        if getattr(plan, 'fwd_half', None) is None:
+        plan = self._plan_for(wp, dp, (2 * n, C_, H, W), dev, training=training, need_bwd=True, want_w=True, groups=2, dual=n)
+        if plan.fwd_half is None:
             CN.split_forward_groups(plan, n)
-        plan.packs = (wp, dp)
         lease = CN._Lease(plan)
         plan.sums_f.zero_()
         half = plan.fwd_half[1]

@@ -499,6 +499,31 @@ class Plan:
             self.ops.run(stream)
 
 
+def new_buf(bufs, B, C_, H, W, dtype, device):
+    """A zeroed G32 buffer that the list `bufs` (a plan's or a backward pass's) keeps alive."""
+    b = G32(B, C_, H, W, dtype, device)
+    bufs.append(b)
+    return b
+
+
+def layout_op(ops, dt_e, B, g, C_, to_g32, nchw=None, affine=None):
+    """NCHW -> G32 (to_g32 = 1) or G32 -> NCHW layout op over channels [0, C_) of the first B images of buffer g,
+    appended to `ops`; returns its index.  nchw: the fp32 NCHW side, when it is known at build time.  affine: per-channel
+    (mean, 1/std) of an input normalisation folded into the conversion (and into its adjoint on the way back)."""
+    lo = L.esr_layout()
+    lo.dtype, lo.to_g32 = dt_e, to_g32
+    lo.B, lo.C, lo.H, lo.W = B, C_, g.H, g.W
+    lo.g32 = g.view(0, C_)
+    if nchw is not None:
+        lo.nchw = nchw
+    if affine is not None:
+        lo.use_affine = 1
+        for i in range(len(affine[0])):
+            lo.mean_c[i] = affine[0][i]
+            lo.inv_std_c[i] = affine[1][i]
+    return ops.add(L.OP_LAYOUT, 'layout', lo)
+
+
 class Builder:
     """Emits the fused-conv sequence of RDB / RRDB / RRDBNet into a Plan."""
 
@@ -518,9 +543,7 @@ class Builder:
         self.zbufs = []
 
     def buf(self, C_, H=None, W=None):
-        b = G32(self.B, C_, H or self.H, W or self.W, self.dtype, self.device)
-        self.bufs.append(b)
-        return b
+        return new_buf(self.bufs, self.B, C_, H or self.H, W or self.W, self.dtype, self.device)
 
     def upload(self, table):
         t = upload_table(table, self.device)
@@ -528,12 +551,7 @@ class Builder:
         return t
 
     def layout(self, ops, g, C_, to_g32):
-        """NCHW -> G32 (to_g32 = 1) or G32 -> NCHW layout op over channels [0, C_) of buffer g, appended to `ops`."""
-        lo = L.esr_layout()
-        lo.dtype, lo.to_g32 = self.dt_e, to_g32
-        lo.B, lo.C, lo.H, lo.W = self.B, C_, g.H, g.W
-        lo.g32 = g.view(0, C_)
-        return ops.add(L.OP_LAYOUT, 'layout', lo)
+        return layout_op(ops, self.dt_e, self.B, g, C_, to_g32)
 
     def import_nchw(self, dst, C_):
         return self.layout(self.plan.ops, dst, C_, 1)

@@ -275,15 +275,14 @@ class ESRGANPlusStep:
                 l_d, aux = LS.ragan_raw(pr, pg, True, False, 1.0, grad_x=gyt[n:], grad_y=gyt[:n],
                                         grad_scale=S, scale_dev=sdev, global_mean=mean)
                 CN.run_pass_into(PD)
-                views = PD.__dict__.get('_param_views')
-                if views is None:
+                if PD.param_views is None:
                     views, off = [], 0
                     for numel, shape in PD.grad_views:
                         views.append(PD.grad_flat[off:off + numel].view(shape))
                         off += numel
-                    PD._param_views = views
-                    PD._param_list = [t for _, t in netD._pspec()]
-                for p_, v in zip(PD._param_list, views):
+                    PD.param_views = views
+                    PD.param_list = [t for _, t in netD._pspec()]
+                for p_, v in zip(PD.param_list, PD.param_views):
                     p_.grad = v
                 self.exD.start()
                 return aux
