@@ -469,7 +469,7 @@ class _PlannedModule(nn.Module):
         return dp
 
     def _subpix_keys(self):
-        """Keys of up-convs to run in the sub-pixel form (engine.WeightPack)."""
+        """Keys of up-convs to run in the sub-pixel form (packs.WeightPack)."""
         return ()
 
     def prepack(self, fwd=True, dgrad=True):
@@ -506,7 +506,7 @@ class _PlannedModule(nn.Module):
 
 
 def _rdb_gathers(prefix, m):
-    """Gather-form input-gradient operands of one dense block (engine.DgradPack): the gradient of
+    """Gather-form input-gradient operands of one dense block (packs.DgradPack): the gradient of
     channel slice j (x4, x3, x2, x1, x) is ONE conv over Q = [g_t | g_a4 | g_a3 | g_a2 | g_a1 | g_x2]
     (the pre-activation gradients of the LATER convs, in that channel order; g_t stands for g_a5 / 0.2,
     hence the 0.2 on conv5's piece; g_x2, un-masked, feeds the transposed 1x1 at the centre tap)."""

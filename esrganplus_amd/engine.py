@@ -14,25 +14,11 @@ import os
 import torch
 
 from . import _lib as L
+from .packs import ConvW, DgradPack, RdbBwdStreams, RdbStreams, WeightPack, _dt, require_cuda  # noqa: F401 (re-exported)
 
 SIGMA = 0.1   # GaussianNoise sigma (block.py:111)
 
 _STORE_FLAVOUR = int(os.environ.get('ESR_STORE_FLAVOUR', '0'))   # experiment knob: 1 = nt epilogue stores
-
-
-def _dt(dtype):
-    if dtype in ('fp16', torch.float16, L.ESR_F16):
-        return L.ESR_F16, torch.float16, 16
-    if dtype in ('fp32', torch.float32, L.ESR_F32):
-        return L.ESR_F32, torch.float32, 8
-    raise ValueError('dtype must be fp16 or fp32, got %r' % (dtype,))
-
-
-def require_cuda(t, what):
-    if not t.is_cuda:
-        raise L.HipExtensionError(
-            'esrganplus_amd: %s is on %s — the HIP path needs a CUDA/HIP tensor on an MI355X; '
-            'there is no CPU fallback (use oracle/ for CPU reference results).' % (what, t.device))
 
 
 # ESR_SIDE=0: weight-gradient runs on the launch stream instead of the side stream (A/B)
@@ -67,275 +53,6 @@ class G32:
 
     def groups(self, nch):
         return (nch + self.cpg - 1) // self.cpg
-
-
-class ConvW:
-    """Packed weights of one conv (a slice of a WeightPack arena)."""
-    __slots__ = ('key', 'cout', 'cin', 'ks', 'w_ptr', 'bias_ptr', 'has_bias', 'subpix')
-
-
-class WeightPack:
-    """MFMA-fragment-ordered copies of a module's conv weights (fp32 OIHW nn.Parameters stay the
-    master copy — networks.py:30-44 pokes ``m.weight.data``, Adam updates them in place).
-    ``ensure()`` re-packs (one launch per tensor, recorded once) whenever a parameter's storage
-    or version changed, or unconditionally when ``force``."""
-
-    def __init__(self, convs, dtype, device, subpix=()):
-        # convs: list of (key, weight_param, bias_param_or_None); subpix: keys of up-convs (nearest x2 + 3x3,
-        # block.py:315-322) packed in the 4-phase 2x2 form (esr_pack.ups_fwd, run with esr_conv.upsample = 3)
-        self.esr_dtype, self.tdtype, self.cpg = _dt(dtype)
-        self.subpix = frozenset(subpix)
-        self.device = device
-        self.convs = convs
-        self.entries = {}
-        total = 0
-        offs = []
-        for key, w, b in convs:
-            cout, cin, ks, _ = w.shape
-            offs.append(total)
-            if key in self.subpix:      # 4 phases x cout blocks, 2x2 taps
-                total += L.packed_weight_bytes(4 * 32 * ((cout + 31) // 32), cin, 2, self.esr_dtype)
-            else:
-                total += L.packed_weight_bytes(cout, cin, ks, self.esr_dtype)
-        self.arena = torch.zeros(total, dtype=torch.uint8, device=device)
-        nb_pad = sum(((w.shape[0] + 31) // 32) * 32 for _, w, b in convs if b is not None and w.shape[0] % 32)
-        self.bias_arena = torch.zeros(max(nb_pad, 1), dtype=torch.float32, device=device)
-        self._bias_copies = []
-        bo = 0
-        for (key, w, b), off in zip(convs, offs):
-            e = ConvW()
-            e.key, (e.cout, e.cin, e.ks) = key, w.shape[:3]
-            e.subpix = key in self.subpix
-            e.w_ptr = self.arena.data_ptr() + off
-            e.has_bias = b is not None
-            e.bias_ptr = None
-            if b is not None:
-                if e.cout % 32 == 0:
-                    e.bias_ptr = None      # filled in _rebuild (points at the parameter itself)
-                else:
-                    n = ((e.cout + 31) // 32) * 32
-                    e.bias_ptr = self.bias_arena.data_ptr() + 4 * bo
-                    self._bias_copies.append((b, self.bias_arena[bo:bo + e.cout]))
-                    bo += n
-            self.entries[key] = e
-        self._sig = None
-        self._ptrs = None
-        self.ops = None
-        self.generation = 0      # bumped when any pointer handed out may have changed
-        self.pack_count = 0      # bumped every time the arena is re-packed (RdbStreams re-gathers)
-
-    def _check_params(self):
-        for key, w, b in self.convs:
-            for p in (w, b):
-                if p is None:
-                    continue
-                require_cuda(p, 'parameter ' + key)
-                if p.dtype != torch.float32 or not p.is_contiguous():
-                    raise L.HipExtensionError('parameter %s must be contiguous fp32 (master weights)' % key)
-
-    def _rebuild(self):
-        self._check_params()
-        packs = []
-        for key, w, b in self.convs:
-            e = self.entries[key]
-            pk = L.esr_pack()
-            pk.src = w.data_ptr()
-            pk.dst = e.w_ptr
-            pk.cout, pk.cin, pk.ks = e.cout, e.cin, e.ks
-            pk.dtype = self.esr_dtype
-            pk.transpose_flip = 0
-            pk.ups_fwd = 1 if e.subpix else 0
-            packs.append(pk)
-            if b is not None and e.cout % 32 == 0:
-                e.bias_ptr = b.data_ptr()
-        ops = L.OpList()                      # ONE launch re-packs every conv of the network
-        bp, self._pack_keep = L.batch_pack_op(packs, self.device)
-        ops.add(L.OP_PACK_BATCH, 'pack_batch', bp)
-        self.ops = ops
-        self.generation += 1
-
-    def _ptr_fingerprint(self):
-        # a few sampled storages + the count: parameters move together (.to / .cuda / DataParallel replicas); the full
-        # per-tensor tuple (2 x ~390 data_ptr calls for the generator) costs ~0.2 ms of host time per training step
-        c, n = self.convs, len(self.convs)
-        idx = sorted({0, n // 3, (2 * n) // 3, n - 1})
-        return (n,) + tuple(c[i][1].data_ptr() for i in idx) + tuple(c[i][2].data_ptr() for i in idx if c[i][2] is not None)
-
-    FULL_CHECK_EVERY = 64     # calls between full pointer comparisons (an unsampled parameter re-pointed by hand:
-    #                            `p.data = t`, per-layer re-init, load_state_dict(assign=True) — ADVICE r04)
-
-    def ensure(self, stream, force=False, record_sig=False, full=False):
-        """full=True (the module saw load_state_dict / _apply / replicate): compare EVERY parameter's storage, not the
-        sampled fingerprint; the same happens on every FULL_CHECK_EVERY-th call."""
-        fp = self._ptr_fingerprint()
-        self._calls = getattr(self, '_calls', 0) + 1
-        if full or self._calls % self.FULL_CHECK_EVERY == 0 or fp != getattr(self, '_fp', None):
-            ptrs = tuple(p.data_ptr() for _, w, b in self.convs for p in (w, b) if p is not None)
-            if ptrs != self._ptrs:
-                self._rebuild()
-                self._ptrs = ptrs
-                self._sig = None
-            self._fp = fp
-        # training passes re-pack unconditionally (FusedAdam updates through raw pointers: no version bump to see)
-        # (record_sig: a forced pack whose result a later non-forced call may rely on — _PlannedModule.prepack)
-        sig = None if (force and not record_sig) else tuple(p._version for _, w, b in self.convs for p in (w, b) if p is not None)
-        if force or sig != self._sig:
-            self.ops.run(stream)
-            with torch.no_grad():
-                for src, dst in self._bias_copies:
-                    dst.copy_(src)
-            self._sig = sig
-            self.pack_count += 1
-
-
-class RdbStreams:
-    """Fused weight streams of dense blocks for esr_rdb_forward (include/esrgan_hip.h, esr_rdb_block): per
-    block the 1 KB MFMA fragments of conv1..conv5 + conv1x1 in the order the kernel's units consume them
-    (esr_rdb_block.w in include/esrgan_hip.h) — a pure gather of fragments out of the per-conv packed arena
-    of `wp` (WeightPack), run as ONE esr_gather_fragments launch right after every re-pack."""
-
-    def __init__(self, wp, prefixes):
-        self.wp, self.prefixes = wp, list(prefixes)
-        self.cpg = wp.cpg
-        self.stream_bytes = L.lib().esr_rdb_weight_stream_bytes(wp.esr_dtype)
-        self.arena = torch.zeros(len(self.prefixes) * self.stream_bytes, dtype=torch.uint8, device=wp.device)
-        self.bias = torch.zeros(len(self.prefixes) * 192, dtype=torch.float32, device=wp.device)   # [block][192]
-        self._gen = None
-        self.ops = None
-
-    def w_ptr(self, i):
-        return self.arena.data_ptr() + i * self.stream_bytes
-
-    def bias_ptr(self, i):
-        return self.bias.data_ptr() + i * 192 * 4
-
-    def _table(self):
-        cpg, base = self.cpg, self.wp.arena.data_ptr()
-        kx, kd = 64 // cpg, 32 // cpg
-        offs = []
-        for p in self.prefixes:
-            ent = [self.wp.entries[p + '.conv%d.0' % k] for k in range(1, 6)]
-            nch = [(64 + 32 * k) // cpg for k in range(5)]            # input chunks of conv1..conv5
-
-            def frag(blk, c, kh, kw):                                # cout block 0..5 = conv1..conv4, conv5[0:32], conv5[32:64]
-                k, cb = (blk, 0) if blk < 4 else (4, blk - 4)
-                return ent[k].w_ptr - base + (((cb * nch[k] + c) * 3 + kh) * 3 + kw) * 1024
-            e1 = self.wp.entries[p + '.conv1x1']
-            one = [e1.w_ptr - base + c * 1024 for c in range(kx)]
-            for ph in range(1, 6):                                   # phase = input slice x, x1..x4
-                c0 = 0 if ph == 1 else kx + (ph - 2) * kd
-                ks = kx if ph == 1 else kd
-                if cpg == 8:
-                    # fp32: units (K step, column tap) over conv ph..5, the 1x1 at the end of the stream
-                    for c in range(ks):
-                        for kw in range(3):
-                            offs += [frag(blk, c0 + c, kh, kw) for blk in range(ph - 1, 6) for kh in range(3)]
-                    continue
-                # fp16 (rdb_fused.hip, Sched): crit_p = conv_p alone, one unit per K step (3 kw x 3 kh); bulk_p =
-                # conv_{p+1}..conv5, one unit per (K step, kw); the 1x1 after bulk_1; phase 5 = conv5's two blocks
-                if ph < 5:
-                    for c in range(ks):
-                        offs += [frag(ph - 1, c0 + c, kh, kw) for kw in range(3) for kh in range(3)]
-                    for c in range(ks):
-                        for kw in range(3):
-                            offs += [frag(blk, c0 + c, kh, kw) for blk in range(ph, 6) for kh in range(3)]
-                    if ph == 1:
-                        offs += one
-                else:
-                    for c in range(ks):
-                        for kw in range(3):
-                            offs += [frag(blk, c0 + c, kh, kw) for blk in (4, 5) for kh in range(3)]
-            if cpg == 8:
-                offs += one
-        assert len(offs) * 1024 == len(self.prefixes) * self.stream_bytes, (len(offs), self.stream_bytes)
-        return offs
-
-    def ensure(self, stream, force=False):
-        """Call after wp.ensure(): re-gathers when the packed arena was rewritten."""
-        if self.ops is None:
-            self._tab = torch.tensor(self._table(), dtype=torch.int64, device=self.wp.device)
-            g = L.esr_frag_gather()
-            g.src_off, g.src_base, g.dst, g.n = (self._tab.data_ptr(), self.wp.arena.data_ptr(),
-                                                 self.arena.data_ptr(), self._tab.numel())
-            self.ops = L.OpList()
-            self.ops.add(L.OP_FRAG_GATHER, 'frag_gather', g)
-            # the biases of a block as one [192] vector: 128-byte pieces straight from the nn.Parameters
-            boffs = []
-            for p in self.prefixes:
-                for k in range(1, 6):
-                    bp = self.wp.entries[p + '.conv%d.0' % k].bias_ptr
-                    boffs += [bp + 128 * q for q in range(2 if k == 5 else 1)]
-            self._btab = torch.tensor(boffs, dtype=torch.int64, device=self.wp.device)
-            gb = L.esr_frag_gather()
-            gb.src_off, gb.src_base, gb.dst, gb.n, gb.piece_bytes = self._btab.data_ptr(), None, self.bias.data_ptr(), len(boffs), 128
-            self.ops.add(L.OP_FRAG_GATHER, 'frag_gather', gb)
-            self._bias_src = tuple(boffs)
-        gen = (self.wp.generation, self.wp.pack_count)
-        if force or gen != self._gen:
-            self.ops.run(stream)
-            self._gen = gen
-
-
-class RdbBwdStreams:
-    """Fused weight streams of the BACKWARD chain (esr_rdb_backward; include/esrgan_hip.h, "Backward weight stream"):
-    per block the 1 KB fragments of its gather-form operands (DgradPack entries .g4 .g3 .c2 .g1 .c0 = cout blocks
-    0..3, 4/5) in the forward stream's crit / bulk unit order, the transposed 1x1 (.o1) behind crit_3 — a pure gather
-    out of the DgradPack arena, re-run after every re-pack."""
-
-    def __init__(self, dp, prefixes):
-        self.dp, self.prefixes = dp, list(prefixes)
-        assert dp.esr_dtype == L.ESR_F16
-        self.cpg = dp.cpg
-        self.stream_bytes = L.lib().esr_rdb_weight_stream_bytes(dp.esr_dtype)
-        self.arena = torch.zeros(len(self.prefixes) * self.stream_bytes, dtype=torch.uint8, device=dp.arena.device)
-        self._gen, self.ops = None, None
-
-    def w_ptr(self, i):
-        return self.arena.data_ptr() + i * self.stream_bytes
-
-    def _table(self):
-        cpg, base = self.cpg, self.dp.arena.data_ptr()
-        kx, kd = 64 // cpg, 32 // cpg
-        offs = []
-        for p in self.prefixes:
-            ent = [self.dp.entries[p + sfx] for sfx in ('.g4', '.g3', '.c2', '.g1', '.c0')]
-            nch = [(64 + 32 * k) // cpg for k in range(5)]            # K chunks of the five slice convs
-
-            def frag(blk, c, kh, kw):
-                k, cb = (blk, 0) if blk < 4 else (4, blk - 4)
-                return ent[k].w_ptr - base + (((cb * nch[k] + c) * 3 + kh) * 3 + kw) * 1024
-            one = [self.dp.entries[p + '.o1'].w_ptr - base + f * 1024 for f in range(4)]
-            for ph in range(1, 6):
-                c0 = 0 if ph == 1 else kx + (ph - 2) * kd
-                ks = kx if ph == 1 else kd
-                if ph < 5:
-                    for c in range(ks):
-                        offs += [frag(ph - 1, c0 + c, kh, kw) for kw in range(3) for kh in range(3)]
-                    if ph == 3:
-                        offs += one
-                    for c in range(ks):
-                        for kw in range(3):
-                            offs += [frag(blk, c0 + c, kh, kw) for blk in range(ph, 6) for kh in range(3)]
-                else:
-                    for c in range(ks):
-                        for kw in range(3):
-                            offs += [frag(blk, c0 + c, kh, kw) for blk in (4, 5) for kh in range(3)]
-        assert len(offs) * 1024 == len(self.prefixes) * self.stream_bytes, (len(offs), self.stream_bytes)
-        return offs
-
-    def ensure(self, stream, force=False):
-        """Call after dp.ensure(): re-gathers when the packed arena was rewritten."""
-        if self.ops is None:
-            self._tab = torch.tensor(self._table(), dtype=torch.int64, device=self.arena.device)
-            g = L.esr_frag_gather()
-            g.src_off, g.src_base, g.dst, g.n = (self._tab.data_ptr(), self.dp.arena.data_ptr(),
-                                                 self.arena.data_ptr(), self._tab.numel())
-            self.ops = L.OpList()
-            self.ops.add(L.OP_FRAG_GATHER, 'frag_gather', g)
-        gen = getattr(self.dp, 'pack_count', 0)
-        if force or gen != self._gen:
-            self.ops.run(stream)
-            self._gen = gen
 
 
 def use_train_chain(dtype_e, B, H, W, explicit_z):
@@ -1015,123 +732,6 @@ def build_rrdbnet_plan(wp, nb, in_nc, out_nc, B, H, W, dtype, device, noise, var
 # =================================================================================================
 # Training path: forward that keeps every activation + the matching backward launch list
 # =================================================================================================
-class DgradPack:
-    """Packed operands of the input-gradient convolutions: Cin<->Cout transposed, taps rotated 180
-    degrees (esr_pack.transpose_flip); conv5 of an RDB additionally folds the x4->x2 identity path
-    (block.py:266) into its x2 output slice, and the upconvs get the 4x4/stride-2 adjoint kernel."""
-
-    def __init__(self, convs, dtype, device, special, gathers=()):
-        # convs: list of (key, weight_param); special: key -> dict(sum=(dst,src,count)) / dict(ups=True)
-        # gathers: list of (key, dst_cout, [(weight_param, src_co0, scale), ...]) — gather-form operands
-        # of a dense block (include/esrgan_hip.h: esr_pack.gather): K = the pieces' forward couts, in order
-        self.esr_dtype, self.tdtype, self.cpg = _dt(dtype)
-        self.convs, self.special, self.gathers = convs, special, list(gathers)
-        self.entries = {}
-        total, offs = 0, []
-        for key, w in convs:
-            cout, cin, ks, _ = w.shape
-            ks_out = 4 if special.get(key, {}).get('ups') else ks
-            offs.append(total)
-            total += L.packed_weight_bytes(cin, cout, ks_out, self.esr_dtype)
-        # a gather entry is (key, dst_cout, [(weight, src_co0, scale[, fold_co0]), ...]) or, for the transposed 1x1 of
-        # the backward chain, (key, 'one_t', conv1x1.weight) — 4 KB of fragments (esr_pack.one_t; fp16 only)
-        self.ones = [g for g in self.gathers if g[1] == 'one_t']
-        self.gathers = [g for g in self.gathers if g[1] != 'one_t']
-        if self.esr_dtype != L.ESR_F16:
-            self.ones = []
-        goffs = []
-        for key, dst_cout, pieces in self.gathers:
-            k_total = sum(pc[0].shape[0] for pc in pieces)
-            goffs.append(total)
-            total += L.packed_weight_bytes(dst_cout, k_total, 3, self.esr_dtype)
-        ooffs = []
-        for key, _, w in self.ones:
-            ooffs.append(total)
-            total += 4096
-        self.arena = torch.zeros(total, dtype=torch.uint8, device=device)
-        for (key, dst_cout, pieces), off in zip(self.gathers, goffs):
-            e = ConvW()
-            e.key, e.cout, e.cin, e.ks = key, dst_cout, sum(pc[0].shape[0] for pc in pieces), 3
-            e.w_ptr, e.bias_ptr, e.has_bias = self.arena.data_ptr() + off, None, False
-            self.entries[key] = e
-        for (key, _, w), off in zip(self.ones, ooffs):
-            e = ConvW()
-            e.key, e.cout, e.cin, e.ks = key, 64, 32, 1
-            e.w_ptr, e.bias_ptr, e.has_bias = self.arena.data_ptr() + off, None, False
-            self.entries[key] = e
-        for (key, w), off in zip(convs, offs):
-            e = ConvW()
-            e.key = key
-            fc, fi, ks = w.shape[:3]
-            e.cout, e.cin = fi, fc                  # the dgrad conv maps fwd-Cout -> fwd-Cin
-            e.ks = 4 if special.get(key, {}).get('ups') else ks
-            e.w_ptr, e.bias_ptr, e.has_bias = self.arena.data_ptr() + off, None, False
-            self.entries[key] = e
-        self._ptrs = None
-        self.ops = None
-
-    def ensure(self, stream, force=True, record_sig=False):
-        """force=False (a frozen eval-mode net, the VGG feature extractor): re-pack only when a parameter's
-        storage or version changed, like WeightPack.ensure."""
-        fp = (len(self.convs), len(self.gathers), len(self.ones)) + tuple(
-            lst[i][-1].data_ptr() if torch.is_tensor(lst[i][-1]) else lst[i][-1][0][0].data_ptr()
-            for lst in (self.convs, self.gathers, self.ones) if lst for i in sorted({0, len(lst) // 2, len(lst) - 1}))
-        ptrs = self._ptrs
-        self._calls = getattr(self, '_calls', 0) + 1
-        if (self._calls % WeightPack.FULL_CHECK_EVERY == 0
-                or fp != getattr(self, '_fp', None)):      # (sampled storages first, as WeightPack.ensure)
-            ptrs = tuple(w.data_ptr() for _, w in self.convs) + tuple(
-                pc[0].data_ptr() for _, _, pieces in self.gathers for pc in pieces) + tuple(w.data_ptr() for _, _, w in self.ones)
-            self._fp = fp
-        if ptrs != self._ptrs:
-            packs = []
-            for key, dst_cout, pieces in self.gathers:
-                e = self.entries[key]
-                nchunks, chunk0 = e.cin // self.cpg, 0
-                for pc in pieces:
-                    w, src_co0, scale = pc[:3]
-                    assert w.shape[0] % self.cpg == 0 and src_co0 + dst_cout <= w.shape[1]
-                    pk = L.esr_pack()
-                    pk.src, pk.dst = w.data_ptr(), e.w_ptr
-                    pk.cout, pk.cin, pk.ks = w.shape[0], w.shape[1], 3
-                    pk.dtype, pk.transpose_flip, pk.gather = self.esr_dtype, 1, 1
-                    pk.dst_cout, pk.dst_chunk0, pk.dst_nchunks = dst_cout, chunk0, nchunks
-                    pk.src_co0, pk.src_ks, pk.scale = src_co0, w.shape[2], scale
-                    pk.fold_co0 = pc[3] if len(pc) > 3 else 0
-                    packs.append(pk)
-                    chunk0 += w.shape[0] // self.cpg
-            for key, _, w in self.ones:
-                pk = L.esr_pack()
-                pk.src, pk.dst = w.data_ptr(), self.entries[key].w_ptr
-                pk.cout, pk.cin, pk.ks, pk.dtype, pk.one_t, pk.scale = w.shape[0], w.shape[1], 1, self.esr_dtype, 1, 1.0
-                packs.append(pk)
-            for key, w in self.convs:
-                e = self.entries[key]
-                sp = self.special.get(key, {})
-                pk = L.esr_pack()
-                pk.src, pk.dst = w.data_ptr(), e.w_ptr
-                pk.cout, pk.cin = w.shape[0], w.shape[1]
-                pk.ks = e.ks
-                pk.dtype = self.esr_dtype
-                pk.transpose_flip = 2 if sp.get('ts2') else 1
-                if 'sum' in sp:
-                    pk.sum_dst, pk.sum_src, pk.sum_count = sp['sum']
-                pk.ups_dgrad = 1 if sp.get('ups') else 0
-                packs.append(pk)
-            ops = L.OpList()
-            bp, self._pack_keep = L.batch_pack_op(packs, self.arena.device)
-            ops.add(L.OP_PACK_BATCH, 'pack_batch', bp)
-            self.ops, self._ptrs = ops, ptrs
-            self._sig = None
-        sig = None if (force and not record_sig) else (tuple(w._version for _, w in self.convs)
-                                  + tuple(pc[0]._version for _, _, pieces in self.gathers for pc in pieces)
-                                  + tuple(w._version for _, _, w in self.ones))
-        if force or sig != getattr(self, '_sig', None):
-            self.ops.run(stream)  # (training nets: weights change every optimizer step, always re-pack)
-            self._sig = sig
-            self.pack_count = getattr(self, 'pack_count', 0) + 1
-
-
 class TapMajorGrads:
     """fp16 wgrad accumulates 3x3 weight gradients tap-major ([tap][cout][cin]: atomics of one wave
     instruction land in 2 cache lines instead of ~36); one esr_grad_unpermute launch at the end of the

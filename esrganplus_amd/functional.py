@@ -315,10 +315,10 @@ def rrdbnet_train_forward(net, x, z=None):
     zs = _zs_list(z, E.NoiseLayers(net.variant, 'net', net.nb).total, (B, 64, H, W), dev) if noise else None
     wp = net._weights(dev)
     dp = net._dgrad_weights(dev)
-    n_packs = getattr(dp, 'pack_count', 0)
+    n_packs = dp.pack_count
     dp.ensure(st, force=not net._dgrad_fresh())
     pack_ev = None
-    if getattr(dp, 'pack_count', 0) != n_packs and not torch.cuda.is_current_stream_capturing():
+    if dp.pack_count != n_packs and not torch.cuda.is_current_stream_capturing():
         # the input-gradient operands were re-packed on THIS stream just now (first step, ESR_PREPACK=0, after
         # load_state_dict / resume): whoever gathers the backward chain's weight streams from dp.arena on another
         # stream (`rrdbnet_train_prepare` on the train step's side stream) has to wait for it — recorded here, in
