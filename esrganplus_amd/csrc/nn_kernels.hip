@@ -487,7 +487,9 @@ __global__ __launch_bounds__(256) void adam_kernel(const esr_adam a) {
     bc1 = (float)(1.0 - pow(a.beta1_d, t));
     bc2 = (float)(1.0 - pow(a.beta2_d, t));
   }
-  const float step = a.lr / bc1, rs2 = rsqrtf(bc2), omb1 = 1.f - a.beta1, omb2 = 1.f - a.beta2;
+  // 1 - beta from the fp64 betas: 1.f - (float)0.999 is off by 1.3e-5 relative (half an ulp of 0.999 against 0.001),
+  // which scales v but not bc2 and so biases every update by 6e-6
+  const float step = a.lr / bc1, rs2 = rsqrtf(bc2), omb1 = (float)(1.0 - a.beta1_d), omb2 = (float)(1.0 - a.beta2_d);
   float gs = a.grad_scale;
   if (a.amp_state) {                       // dynamic loss scaling: skip the step on overflow, else un-scale
     if (a.amp_state[4 + a.amp_slot] != 0.f) return;
@@ -553,7 +555,10 @@ extern "C" int esr_adam_step(const esr_adam* p, esr_stream_t stream) {
     esr_set_error("esr_adam_step: invalid arguments");
     return ESR_ERR_INVALID;
   }
-  hipLaunchKernelGGL(adam_kernel, dim3(p->nblocks), dim3(256), 0, (hipStream_t)stream, *p);
+  esr_adam q = *p;
+  if (q.beta1_d == 0.0) q.beta1_d = q.beta1;     // a caller that fills the fp32 betas only
+  if (q.beta2_d == 0.0) q.beta2_d = q.beta2;
+  hipLaunchKernelGGL(adam_kernel, dim3(q.nblocks), dim3(256), 0, (hipStream_t)stream, q);
   return esr_check_launch("adam_kernel");
 }
 

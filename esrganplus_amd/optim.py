@@ -150,9 +150,10 @@ class FusedAdam(torch.optim.Optimizer):
             a.lr, a.beta1, a.beta2, a.eps = group['lr'], b1, b2, group['eps']
             a.bc1, a.bc2 = 1.0 - math.pow(b1, st['step']), 1.0 - math.pow(b2, st['step'])
             a.grad_scale, a.weight_decay = grad_scale, group['weight_decay']
+            a.beta1_d, a.beta2_d = float(b1), float(b2)       # 1 - beta is formed from these (fp32 betas lose it)
             if scaler is not None:
                 a.amp_state, a.amp_slot = scaler.state.data_ptr(), slot
-                a.step_count, a.beta1_d, a.beta2_d = st['applied'].data_ptr(), float(b1), float(b2)
+                a.step_count = st['applied'].data_ptr()
             L.check(L.lib().esr_adam_step(C.byref(a), C.c_void_p(stream)), 'esr_adam_step')
         return loss
 

@@ -343,7 +343,8 @@ typedef struct esr_adam {
                              APPLIED including the current one (ESR_AMP_COUNT advances it only when the step is not
                              skipped): bc = 1 - beta^step_count[0] is formed in the kernel from beta1_d / beta2_d, so a
                              skipped step does not age Adam's bias correction (torch.amp.GradScaler semantics) */
-  double beta1_d, beta2_d;
+  double beta1_d, beta2_d; /* the betas in fp64: 1 - beta (and the device-side bias correction) come from these, so that
+                             fp32 rounding of a beta near 1 does not scale the moments; 0: taken from beta1 / beta2 */
 } esr_adam;
 
 /* Dynamic loss scaling for the fp16 training path (new capability; the reference trains in fp32 only).
