@@ -10,7 +10,7 @@ import math
 import torch.nn as nn
 
 from . import block as B
-from .functional import run_rrdbnet
+from .functional import run_rrdbnet, run_rrdbnet_x8
 
 
 class _RRDBNetBase(B._PlannedModule):
@@ -89,6 +89,14 @@ class _RRDBNetBase(B._PlannedModule):
         execution order, for bit-parity tests; default = fused Philox stream."""
         self._join_pending()
         return run_rrdbnet(self, x, z)
+
+    def forward_x8(self, x, slots_per_pass=None):
+        """Geometric self-ensemble (the reference's ``SRModel.test_x8``, codes/models/SR_model.py:82-120): the mean of the
+        eight flip / transpose variants, per image, as one batched launch plan -> [B, out_nc, 4H, 4W] float32 without
+        gradient.  Always the eval forward; ``self.training`` and ``requires_grad`` are left as they are.  See
+        ``functional.run_rrdbnet_x8``."""
+        self._join_pending()
+        return run_rrdbnet_x8(self, x, slots_per_pass)
 
 
 class RRDBNet(_RRDBNetBase):

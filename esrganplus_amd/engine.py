@@ -133,6 +133,8 @@ def set_nchw(op, ptr):
     """Bind the caller's NCHW tensor to an op that reads or writes one: a conv with an NCHW epilogue or a layout op."""
     if op.kind == L.OP_CONV:
         op.u.conv.nchw_out = ptr
+    elif op.kind == L.OP_DIHEDRAL:
+        op.u.dihedral.nchw = ptr
     else:
         op.u.layout.nchw = ptr
 
@@ -186,7 +188,7 @@ class Plan:
 
     def run(self, x, out, stream, seed=0, zs=None):
         arr = self.ops.array()
-        arr[self.in_op].u.layout.nchw = x.data_ptr()
+        set_nchw(arr[self.in_op], x.data_ptr())
         set_nchw(arr[self.out_op], out.data_ptr())
         mode = L.NOISE_OFF
         if not self.graph_bound:
@@ -241,10 +243,25 @@ def layout_op(ops, dt_e, B, g, C_, to_g32, nchw=None, affine=None):
     return ops.add(L.OP_LAYOUT, 'layout', lo)
 
 
+def dihedral_op(ops, dt_e, B, C_, H, W, to_g32, k_count, g=None, slots=None):
+    """Self-ensemble end (esr_dihedral) appended to `ops`: the import of k_count transformed copies of B NCHW images of
+    H x W into buffer g, or the reduce of k_count x B outputs — from g or from the fp32 NCHW tensor `slots` — into B
+    NCHW images of H x W.  The range's first k, accumulate and scale are set per pass (X8Plan.run)."""
+    d = L.esr_dihedral()
+    d.dtype, d.to_g32 = dt_e, to_g32
+    d.B, d.C, d.H, d.W = B, C_, H, W
+    if g is not None:
+        d.g32 = g.view(0, C_)
+    if slots is not None:
+        d.slots_nchw = slots.data_ptr()
+    d.k_begin, d.k_count, d.accumulate, d.scale = 0, k_count, 0, 1.0
+    return ops.add(L.OP_DIHEDRAL, 'dihedral', d)
+
+
 class Builder:
     """Emits the fused-conv sequence of RDB / RRDB / RRDBNet into a Plan."""
 
-    def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1):
+    def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1, x8=None):
         self.wp = wp
         self.B, self.H, self.W = B, H, W
         self.dt_e, self.tdtype, self.cpg = _dt(dtype)
@@ -258,6 +275,7 @@ class Builder:
         self.plan = Plan()
         self.bufs = self.plan.bufs    # everything the ops point at stays alive with the plan
         self.zbufs = []
+        self.x8 = x8                  # (images, H, W of the NCHW input): the batch is slots x images of a self-ensemble
 
     def buf(self, C_, H=None, W=None):
         return new_buf(self.bufs, self.B, C_, H or self.H, W or self.W, self.dtype, self.device)
@@ -459,8 +477,19 @@ class Builder:
         P.ops.add_conv(_conv(d, B, 4 * H, 4 * W, u2.view(0), 64, u3.view(0, 64), e['model.8'], L.ACT_LRELU))
         c = _conv(d, B, 4 * H, 4 * W, u3.view(0), 64, None, e['model.10'])
         c.nchw_out_c = out_nc
-        P.out_op = P.ops.add_conv(c)
         P.out_shape = (B, out_nc, 4 * H, 4 * W)
+        if self.x8 is None:
+            P.out_op = P.ops.add_conv(c)
+        else:
+            # self-ensemble: HR_conv1 leaves its fp32 NCHW result (unrounded in either precision, as the ordinary plan's)
+            # in a buffer of the plan, slot-major, and the reduce undoes the transforms into the caller's tensor
+            n, xh, xw = self.x8
+            slots = torch.empty(P.out_shape, dtype=torch.float32, device=self.device)
+            self.bufs.append(slots)
+            c.nchw_out = slots.data_ptr()
+            P.ops.add_conv(c)
+            P.out_op = dihedral_op(P.ops, d, n, out_nc, 4 * xh, 4 * xw, 0, B // n, slots=slots)
+            P.out_shape = (n, out_nc, 4 * xh, 4 * xw)
         return t, u1, u2, u3
 
     def rrdbnet(self, in_nc, out_nc, explicit_z):
@@ -471,7 +500,11 @@ class Builder:
         self.alloc_z(explicit_z)
         xin = self.buf(in_nc)
         fea = self.buf(64)
-        P.in_op = self.import_nchw(xin, in_nc)
+        if self.x8 is None:
+            P.in_op = self.import_nchw(xin, in_nc)
+        else:
+            n, xh, xw = self.x8
+            P.in_op = dihedral_op(P.ops, self.dt_e, n, in_nc, xh, xw, 1, B // n, g=xin)
         if nb and rdb_chain_ok(B, H, W, self.noise, explicit_z):
             # fused trunk: two 64-channel slots + the chain's 128-channel dense scratch
             xa, xb = self.buf(64), self.buf(64)
@@ -727,6 +760,50 @@ def build_block_plan(kind, wp, B, H, W, dtype, device, noise, variant, explicit_
 
 def build_rrdbnet_plan(wp, nb, in_nc, out_nc, B, H, W, dtype, device, noise, variant, explicit_z):
     return Builder(wp, B, H, W, dtype, device, noise, variant, 'net', nb).rrdbnet(in_nc, out_nc, explicit_z)
+
+
+X8_SLOTS = (8, 4, 2, 1)
+
+
+def x8_slots(H, W, slots_per_pass=None):
+    """Slots (transformed copies per image) one pass of the self-ensemble runs as a batch: the argument, else
+    ESR_X8_SLOTS, else 8 for square input and 4 otherwise — a pass cannot mix H x W and W x H slots."""
+    n = env_int('ESR_X8_SLOTS', 8, 1, 8) if slots_per_pass is None else int(slots_per_pass)
+    if n not in X8_SLOTS:
+        raise ValueError('slots per pass of the x8 self-ensemble must be one of %s, got %r' % (X8_SLOTS, n))
+    return min(n, 4) if H != W else n
+
+
+class X8Plan:
+    """The x8 self-ensemble of one (batch, shape, precision): 8 / slots passes over one inference plan of batch
+    slots x B (two plans for non-square input: H x W for k 0..3, W x H for k 4..7), chained through the reduce op's
+    `accumulate`; the last pass applies the 1/8."""
+
+    def __init__(self, plans, slots, out_shape):
+        self.plans, self.slots, self.out_shape = plans, slots, out_shape
+
+    def bind_pass(self, k0):
+        """The plan of the pass that starts at slot k0, its two dihedral ops set to that range."""
+        plan = self.plans[-1 if k0 >= 4 else 0]
+        arr = plan.ops.array()
+        arr[plan.in_op].u.dihedral.k_begin = k0
+        r = arr[plan.out_op].u.dihedral
+        r.k_begin, r.accumulate, r.scale = k0, int(k0 > 0), 0.125 if k0 + self.slots == 8 else 1.0
+        return plan
+
+    def run(self, x, out, stream):
+        for k0 in range(0, 8, self.slots):
+            self.bind_pass(k0).run(x, out, stream)
+
+
+def build_rrdbnet_x8_plan(wp, nb, in_nc, out_nc, B, H, W, dtype, device, variant, slots):
+    """Self-ensemble form of build_rrdbnet_plan (eval mode): the dihedral import in place of the NCHW import, the
+    dihedral reduce behind HR_conv1, and between them the ops of the ordinary plan of batch slots x B."""
+    plans = []
+    for sh, sw in ([(H, W)] if H == W else [(H, W), (W, H)]):
+        b = Builder(wp, slots * B, sh, sw, dtype, device, False, variant, 'net', nb, x8=(B, H, W))
+        plans.append(b.rrdbnet(in_nc, out_nc, False))
+    return X8Plan(plans, slots, (B, out_nc, 4 * H, 4 * W))
 
 
 # =================================================================================================

@@ -468,3 +468,78 @@ def run_rrdbnet(net, x, z=None):
     plan.run(xin, out, E.current_stream(), _draw_seed() if (noise and zs is None) else 0, zs)
     order.leave(cur)
     return out
+
+
+def x8_transform(x, k):
+    """Transform k = 0..7 of the self-ensemble, the reference's list order (codes/models/SR_model.py:103-105): bit 0 flips
+    along W ('v'), bit 1 along H ('h'), bit 2 transposes ('t'); v and h first, t last."""
+    if k & 1:
+        x = x.flip(3)
+    if k & 2:
+        x = x.flip(2)
+    if k & 4:
+        x = x.transpose(2, 3)
+    return x.contiguous()
+
+
+def x8_inverse(y, k):
+    """Undoes transform k on an output, in the reference's order (SR_model.py:107-113): t, then h, then v."""
+    if k & 4:
+        y = y.transpose(2, 3)
+    if k & 2:
+        y = y.flip(2)
+    if k & 1:
+        y = y.flip(3)
+    return y.contiguous()
+
+
+def x8_reference(fn, x):
+    """Pure-torch restatement of the reference's ``SRModel.test_x8`` (codes/models/SR_model.py:82-120) over a forward
+    ``fn``: the same eight transforms in the same list order, the same inverses, and the mean per image — the reference's
+    ``cat(...).mean(dim=0)`` also averages ACROSS images and is only meaningful at B = 1, where the two agree.  Square
+    input runs as one call ``fn(cat of the 8 B copies)``, non-square input as two calls of 4 B (H x W, then W x H).  The
+    mean is formed as seven fp32 adds in k order times 0.125 (torch's ``mean`` does not fix a summation order)."""
+    B = x.shape[0]
+    xs = [x8_transform(x, k) for k in range(8)]
+    if x.shape[2] == x.shape[3]:
+        ys = list(fn(torch.cat(xs, 0)).float().split(B, 0))
+    else:
+        ys = list(fn(torch.cat(xs[:4], 0)).float().split(B, 0)) + list(fn(torch.cat(xs[4:], 0)).float().split(B, 0))
+    acc = x8_inverse(ys[0], 0)
+    for k in range(1, 8):
+        acc = acc + x8_inverse(ys[k], k)
+    return acc * 0.125
+
+
+def run_rrdbnet_x8(net, x, slots_per_pass=None):
+    """Geometric self-ensemble of RRDBNet (the reference's ``SRModel.test_x8``, codes/models/SR_model.py:82-120) as
+    batched launch plans: the eight flip / transpose copies of ``x`` are written straight into the plan's input buffer,
+    run as one batch of 8 B (non-square input: 4 B at H x W, then 4 B at W x H), and the inverse transforms and the mean
+    are one reduce into the result.  Noise is off whatever ``net.training`` is (the reference calls ``eval()`` first); the
+    module's mode and every ``requires_grad`` are left untouched; the result [B, out_nc, 4H, 4W] fp32 carries no
+    gradient.  B > 1 is ensembled PER IMAGE (the reference's ``cat`` + ``mean(dim=0)`` would also average across the
+    images and is only meaningful at B = 1).  slots_per_pass (8, 4, 2 or 1; default ESR_X8_SLOTS, else 8 for square and 4
+    for non-square input) bounds the memory of large images: each pass runs slots x B copies."""
+    if x.dim() == 4 and x.shape[0] == 0:
+        E.require_cuda(x, 'input')
+        return x.new_zeros((0, net.out_nc, 4 * x.shape[2], 4 * x.shape[3]), dtype=torch.float32)
+    xin = _prep_input(x, 'input')
+    B, C_, H, W = xin.shape
+    if C_ != net.in_nc:
+        raise ValueError('expected %d input channels, got %d' % (net.in_nc, C_))
+    slots = E.x8_slots(H, W, slots_per_pass)
+    order = E.StreamOrder.of(net)
+    cur = order.enter()
+    wp = net._weights(xin.device)
+    key = ('x8', slots, B, H, W, net.precision, False, False, wp.generation)
+    plan = net._plans.get(key)
+    if plan is None:
+        if len(net._plans) >= net.max_cached_plans:
+            net._plans.clear()
+        plan = E.build_rrdbnet_x8_plan(wp, net.nb, net.in_nc, net.out_nc, B, H, W, net.precision, xin.device,
+                                       net.variant, slots)
+        net._plans[key] = plan
+    out = torch.empty(plan.out_shape, dtype=torch.float32, device=xin.device)
+    plan.run(xin, out, E.current_stream())
+    order.leave(cur)
+    return out

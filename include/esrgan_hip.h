@@ -192,6 +192,34 @@ typedef struct esr_layout {
   int32_t _pad;
 } esr_layout;
 
+/* Geometric self-ensemble ends (the reference's `SRModel.test_x8`, codes/models/SR_model.py:82-120: eight flip /
+ * transpose copies of the LR image, eight forwards, each inverse applied to its SR output, mean).  Transform k = 0..7 in
+ * the reference's list order, v = k & 1 (flip along W), h = k & 2 (flip along H), t = k & 4 (transpose, applied last):
+ *   ys(i) = h ? H-1-i : i,   xs(j) = v ? W-1-j : j                      (H x W = the NCHW side)
+ *   slot_k[y][x] = src[ys(y)][xs(x)]   (k < 4, an H x W image)      slot_k[p][q] = src[ys(q)][xs(p)]   (k >= 4, W x H)
+ *   R_k(o)[y][x] = o_k[ys(y)][xs(x)]   (k < 4)                      R_k(o)[y][x] = o_k[xs(x)][ys(y)]   (k >= 4)
+ * Slot s (0 <= s < k_count, k = k_begin + s) of image b is batch index s * B + b of the G32 view; a range may contain
+ * both k < 4 and k >= 4 only when H == W (else ESR_ERR_INVALID).  One channel group: C <= 16 (fp16) / 8 (fp32), else
+ * ESR_ERR_UNSUPPORTED.
+ *   to_g32 = 1  import: reads nchw [B][C][H][W] once and writes the logical pixels of every slot of the range (channels
+ *               padded with zeros to the group; the halo is never touched).
+ *   to_g32 = 0  reduce: acc = accumulate ? nchw : 0;  acc += R_k(o_k) for k ascending (one fp32 add per k);
+ *               nchw = acc * scale.  scale = 0.125 on the last range gives the reference's cat(...).mean(0); the result
+ *               does not depend on how the eight slots are split into ranges (accumulate chains them, scale = 1 before
+ *               the last).  slots_nchw (optional, C <= 8): the slots are read from fp32 NCHW [k_count * B][C][h][w]
+ *               (h x w = H x W for k < 4, W x H for k >= 4) instead of the G32 view — what a conv's nchw_out leaves,
+ *               unrounded in either precision; g32 is then unused.                                                  */
+typedef struct esr_dihedral {
+  int32_t dtype, to_g32;
+  int32_t B, C, H, W;
+  float* nchw;
+  esr_g32 g32;
+  int32_t k_begin, k_count;
+  int32_t accumulate;
+  float scale;
+  const float* slots_nchw;
+} esr_dihedral;
+
 /* Philox-4x32-7 + Box-Muller N(0,1) fill (csrc/common.h), NCHW fp32 — the exact z the fused noise epilogue uses for
  * (seed, layer); lets tests feed the same z to the oracle (GaussianNoise, block.py:117-122). */
 typedef struct esr_noise_fill {
@@ -548,7 +576,7 @@ enum esr_op_kind { ESR_OP_CONV = 1, ESR_OP_PACK = 2, ESR_OP_LAYOUT = 3, ESR_OP_N
                    ESR_OP_WGRAD = 5, ESR_OP_BN = 6, ESR_OP_POOL = 7, ESR_OP_LINEAR = 8,
                    ESR_OP_UNPERMUTE = 9, ESR_OP_PACK_BATCH = 10,
                    ESR_OP_RDB_CHAIN = 11, ESR_OP_FRAG_GATHER = 12, ESR_OP_RDB_WGRAD = 13,
-                   ESR_OP_RDB_CHAIN_BWD = 14 /* u.rdb_chain with mode 2 */ };
+                   ESR_OP_RDB_CHAIN_BWD = 14 /* u.rdb_chain with mode 2 */, ESR_OP_DIHEDRAL = 15 };
 
 /* esr_op.flags */
 #define ESR_OPF_SIDE 1   /* on a run of consecutive ESR_OP_WGRAD ops: launch the run on the library's side
@@ -590,6 +618,7 @@ typedef struct esr_op {
     esr_rdb_chain rdb_chain;
     esr_frag_gather frag_gather;
     esr_rdb_wgrad rdb_wgrad;
+    esr_dihedral dihedral;
   } u;
 } esr_op;
 
@@ -601,6 +630,7 @@ int esr_conv_forward(const esr_conv* p, esr_stream_t stream);
 int esr_pack_conv_weights(const esr_pack* p, esr_stream_t stream);
 int esr_convert_layout(const esr_layout* p, esr_stream_t stream);
 int esr_fill_noise(const esr_noise_fill* p, esr_stream_t stream);
+int esr_dihedral_op(const esr_dihedral* p, esr_stream_t stream);   /* added under ABI 6: a pure addition */
 int esr_conv_wgrad(const esr_wgrad* p, esr_stream_t stream);
 /* n independent weight-gradient problems (disjoint dw/dbias blocks).  fp16 3x3/s1 and 1x1 entries are
  * packed, up to 8 at a time, into ONE launch (at training sizes a single conv's wgrad is ~64
@@ -698,7 +728,7 @@ int esr_graph_destroy(esr_graph_t g);
 int esr_run_ops_timed(const esr_op* ops, int32_t n, esr_stream_t stream, float* ms_out);
 
 const char* esr_last_error(void);
-int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
+int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
                                 esr_l1_loss, esr_ragan_loss, ESR_OPF_SIDE_FREE) */
 size_t esr_sizeof_op(void);
 

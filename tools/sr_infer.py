@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """Inference harness reproducing the reference's ``test_image/test.py`` (lines 9-40) on the HIP path
-with PIL instead of cv2:  python tools/sr_infer.py <model.pth|synthetic> <in_dir> <out_dir> [fp16|fp32]
+with PIL instead of cv2:  python tools/sr_infer.py <model.pth|synthetic> <in_dir> <out_dir> [fp16|fp32] [--x8]
 
-Per image: RGB /255 -> NCHW float32 -> RRDB_Net(3,3,64,23,...) -> clamp(0,1) -> *255 round -> PNG."""
+Per image: RGB /255 -> NCHW float32 -> RRDB_Net(3,3,64,23,...) -> clamp(0,1) -> *255 round -> PNG.
+--x8: the geometric self-ensemble (the reference's ``SRModel.test_x8``, codes/models/SR_model.py:82-120) in place of the
+plain forward: ``model.forward_x8``."""
 import glob
 import os
 import sys
@@ -16,8 +18,10 @@ from esrganplus_amd import architecture as arch, synth
 
 
 def main():
-    model_path, in_dir, out_dir = sys.argv[1], sys.argv[2], sys.argv[3]
-    prec = sys.argv[4] if len(sys.argv) > 4 else 'fp32'
+    argv = [a for a in sys.argv[1:] if a != '--x8']
+    x8 = '--x8' in sys.argv[1:]
+    model_path, in_dir, out_dir = argv[0], argv[1], argv[2]
+    prec = argv[3] if len(argv) > 3 else 'fp32'
     dev = torch.device('cuda')
     model = arch.RRDB_Net(3, 3, 64, 23, gc=32, upscale=4, norm_type=None, act_type='leakyrelu',
                           mode='CNA', res_scale=1, upsample_mode='upconv')
@@ -33,7 +37,7 @@ def main():
         img = np.array(Image.open(path).convert('RGB')).astype(np.float64) / 255
         x = torch.from_numpy(np.transpose(img, (2, 0, 1))).float().unsqueeze(0).to(dev)
         with torch.no_grad():
-            out = model(x).data.squeeze().float().cpu().clamp_(0, 1).numpy()
+            out = (model.forward_x8(x) if x8 else model(x)).data.squeeze().float().cpu().clamp_(0, 1).numpy()
         out = (np.transpose(out, (1, 2, 0)) * 255.0).round().astype(np.uint8)
         Image.fromarray(out).save(os.path.join(out_dir, '%s_rlt.png' % base))
         print(idx, base, img.shape[:2], '->', out.shape[:2])
