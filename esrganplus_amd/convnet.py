@@ -647,6 +647,20 @@ def run_pass_into(Q, gx_into=None, accumulate=False):
     Q.bwd.run(E.current_stream())
 
 
+def bind_param_grads(Q, mod):
+    """Points the `.grad` of `mod`'s parameters at views of Q.grad_flat (made once; pspec order): what run_pass_into left
+    there is what an optimizer reads, in place."""
+    if Q.param_views is None:
+        views, off = [], 0
+        for numel, shape in Q.grad_views:
+            views.append(Q.grad_flat[off:off + numel].view(shape))
+            off += numel
+        Q.param_views = views
+        Q.param_list = [t for _, t in mod._pspec()]
+    for p, v in zip(Q.param_list, Q.param_views):
+        p.grad = v
+
+
 class SeqNetFn(torch.autograd.Function):
     """One autograd node for a whole feed-forward plan."""
 

@@ -620,54 +620,16 @@ def current_stream():
 _concurrent_cache = {}
 
 
-def concurrent_streams(device, n, probe=True):
-    """n torch streams on `device` that really run NEXT TO the current stream and next to each other.  HIP maps streams
-    onto a few hardware queues (GPU_MAX_HW_QUEUES, default 4) and two streams on one queue serialise; measured on
-    MI355X / ROCm 7.2 (tools/stream_probe.py): the FIRST stream a process creates shares its queue with the default
-    stream — the train step's "side" stream of round 3, whose D step therefore never overlapped the main stream's
-    work.  Probe: hold one workgroup on a (esr_debug_hold_cus, released as soon as the answer is known) and see whether
-    a tiny kernel on b completes meanwhile, both directions, against the current stream and the streams already
-    chosen.  Cached per (device, current stream).  probe=False: plain new streams."""
-    import time
+def concurrent_streams(device, n):
+    """n torch streams on `device` for work next to the current stream: plain new streams, cached per (device, current
+    stream).  HIP maps streams onto a few hardware queues (GPU_MAX_HW_QUEUES, default 4) and two streams on one queue
+    serialise; measured on MI355X / ROCm 7.2 (tools/stream_probe.py): the FIRST stream a process creates shares its
+    queue with the default stream — the train step's "side" stream of round 3, whose D step therefore never
+    overlapped the main stream's work."""
     dev = torch.device(device)
-    cur = torch.cuda.current_stream(dev)
-    key = (dev.index, cur.cuda_stream)
-    have = _concurrent_cache.setdefault(key, [])
-    if len(have) >= n:
-        return have[:n]
-    if not probe or torch.cuda.is_current_stream_capturing():
-        while len(have) < n:
-            have.append(torch.cuda.Stream(device=dev))
-        return have[:n]
-    words = torch.zeros(16, dtype=torch.int32).pin_memory()
-    p_release, p_started = C.c_void_p(words.data_ptr()), C.c_void_p(words.data_ptr() + 4)
-    x = torch.zeros(64, device=dev)
-
-    def runs_next_to(a, b):
-        # tiny kernel on b while one workgroup is held on a
-        torch.cuda.synchronize(dev)
-        words.zero_()
-        L.check(L.lib().esr_debug_hold_cus(1, p_release, 20, p_started, C.c_void_p(a.cuda_stream)), 'esr_debug_hold_cus')
-        t0 = time.perf_counter()
-        with torch.cuda.stream(b):
-            x.add_(1.0)
-        b.synchronize()
-        dt = time.perf_counter() - t0
-        words[0] = 1
-        torch.cuda.synchronize(dev)
-        return dt < 0.008
-
-    keep = []          # rejected candidates stay alive until the search ends (a freed stream's slot would be re-issued)
-    for _ in range(24):
-        if len(have) >= n:
-            break
-        cand = torch.cuda.Stream(device=dev)
-        if all(runs_next_to(o, cand) and runs_next_to(cand, o) for o in [cur] + have):
-            have.append(cand)
-        else:
-            keep.append(cand)
-    while len(have) < n:                         # nothing better found: serialising streams still give correct results
-        have.append(keep.pop() if keep else torch.cuda.Stream(device=dev))
+    have = _concurrent_cache.setdefault((dev.index, torch.cuda.current_stream(dev).cuda_stream), [])
+    while len(have) < n:
+        have.append(torch.cuda.Stream(device=dev))
     return have[:n]
 
 

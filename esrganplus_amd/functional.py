@@ -319,7 +319,7 @@ def rrdbnet_train_forward(net, x, z=None):
     dp.ensure(st, force=not net._dgrad_fresh())
     pack_ev = None
     if dp.pack_count != n_packs and not torch.cuda.is_current_stream_capturing():
-        # the input-gradient operands were re-packed on THIS stream just now (first step, ESR_PREPACK=0, after
+        # the input-gradient operands were re-packed on THIS stream just now (first step, after
         # load_state_dict / resume): whoever gathers the backward chain's weight streams from dp.arena on another
         # stream (`rrdbnet_train_prepare` on the train step's side stream) has to wait for it — recorded here, in
         # front of the forward's launches, so that the wait does not cover the forward

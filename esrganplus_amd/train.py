@@ -18,10 +18,26 @@ import os
 
 import torch
 
+from . import convnet as CN
 from . import dp as DP
 from . import engine as E
+from . import functional as Fn
 from . import losses as LS
 from .optim import FusedAdam, DynamicLossScaler
+
+# the step's log (SRRaGAN_model.py:171-186), in the order the logging form copies it to the host
+LOG_KEYS = ('l_g_pix', 'l_g_fea', 'l_g_gan', 'l_d_real', 'l_d_fake', 'D_real', 'D_fake')
+
+
+def _log_values(l_g_pix, l_g_fea, l_g_gan, aux):
+    return (l_g_pix, l_g_fea, l_g_gan, aux[2], aux[3], aux[0], aux[1])          # LOG_KEYS order
+
+
+def _buffer_like(buf, ref):
+    """`buf` when it has `ref`'s shape and device, else a new (uninitialised) tensor like `ref`."""
+    if buf is None or buf.shape != ref.shape or buf.device != ref.device:
+        buf = torch.empty_like(ref)
+    return buf
 
 
 class ESRGANPlusStep:
@@ -49,20 +65,22 @@ class ESRGANPlusStep:
         self.log = {}
         self.fake_H = None
         self._steps = 0
+        # what the hand-written step keeps between calls: the buffers dL/d fake_H is collected in, the pinned host copy
+        # of the log, the event behind the tail a step left on the side stream; the static loss scale as a device scalar
+        # (autograd form); `_marks`: a list set from outside (tools/train_marks.py) collects (name, timed event) pairs
+        self._gy = self._gy2 = self._log_host = self._ev_tail = None
+        self._scale_tensor = self._scale_value = None
+        self._marks = None
         # stream overlap of the step (ESR_TRAIN_OVERLAP): 0 = everything in sequence on the caller's stream (9.8 ms);
-        # 1 (default) = netF(var_H) and the D step on a second stream (8.9 ms); 2 = additionally the G step's netD
-        # pass on a third stream next to its netF pass, forward AND backward (autograd runs a node's backward on the
-        # stream its forward ran on).  Measured, round 4 (profiles/r04_experiments.md): more concurrency is NOT faster
-        # here — 2 costs 0.1-0.15 ms over 1, streams probed to be truly concurrent (engine.concurrent_streams,
-        # ESR_STREAM_PROBE=1) 0.4-0.9 ms, GPU_MAX_HW_QUEUES=8 3-5 ms: a persistent chain launch (128 lock-stepped
-        # workgroups exchanging halos) that shares the chip with other launches runs at the pace of its most-delayed
-        # tile, and the small launches slow each other 2-5x.  What mode 1 overlaps is what the default stream's
-        # hardware queue lets through.
-        self.overlap = self._knob_int('ESR_TRAIN_OVERLAP', '1', (0, 1, 2))
+        # 1 (default) = netF(var_H) and the D step on a second stream (8.9 ms).  Measured, round 4
+        # (profiles/r04_experiments.md): more concurrency is NOT faster here — the G step's netD pass on a third stream
+        # next to its netF pass costs 0.1-0.15 ms over 1, streams probed to be truly concurrent 0.4-0.9 ms,
+        # GPU_MAX_HW_QUEUES=8 3-5 ms: a persistent chain launch (128 lock-stepped workgroups exchanging halos) that
+        # shares the chip with other launches runs at the pace of its most-delayed tile, and the small launches slow
+        # each other 2-5x.  What mode 1 overlaps is what the default stream's hardware queue lets through.
+        self.overlap = self._knob_int('ESR_TRAIN_OVERLAP', '1', (0, 1))
         # ESR_SHARED_D=0: the D step runs its own forward pair (round 3) instead of re-using the G step's pass
         self.shared_d = os.environ.get('ESR_SHARED_D', '1') != '0'
-        # ESR_PREPACK=0: every network packs its weights at the start of its next training forward (round 3)
-        self.prepack = os.environ.get('ESR_PREPACK', '1') != '0'
         # ESR_TRAIN_MANUAL=0: the step is written with autograd (losses as autograd Functions, torch.autograd.backward
         # over the three networks' nodes: ~100 glue launches — clones, gradient copies / sums, zero fills — and their
         # host time per step).  Default: the same launch lists driven directly (`_step_manual`), when the networks
@@ -71,7 +89,7 @@ class ESRGANPlusStep:
         # netF(fake): forward, feature loss and input-gradient pass on the SIDE stream, next to netD's forward and its
         # G-step pass on the main stream (both hang off fake_H only; their two contributions to dL/d fake_H meet in one add)
         self.netf_side = os.environ.get('ESR_TRAIN_NETF_SIDE', '1') == '1'
-        self.d_when = self._knob('ESR_TRAIN_DSTEP', 'last', ('first', 'mid', 'last'))       # see _step_manual
+        self.d_when = self._knob('ESR_TRAIN_DSTEP', 'last', ('first', 'mid', 'last'))       # see _ManualPass.place_d_step
         # The logging form (sync_log=True: the host reads the losses every step and the call returns with the D-side tail
         # ordered on the caller's stream) wants the D step EARLY and the follower pass of G's weight gradients BIG: the main
         # stream waits for the side stream's tail at the end of the call, so what the D step gains by running late under the
@@ -81,15 +99,9 @@ class ESRGANPlusStep:
         self.d_when_sync = self._knob('ESR_TRAIN_DSTEP_SYNC', os.environ.get('ESR_TRAIN_DSTEP', 'mid'), ('first', 'mid', 'last'))
         fw = os.environ.get('ESR_TRAIN_SYNC_FOLLOW_WGS', '' if os.environ.get('ESR_BWD_FOLLOW_WGS') else '128')
         self.follow_wgs_sync = int(fw) if fw else None
-        # host enqueue order of netD's forward vs netF(fake)
-        self.order = self._knob('ESR_TRAIN_ORDER', 'main_first', ('main_first', 'side_first'))
-        self.tail_side = os.environ.get('ESR_TRAIN_TAIL_SIDE', '1') == '1'
-        self.prep_side = os.environ.get('ESR_TRAIN_PREP_SIDE', '1') == '1'      # A/B knob (round 5)
         # netD's forward in two stages: the `real` half on the side stream under the generator's forward (its input is
         # known when the step starts), the `fake` half alone behind the generator (A/B knob, round 5)
         self.d_split = os.environ.get('ESR_TRAIN_DSPLIT', '1') == '1'
-
-        self.overlap_d_step = self.overlap >= 1
 
     @staticmethod
     def _knob(name, default, allowed):
@@ -102,14 +114,12 @@ class ESRGANPlusStep:
     def _knob_int(cls, name, default, allowed):
         return int(cls._knob(name, default, tuple(str(a) for a in allowed)))
 
-    def _side(self, dev, which=0):
-        # ESR_STREAM_PROBE=1: streams PROBED to run concurrently with the caller's stream and with each other
-        # (engine.concurrent_streams: the first stream a process creates shares the default stream's hardware queue);
-        # default: plain new streams, which measured faster (see `overlap` above)
-        return E.concurrent_streams(dev, 2, probe=os.environ.get('ESR_STREAM_PROBE', '0') == '1')[which]
+    def _side(self, dev):
+        # a plain new stream (cached), which measured faster than one probed to run concurrently (see `overlap` above)
+        return E.concurrent_streams(dev, 1)[0]
 
     def _scale_t(self, dev):
-        t = self.__dict__.get('_scale_tensor')
+        t = self._scale_tensor
         if t is None or t.device != dev or float(self._scale_value) != float(self.loss_scale):
             t = self._scale_tensor = torch.full((), float(self.loss_scale), dtype=torch.float32, device=dev)
             self._scale_value = float(self.loss_scale)
@@ -149,263 +159,53 @@ class ESRGANPlusStep:
             last layout ops of netF's and netD's input-gradient passes ADD into it (esr_layout.accumulate);
           * netD's parameter gradients stay in its plan's flat buffer (the parameters' .grad are persistent views of
             it: FusedAdam reads them in place); RRDBNet's leave the backward as one flat buffer which the parameters'
-            `.grad` alias (`_deliver_flat_grads(adopt=True)`: no copy) and FusedAdam reads in place."""
-        from . import functional as Fn
-        from . import convnet as CN
-        netG, netD, netF = self.netG, self.netD, self.netF
-        dev = var_L.device
-        S = float(self.loss_scale)
-        sdev = self.scaler.state if self.scaler else None          # state[0] = the dynamic loss scale (device)
-        mean = self.data_parallel
-        ov = self.overlap
-        n = var_L.shape[0]
-        main = torch.cuda.current_stream()
-        side = self._side(dev, 0) if ov >= 1 else None
-        if not netG.mark_grads_stale():
+            `.grad` alias (`_deliver_flat_grads(adopt=True)`: no copy) and FusedAdam reads in place.
+        The phases are `_ManualPass`'s methods; the order below is the order in which the HOST enqueues them."""
+        p = _ManualPass(self, var_L, sync_log)
+        if not self.netG.mark_grads_stale():
             self.optimizer_G.zero_grad(set_to_none=True)
-        marks = self.__dict__.get('_marks')          # measurement (tools/train_marks.py): timed events on the main stream
-
-        def mark(name):
-            if marks is not None:
-                e = torch.cuda.Event(enable_timing=True)
-                e.record(main)
-                marks.append((name, e))
-        mark('start')
+        p.mark('start')
         with torch.no_grad():
-            if ov >= 1:
-                ev0 = torch.cuda.Event()
-                ev0.record(main)                              # var_H (and whatever the caller did before the step)
-            # the generator's forward is enqueued FIRST: a loop that reads its losses every step has the host running
-            # behind the GPU, and the step's critical path starts with this launch list, not with netF(real)'s
-            fake, stG = Fn.rrdbnet_train_forward(netG, var_L, z)
-            self.fake_H = fake
-            mark('G forward')
-            ev_prep = None
-            dsplit = (self.d_split and ov >= 1 and netD._has_bn and netD.training and not E.use_graphs()
-                      and not getattr(netD, '_per_call_weights', False))
-            d_early = None
-            if ov >= 1:
-                side.wait_event(ev0)
-                with torch.cuda.stream(side):
-                    real_fea = netF._run_forward(var_H, need_bwd=False)[0]
-                    if self.prep_side:
-                        # the G backward's step-independent preliminaries (zero fills of the gradient buffers, the backward
-                        # chain's weight-stream gather) under the generator's forward instead of in front of the backward
-                        Fn.rrdbnet_train_prepare(netG, stG)
-                        ev_prep = torch.cuda.Event()
-                        ev_prep.record(side)
-                    if dsplit:
-                        # netD(real): the previous step's D-side tail (Adam, packs) sits on this stream, in front of it
-                        var_ref.record_stream(side)
-                        d_early = netD._pair_begin(var_ref) + (torch.cuda.Event(),)
-                        d_early[2].record(side)
-                real_fea.record_stream(main)
-            gy = self.__dict__.get('_gy')
-            if gy is None or gy.shape != fake.shape or gy.device != fake.device:
-                gy = self._gy = torch.empty_like(fake)
-            l_g_pix = LS.l1_raw(fake, var_H, self.l_pix_w, grad_out=gy, grad_scale=S, scale_dev=sdev)
-            nf_side = self.netf_side and ov >= 1
-            box = {}
+            p.generator_forward(var_L, z)
+            p.under_generator_forward(var_H, var_ref)
+            p.pixel_loss(var_H)
+            p.feature_and_gan_forward(var_H, var_ref)
+            if p.side is not None:
+                # all the D step waits for, WHEREVER it is enqueued below: netD's forward and the GAN loss (not the G backward)
+                p.side.wait_stream(p.main)
+            p.place_d_step('first')
+            p.input_gradients()
+            p.place_d_step('mid')
+            p.generator_backward()
+            p.place_d_step('last')
+            p.leaseF.release()
+            p.leaseD.release()
+            p.gather_log()
+            p.tail()
+        return p.read_log()
 
-            def netf_fake():
-                fake_fea, leaseF = netF._run_forward(fake, need_bwd=True)
-                PF = leaseF.plan
-                box['leaseF'], box['PF'] = leaseF, PF
-                box['l_g_fea'] = LS.l1_raw(fake_fea, real_fea, self.l_fea_w, grad_out=PF.gy_tensor, grad_scale=S, scale_dev=sdev)
-
-            def netd_fwd():
-                ev = self.__dict__.get('_ev_tail')
-                if ev is not None:
-                    main.wait_event(ev)                       # the previous step's D step, D's Adam and packs (side stream)
-                # ONE netD forward for the step's four calls (forward_shared): groups (fake, real)
-                if d_early is not None:
-                    PD, leaseD = d_early[0], d_early[1]
-                    main.wait_event(d_early[2])               # the real half (side stream)
-                    out = netD._pair_finish(PD, fake)
-                else:
-                    out, leaseD = netD._run_forward(torch.cat([fake, var_ref]), need_bwd=True, groups=2 if netD._has_bn else 1, dual=n)
-                    PD = leaseD.plan
-                if side is not None:
-                    out.record_stream(side)                   # (the D step reads it there)
-                box['leaseD'], box['PD'], box['pg'], box['pr'] = leaseD, PD, out[:n], out[n:]
-                # G step: BCE(pred_d_real - mean(pred_g_fake), 0) + BCE(pred_g_fake - mean(pred_d_real), 1), gradient to the fake half
-                box['l_g_gan'], _ = LS.ragan_raw(out[n:], out[:n], False, True, self.l_gan_w, grad_x=None, grad_y=PD.second.gy_tensor,
-                                                 grad_scale=S, scale_dev=sdev, global_mean=mean)
-
-            if nf_side:
-                # netF(fake) — forward, feature loss, input-gradient pass — on the side stream next to netD's forward and
-                # G-step pass on the main stream.  The HOST enqueues the main stream's netD forward first (it is the longer
-                # chain: the G backward hangs off it); the two input gradients meet in one add.
-                gy2 = self.__dict__.get('_gy2')
-                if gy2 is None or gy2.shape != fake.shape or gy2.device != fake.device:
-                    gy2 = self._gy2 = torch.empty_like(fake)
-                side.wait_stream(main)                        # fake_H
-                fake.record_stream(side)
-                if self.order == 'main_first':
-                    netd_fwd()
-                with torch.cuda.stream(side):
-                    netf_fake()
-                    CN.run_pass_into(box['PF'], gx_into=gy2, accumulate=False)
-                    ev_f = torch.cuda.Event()
-                    ev_f.record(side)
-                if self.order != 'main_first':
-                    netd_fwd()
-            else:
-                if ov >= 1:
-                    main.wait_stream(side)
-                else:
-                    real_fea = netF._run_forward(var_H, need_bwd=False)[0]
-                netf_fake()
-                netd_fwd()
-            leaseF, PF, l_g_fea = box['leaseF'], box['PF'], box['l_g_fea']
-            leaseD, PD, pg, pr, l_g_gan = box['leaseD'], box['PD'], box['pg'], box['pr'], box['l_g_gan']
-            mark('pixel loss, netD(fake) forward, GAN loss')
-            ev_glog = None
-            if sync_log and ov >= 1:
-                ev_glog = torch.cuda.Event()          # the G step's three losses are enqueued (main; l_g_fea maybe on side)
-                ev_glog.record(main)
-
-            def d_step():
-                # D step (SRRaGAN_model.py:143-168): the second pair of calls sees the first pair's values
-                if d_early is not None and PD.restat1.ops:
-                    PD.restat1.run(E.current_stream())            # the running-statistics update the early half still owes
-                if PD.restat is not None and PD.restat.ops:
-                    PD.restat.run(E.current_stream())
-                gyt = PD.gy_tensor                                # plan order [fake; real]
-                l_d, aux = LS.ragan_raw(pr, pg, True, False, 1.0, grad_x=gyt[n:], grad_y=gyt[:n],
-                                        grad_scale=S, scale_dev=sdev, global_mean=mean)
-                CN.run_pass_into(PD)
-                if PD.param_views is None:
-                    views, off = [], 0
-                    for numel, shape in PD.grad_views:
-                        views.append(PD.grad_flat[off:off + numel].view(shape))
-                        off += numel
-                    PD.param_views = views
-                    PD.param_list = [t for _, t in netD._pspec()]
-                for p_, v in zip(PD.param_list, PD.param_views):
-                    p_.grad = v
-                self.exD.start()
-                return aux
-
-            # When the host enqueues the D step (~60 launches, ~0.5-1 ms of host time during which the main stream gets
-            # nothing new).  Round 4, same box, ms per step with netF(fake) on the main / side stream: 'first' (before
-            # the main stream's backward passes) 8.03 / 7.92, 'mid' 8.05 / 7.92, 'last' (behind the G backward's launch:
-            # it then runs under the backward chain) 8.35 / 7.57.
-            # Where the HOST enqueues it matters as much: the D step is ~60 launches (~1 ms of host time) during which the
-            # main stream gets nothing new.  'mid': the main stream's netD / netF input-gradient passes (two C calls,
-            # ~0.9 ms of GPU work) go out first and run while the host enqueues the D step; the G backward follows.
-            d_when = self.d_when_sync if sync_log else self.d_when
-            if ov >= 1:
-                side.wait_stream(main)
-                if d_when == 'first':
-                    with torch.cuda.stream(side):
-                        aux = d_step()
-            # dL/d fake_H: + d l_gan (netD, first pair) + d l_fea (netF), added by the passes' last layout ops
-            CN.run_pass_into(PD.second, gx_into=gy, accumulate=True)
-            mark('netD input-gradient pass (G step)')
-            if nf_side:
-                main.wait_event(ev_f)
-                gy.add_(gy2)
-                mark('wait for netF(fake) pass, add')
-            else:
-                CN.run_pass_into(PF, gx_into=gy, accumulate=True)
-            if ov >= 1 and d_when == 'mid':
-                with torch.cuda.stream(side):
-                    aux = d_step()
-            if ev_prep is not None:
-                main.wait_event(ev_prep)
-            Fn.rrdbnet_train_backward(netG, stG, gy, follow_wgs=self.follow_wgs_sync if sync_log else None)
-            mark('G backward (tail, chain, weight gradients, unpermute)')
-            self.exG.start()
-            if ov >= 1:
-                if d_when == 'last':
-                    with torch.cuda.stream(side):
-                        aux = d_step()
-            else:
-                aux = d_step()
-            leaseF.release()
-            leaseD.release()
-            inv = 1.0 / self.loss_scale
-            # The step's tail.  tail_side (static loss scale): the main stream only carries what the NEXT generator forward
-            # waits for — G's Adam and the pack of its forward weights; the D step's end, D's Adam, D's packs and G's
-            # input-gradient packs stay on the side stream, and the main stream meets them again (ev_tail) in front of the
-            # next netD forward.
-            # Only in the pipelined form of the call (sync_log=False: the caller reads nothing before `finish()` / a device
-            # synchronisation); the default call returns with everything ordered on the current stream.
-            # sync_log (the reference reads seven .item()s per step, SRRaGAN_model.py:171-186): round 5 — the host no longer
-            # waits for the END of the step.  The seven scalars are gathered and copied to pinned memory on the side stream
-            # right behind the D step's loss kernel (ev_log); the tail below is enqueued first, THEN the host waits for
-            # ev_log only: it returns ~1.3 ms of GPU work early and enqueues the next step under the rest of this one
-            # (8.1 -> ~7 ms per step for a loop that logs every step).
-            ev_log, log_keep = None, None
-            if ev_glog is not None:
-                with torch.cuda.stream(side):
-                    side.wait_event(ev_glog)
-                    host = self.__dict__.get('_log_host')
-                    if host is None:
-                        host = self._log_host = torch.empty(7, dtype=torch.float32).pin_memory()
-                    log_keep = torch.stack([t.detach().reshape(()).float() for t in
-                                            (l_g_pix, l_g_fea, l_g_gan, aux[2], aux[3], aux[0], aux[1])])
-                    host.copy_(log_keep, non_blocking=True)
-                    ev_log = torch.cuda.Event()
-                    ev_log.record(side)
-            tail_side = ov >= 1 and self.tail_side and self.scaler is None
-            if not tail_side:
-                if ov >= 1:
-                    main.wait_stream(side)
-                self.exG.wait()
-                self.optimizer_G.step(grad_scale=inv, scaler=self.scaler)
-                self.exD.wait()
-                self.optimizer_D.step(grad_scale=inv, scaler=self.scaler)
-                if self.scaler:
-                    self.scaler.update()
-                if self.prepack:
-                    netG.prepack(fwd=True, dgrad=False)
-                    if ov >= 1:
-                        side.wait_stream(main)
-                        with torch.cuda.stream(side):
-                            netD.prepack()
-                            netG.prepack(fwd=False, dgrad=True)
-                    else:
-                        netD.prepack()
-                        netG.prepack(fwd=False, dgrad=True)
-                if ov >= 1:
-                    self._ev_tail = torch.cuda.Event()
-                    self._ev_tail.record(side)
-                    self._defer_networks(self._ev_tail)
-            else:
-                self.exG.wait()
-                self.optimizer_G.step(grad_scale=inv, scaler=None)
-                if self.prepack:
-                    netG.prepack(fwd=True, dgrad=False)
-                mark('Adam(G), forward weight pack')
-                side.wait_stream(main)                        # G's new weights (its input-gradient packs read them)
-                with torch.cuda.stream(side):
-                    self.exD.wait()
-                    self.optimizer_D.step(grad_scale=inv, scaler=None)
-                    if self.prepack:
-                        netD.prepack()
-                        netG.prepack(fwd=False, dgrad=True)
-                    self._ev_tail = torch.cuda.Event()
-                    self._ev_tail.record(side)
-                self._defer_networks(self._ev_tail)
-        logs = dict(l_g_pix=l_g_pix, l_g_fea=l_g_fea, l_g_gan=l_g_gan, l_d_real=aux[2], l_d_fake=aux[3],
-                    D_real=aux[0], D_fake=aux[1])
-        if sync_log:
-            if ev_log is not None:
-                ev_log.synchronize()                              # the losses, not the end of the step
-                self.log = dict(zip(('l_g_pix', 'l_g_fea', 'l_g_gan', 'l_d_real', 'l_d_fake', 'D_real', 'D_fake'),
-                                    self._log_host.tolist()))
-                del log_keep
-                # the default call's contract: everything it enqueued is ordered on the CURRENT stream when it returns
-                main.wait_event(self._ev_tail)
-            else:
-                if ov >= 1:
-                    main.wait_stream(side)
-                self.log = {k: float(v) for k, v in logs.items()}
+    def _tail_on_main(self, main, side):
+        """The step's tail ordered on the main stream, behind both backward passes: the two optimizer steps (each
+        behind its gradient exchange), the loss scaler's update, and the next step's weight packs, now: the generator's
+        forward copy on the main stream (the step starts with it anyway), everything that is only needed later — D's two
+        packs, G's input-gradient operands — on the side stream (side=None: inline), next to it and to the start of the
+        next generator forward."""
+        inv = 1.0 / self.loss_scale          # the loss-scale division rides inside the Adam kernel
+        self.exG.wait()
+        self.optimizer_G.step(grad_scale=inv, scaler=self.scaler)
+        self.exD.wait()
+        self.optimizer_D.step(grad_scale=inv, scaler=self.scaler)
+        if self.scaler:
+            self.scaler.update()
+        self.netG.prepack(fwd=True, dgrad=False)
+        if side is not None:
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                self.netD.prepack()
+                self.netG.prepack(fwd=False, dgrad=True)
         else:
-            self.log = logs
-        return self.log
+            self.netD.prepack()
+            self.netG.prepack(fwd=False, dgrad=True)
 
     def _defer_networks(self, ev):
         # the networks' PUBLIC entry points (forward / forward_pair / state_dict) order this event in front of their
@@ -425,9 +225,8 @@ class ESRGANPlusStep:
         """Orders what a pipelined step (``step(..., sync_log=False)``) left on the side stream — the end of the D
         step, D's Adam, the weight packs — in front of the current stream: call it (or synchronise the device) before
         reading the networks' parameters, buffers or the logged losses after such a step."""
-        ev = self.__dict__.get('_ev_tail')
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
+        if self._ev_tail is not None:
+            torch.cuda.current_stream().wait_event(self._ev_tail)
 
     def step(self, var_L, var_H, var_ref=None, z=None, sync_log=True):
         """One optimisation step (SRRaGAN_model.py:113-168).  sync_log=False: the pipelined form for training loops —
@@ -442,17 +241,16 @@ class ESRGANPlusStep:
         # batch means of the relativistic terms: over ALL ranks when data-parallel (losses._RaGANGlobalFn: the fused
         # kernel + two scalar all-reduces), else inside the one fused loss launch
         mean = self.data_parallel
-        cuda = True
-        ov = self.overlap
+        main = side = None
         # ---------------- G ----------------
         for p in netD.parameters():
             p.requires_grad = False
         if not (hasattr(netG, 'mark_grads_stale') and netG.mark_grads_stale()):
             self.optimizer_G.zero_grad(set_to_none=True)     # (first step / gradients that are not the module's store)
-        if ov >= 1:
+        if self.overlap >= 1:
             # netF(var_H) does not depend on G: on the second stream, under the generator's forward
             main = torch.cuda.current_stream()
-            side = self._side(var_L.device, 0)
+            side = self._side(var_L.device)
             side.wait_stream(main)
             with torch.cuda.stream(side), torch.no_grad():
                 real_fea = netF(var_H)
@@ -460,28 +258,7 @@ class ESRGANPlusStep:
         fake_H = netG(var_L, z=z) if z is not None else netG(var_L)
         self.fake_H = fake_H
         l_g_pix = LS.l1_loss(fake_H, var_H, self.l_pix_w)
-
-        shared = self.shared_d and getattr(netD, '_shared_ok', False) and netD.training
-        dh = []
-
-        def d_pass():
-            # both operands in ONE pass (forward_pair: per-half BatchNorm statistics, the detached ``real`` half
-            # costs no backward) — the reference's call order fake, real is the group order.  shared: the same pass
-            # also keeps what the D step's pair needs (forward_shared), so that pair costs no second forward
-            if shared:
-                pg, pr, h = netD.forward_shared(fake_H, var_ref)
-                dh.append(h)
-            else:
-                pg, pr = netD.forward_pair(fake_H, var_ref)
-            return LS.ragan_loss(pr, pg, False, True, self.l_gan_w, mean)[0]
-
-        if ov >= 2:
-            sideD = self._side(var_L.device, 1)
-            sideD.wait_stream(main)
-            sideD.wait_stream(side)               # (netD's weight packs of the previous step's end: prepack)
-            with torch.cuda.stream(sideD):
-                l_g_gan = d_pass()
-        if ov >= 1:
+        if side is not None:
             # join BEFORE netF runs on the main stream: the first netF call of a process packs its weights on the
             # side stream, and the side work finished under the generator's forward anyway
             main.wait_stream(side)
@@ -489,79 +266,304 @@ class ESRGANPlusStep:
         else:
             fake_fea, real_fea = netF.forward_pair(fake_H, var_H)
         l_g_fea = LS.l1_loss(fake_fea, real_fea, self.l_fea_w)
-        if ov < 2:
-            l_g_gan = d_pass()
+        # both operands in ONE pass (forward_pair: per-half BatchNorm statistics, the detached ``real`` half
+        # costs no backward) — the reference's call order fake, real is the group order.  shared: the same pass
+        # also keeps what the D step's pair needs (forward_shared), so that pair costs no second forward
+        shared = None
+        if self.shared_d and getattr(netD, '_shared_ok', False) and netD.training:
+            pg, pr, shared = netD.forward_shared(fake_H, var_ref)
+        else:
+            pg, pr = netD.forward_pair(fake_H, var_ref)
+        l_g_gan = LS.ragan_loss(pr, pg, False, True, self.l_gan_w, mean)[0]
         scale = self.scaler.scale if self.scaler else self._scale_t(fake_H.device)
+        aux = self._backward_autograd((l_g_pix, l_g_fea, l_g_gan), fake_H, var_ref, shared, scale, main, side)
+        # (with overlap: the side stream's packs are joined at the next step's `main.wait_stream(side)` in front of
+        # netF(fake_H): before any consumer)
+        self._tail_on_main(main, side)
+        logs = zip(LOG_KEYS, _log_values(l_g_pix, l_g_fea, l_g_gan, aux))
+        if sync_log:      # the reference calls .item() on every loss each step (SRRaGAN_model.py:171-186)
+            self.log = {k: float(v.detach()) for k, v in logs}
+        else:
+            self.log = {k: v.detach() for k, v in logs}
+        return self.log
 
-        def d_step():
-            # ---------------- D ---------------- (SRRaGAN_model.py:143-168; only needs fake_H's VALUES and D as it is)
-            for p in netD.parameters():
-                p.requires_grad = True
-            self.optimizer_D.zero_grad(set_to_none=True)
-            if shared:
-                pred_d_real, pred_d_fake = dh.pop().second_pass()
-            else:
-                with netD.weights_unchanged():        # no optimizer step since the G step's D pass
-                    pred_d_real, pred_d_fake = netD.forward_pair(var_ref, fake_H.detach())
-            l_d_total, aux = LS.ragan_loss(pred_d_real, pred_d_fake, True, False, 1.0, mean)
-            torch.autograd.backward([l_d_total], [scale])
-            return aux
-
-        def g_backward():
-            # d(scale * (pix + fea + gan)): one backward over the three terms, no sum / multiply launches
-            torch.autograd.backward([l_g_pix, l_g_fea, l_g_gan], [scale, scale, scale])
-
-        if ov >= 1:
+    def _backward_autograd(self, g_losses, fake_H, var_ref, shared, scale, main, side):
+        """The G backward — d(scale * (pix + fea + gan)): one backward over the three terms, no sum / multiply launches —
+        and the D step, each followed by the start of its gradient exchange; returns the D step's `aux`."""
+        g_losses, scales = list(g_losses), [scale] * len(g_losses)
+        if side is not None:
             # The D step does not depend on the G backward: it runs on a second stream UNDER it (both are chains of
             # small launches).  Same arithmetic, same order of BatchNorm running-statistics updates (its forward
             # still follows the G step's D pass); the autograd graphs are disjoint.  Data-parallel runs take the
             # same route: every rank issues its collectives in the same program order (D's loss sums, D's gradient
             # buckets on the side stream; G's in-backward buckets on the main stream), each stream-ordered after
             # the kernels that feed it.
-            if ov >= 2:
-                # fake_H was complete when sideD started; the D step must follow the G step's D pass (BatchNorm
-                # running statistics, the weight pack) but not netF(fake_H) on the main stream
-                side.wait_stream(sideD)
-            else:
-                side.wait_stream(main)
+            side.wait_stream(main)
             with torch.cuda.stream(side):
-                aux = d_step()
+                aux = self._d_step_autograd(fake_H, var_ref, shared, scale)
                 self.exD.start()
-            g_backward()
+            torch.autograd.backward(g_losses, scales)
             self.exG.start()
             main.wait_stream(side)
-            if ov >= 2:
-                main.wait_stream(sideD)
         else:
-            g_backward()
+            torch.autograd.backward(g_losses, scales)
             self.exG.start()                  # RCCL all-reduce of G grads overlaps the D pass below
-            aux = d_step()
+            aux = self._d_step_autograd(fake_H, var_ref, shared, scale)
             self.exD.start()
-        inv = 1.0 / self.loss_scale          # the loss-scale division rides inside the Adam kernel
-        self.exG.wait()
-        self.optimizer_G.step(grad_scale=inv, scaler=self.scaler)
-        self.exD.wait()
-        self.optimizer_D.step(grad_scale=inv, scaler=self.scaler)
-        if self.scaler:
-            self.scaler.update()
-        if self.prepack and cuda:
-            # the next step's weight packs, now: the generator's forward copy on the main stream (the step starts with
-            # it anyway), everything that is only needed later — D's two packs, G's input-gradient operands — on the
-            # side stream, next to it and to the start of the next generator forward
-            netG.prepack(fwd=True, dgrad=False)
-            if ov >= 1:
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    netD.prepack()
-                    netG.prepack(fwd=False, dgrad=True)
-                # (joined at the next step's `main.wait_stream(side)` in front of netF(fake_H): before any consumer)
-            else:
-                netD.prepack()
-                netG.prepack(fwd=False, dgrad=True)
-        logs = dict(l_g_pix=l_g_pix, l_g_fea=l_g_fea, l_g_gan=l_g_gan, l_d_real=aux[2], l_d_fake=aux[3],
-                    D_real=aux[0], D_fake=aux[1])
-        if sync_log:      # the reference calls .item() on every loss each step (SRRaGAN_model.py:171-186)
-            self.log = {k: float(v.detach()) for k, v in logs.items()}
+        return aux
+
+    def _d_step_autograd(self, fake_H, var_ref, shared, scale):
+        # ---------------- D ---------------- (SRRaGAN_model.py:143-168; only needs fake_H's VALUES and D as it is)
+        netD = self.netD
+        for p in netD.parameters():
+            p.requires_grad = True
+        self.optimizer_D.zero_grad(set_to_none=True)
+        if shared is not None:
+            pred_d_real, pred_d_fake = shared.second_pass()
         else:
-            self.log = {k: v.detach() for k, v in logs.items()}
-        return self.log
+            with netD.weights_unchanged():        # no optimizer step since the G step's D pass
+                pred_d_real, pred_d_fake = netD.forward_pair(var_ref, fake_H.detach())
+        l_d_total, aux = LS.ragan_loss(pred_d_real, pred_d_fake, True, False, 1.0, self.data_parallel)
+        torch.autograd.backward([l_d_total], [scale])
+        return aux
+
+
+class _ManualPass:
+    """One call of `ESRGANPlusStep._step_manual`: what its phases hand to each other, and the phases themselves in the
+    order the driver lists them.  Every phase only enqueues; `read_log` is the one place where the host waits."""
+
+    def __init__(self, st, var_L, sync_log):
+        self.st, self.sync_log = st, sync_log
+        self.n = var_L.shape[0]
+        self.S = float(st.loss_scale)
+        self.sdev = st.scaler.state if st.scaler else None          # state[0] = the dynamic loss scale (device)
+        self.main = torch.cuda.current_stream()
+        self.side = st._side(var_L.device) if st.overlap >= 1 else None
+        self.d_when = st.d_when_sync if sync_log else st.d_when
+        self.fake = self.stG = self.real_fea = self.d_early = None
+        self.ev0 = self.ev_prep = self.ev_f = self.ev_glog = self.ev_log = self.log_keep = None
+        self.leaseF = self.PF = self.leaseD = self.PD = self.pg = self.pr = None
+        self.l_g_pix = self.l_g_fea = self.l_g_gan = self.aux = None
+
+    def mark(self, name):
+        marks = self.st._marks          # measurement (tools/train_marks.py): timed events on the main stream
+        if marks is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(self.main)
+            marks.append((name, e))
+
+    def generator_forward(self, var_L, z):
+        st = self.st
+        if self.side is not None:
+            self.ev0 = torch.cuda.Event()
+            self.ev0.record(self.main)                    # var_H (and whatever the caller did before the step)
+        # the generator's forward is enqueued FIRST: a loop that reads its losses every step has the host running
+        # behind the GPU, and the step's critical path starts with this launch list, not with netF(real)'s
+        self.fake, self.stG = Fn.rrdbnet_train_forward(st.netG, var_L, z)
+        st.fake_H = self.fake
+        self.mark('G forward')
+
+    def under_generator_forward(self, var_H, var_ref):
+        """What does not depend on the generator, on the side stream under its forward: netF(real), the G backward's
+        preliminaries, the `real` half of a two-stage netD forward."""
+        st, side = self.st, self.side
+        if side is None:
+            return
+        netD, netF = st.netD, st.netF
+        dsplit = (st.d_split and netD._has_bn and netD.training and not E.use_graphs()
+                  and not getattr(netD, '_per_call_weights', False))
+        side.wait_event(self.ev0)
+        with torch.cuda.stream(side):
+            self.real_fea = netF._run_forward(var_H, need_bwd=False)[0]
+            # the G backward's step-independent preliminaries (zero fills of the gradient buffers, the backward
+            # chain's weight-stream gather) under the generator's forward instead of in front of the backward
+            Fn.rrdbnet_train_prepare(st.netG, self.stG)
+            self.ev_prep = torch.cuda.Event()
+            self.ev_prep.record(side)
+            if dsplit:
+                # netD(real): the previous step's D-side tail (Adam, packs) sits on this stream, in front of it
+                var_ref.record_stream(side)
+                self.d_early = netD._pair_begin(var_ref) + (torch.cuda.Event(),)
+                self.d_early[2].record(side)
+        self.real_fea.record_stream(self.main)
+
+    def pixel_loss(self, var_H):
+        st = self.st
+        st._gy = _buffer_like(st._gy, self.fake)
+        self.l_g_pix = LS.l1_raw(self.fake, var_H, st.l_pix_w, grad_out=st._gy, grad_scale=self.S, scale_dev=self.sdev)
+
+    def netf_fake(self):
+        st = self.st
+        fake_fea, self.leaseF = st.netF._run_forward(self.fake, need_bwd=True)
+        self.PF = self.leaseF.plan
+        self.l_g_fea = LS.l1_raw(fake_fea, self.real_fea, st.l_fea_w, grad_out=self.PF.gy_tensor,
+                                 grad_scale=self.S, scale_dev=self.sdev)
+
+    def netd_forward(self, var_ref):
+        st, main, n, d_early = self.st, self.main, self.n, self.d_early
+        netD = st.netD
+        if st._ev_tail is not None:
+            main.wait_event(st._ev_tail)              # the previous step's D step, D's Adam and packs (side stream)
+        # ONE netD forward for the step's four calls (forward_shared): groups (fake, real)
+        if d_early is not None:
+            self.PD, self.leaseD = d_early[0], d_early[1]
+            main.wait_event(d_early[2])               # the real half (side stream)
+            out = netD._pair_finish(self.PD, self.fake)
+        else:
+            out, self.leaseD = netD._run_forward(torch.cat([self.fake, var_ref]), need_bwd=True,
+                                                 groups=2 if netD._has_bn else 1, dual=n)
+            self.PD = self.leaseD.plan
+        if self.side is not None:
+            out.record_stream(self.side)              # (the D step reads it there)
+        self.pg, self.pr = out[:n], out[n:]
+        # G step: BCE(pred_d_real - mean(pred_g_fake), 0) + BCE(pred_g_fake - mean(pred_d_real), 1), gradient to the fake half
+        self.l_g_gan, _ = LS.ragan_raw(out[n:], out[:n], False, True, st.l_gan_w, grad_x=None, grad_y=self.PD.second.gy_tensor,
+                                       grad_scale=self.S, scale_dev=self.sdev, global_mean=st.data_parallel)
+
+    def feature_and_gan_forward(self, var_H, var_ref):
+        """netF(fake) with the feature loss and netD's forward with the GAN loss, next to each other or in sequence."""
+        st, main, side = self.st, self.main, self.side
+        if st.netf_side and side is not None:
+            # netF(fake) — forward, feature loss, input-gradient pass — on the side stream next to netD's forward and
+            # G-step pass on the main stream.  The HOST enqueues the main stream's netD forward first (it is the longer
+            # chain: the G backward hangs off it); the two input gradients meet in one add.
+            st._gy2 = _buffer_like(st._gy2, self.fake)
+            side.wait_stream(main)                        # fake_H
+            self.fake.record_stream(side)
+            self.netd_forward(var_ref)
+            with torch.cuda.stream(side):
+                self.netf_fake()
+                CN.run_pass_into(self.PF, gx_into=st._gy2, accumulate=False)
+                self.ev_f = torch.cuda.Event()
+                self.ev_f.record(side)
+        else:
+            if side is not None:
+                main.wait_stream(side)
+            else:
+                self.real_fea = st.netF._run_forward(var_H, need_bwd=False)[0]
+            self.netf_fake()
+            self.netd_forward(var_ref)
+        self.mark('pixel loss, netD(fake) forward, GAN loss')
+        if self.sync_log and side is not None:
+            self.ev_glog = torch.cuda.Event()         # the G step's three losses are enqueued (main; l_g_fea maybe on side)
+            self.ev_glog.record(main)
+
+    def d_step(self):
+        # D step (SRRaGAN_model.py:143-168): the second pair of calls sees the first pair's values
+        st, PD, n = self.st, self.PD, self.n
+        if self.d_early is not None and PD.restat1.ops:
+            PD.restat1.run(E.current_stream())            # the running-statistics update the early half still owes
+        if PD.restat is not None and PD.restat.ops:
+            PD.restat.run(E.current_stream())
+        gyt = PD.gy_tensor                                # plan order [fake; real]
+        _, self.aux = LS.ragan_raw(self.pr, self.pg, True, False, 1.0, grad_x=gyt[n:], grad_y=gyt[:n],
+                                   grad_scale=self.S, scale_dev=self.sdev, global_mean=st.data_parallel)
+        CN.run_pass_into(PD)
+        CN.bind_param_grads(PD, st.netD)
+        st.exD.start()
+
+    def place_d_step(self, pos):
+        """Enqueues the D step on the side stream if `pos` ('first', 'mid', 'last': where the driver stands) is where
+        this call wants it; without a side stream, once on the main stream behind the G backward ('last').  The side
+        stream's wait for the D step's inputs is the driver's, in front of the 'first' position."""
+        # When the host enqueues the D step (~60 launches, ~0.5-1 ms of host time during which the main stream gets
+        # nothing new).  Round 4, same box, ms per step with netF(fake) on the main / side stream: 'first' (before
+        # the main stream's backward passes) 8.03 / 7.92, 'mid' 8.05 / 7.92, 'last' (behind the G backward's launch:
+        # it then runs under the backward chain) 8.35 / 7.57.
+        # Where the HOST enqueues it matters as much: the D step is ~60 launches (~1 ms of host time) during which the
+        # main stream gets nothing new.  'mid': the main stream's netD / netF input-gradient passes (two C calls,
+        # ~0.9 ms of GPU work) go out first and run while the host enqueues the D step; the G backward follows.
+        side = self.side
+        if side is None:
+            if pos == 'last':
+                self.d_step()
+            return
+        if pos == self.d_when:
+            with torch.cuda.stream(side):
+                self.d_step()
+
+    def input_gradients(self):
+        # dL/d fake_H: + d l_gan (netD, first pair) + d l_fea (netF), added by the passes' last layout ops
+        gy = self.st._gy
+        CN.run_pass_into(self.PD.second, gx_into=gy, accumulate=True)
+        self.mark('netD input-gradient pass (G step)')
+        if self.ev_f is not None:
+            self.main.wait_event(self.ev_f)
+            gy.add_(self.st._gy2)
+            self.mark('wait for netF(fake) pass, add')
+        else:
+            CN.run_pass_into(self.PF, gx_into=gy, accumulate=True)
+
+    def generator_backward(self):
+        st = self.st
+        if self.ev_prep is not None:
+            self.main.wait_event(self.ev_prep)
+        Fn.rrdbnet_train_backward(st.netG, self.stG, st._gy, follow_wgs=st.follow_wgs_sync if self.sync_log else None)
+        self.mark('G backward (tail, chain, weight gradients, unpermute)')
+        st.exG.start()
+
+    def gather_log(self):
+        # sync_log (the reference reads seven .item()s per step, SRRaGAN_model.py:171-186): round 5 — the host no longer
+        # waits for the END of the step.  The seven scalars are gathered and copied to pinned memory on the side stream
+        # right behind the D step's loss kernel (ev_log); the tail is enqueued first, THEN the host waits for
+        # ev_log only (`read_log`): it returns ~1.3 ms of GPU work early and enqueues the next step under the rest of
+        # this one (8.1 -> ~7 ms per step for a loop that logs every step).
+        if self.ev_glog is None:
+            return
+        st, side = self.st, self.side
+        with torch.cuda.stream(side):
+            side.wait_event(self.ev_glog)
+            if st._log_host is None:
+                st._log_host = torch.empty(len(LOG_KEYS), dtype=torch.float32).pin_memory()
+            self.log_keep = torch.stack([t.detach().reshape(()).float() for t in
+                                         _log_values(self.l_g_pix, self.l_g_fea, self.l_g_gan, self.aux)])
+            st._log_host.copy_(self.log_keep, non_blocking=True)
+            self.ev_log = torch.cuda.Event()
+            self.ev_log.record(side)
+
+    def tail(self):
+        # The step's tail.  With a side stream and a static loss scale the main stream only carries what the NEXT
+        # generator forward waits for — G's Adam and the pack of its forward weights; the D step's end, D's Adam, D's
+        # packs and G's input-gradient packs stay on the side stream, and the main stream meets them again (_ev_tail)
+        # in front of the next netD forward.  Else (dynamic loss scaler, or no side stream): ordered on the main stream.
+        # Only in the pipelined form of the call (sync_log=False: the caller reads nothing before `finish()` / a device
+        # synchronisation); the default call returns with everything ordered on the current stream (`read_log`).
+        st, main, side = self.st, self.main, self.side
+        if side is None or st.scaler is not None:
+            if side is not None:
+                main.wait_stream(side)
+            st._tail_on_main(main, side)
+            if side is not None:
+                st._ev_tail = torch.cuda.Event()
+                st._ev_tail.record(side)
+                st._defer_networks(st._ev_tail)
+            return
+        inv = 1.0 / st.loss_scale
+        st.exG.wait()
+        st.optimizer_G.step(grad_scale=inv, scaler=None)
+        st.netG.prepack(fwd=True, dgrad=False)
+        self.mark('Adam(G), forward weight pack')
+        side.wait_stream(main)                        # G's new weights (its input-gradient packs read them)
+        with torch.cuda.stream(side):
+            st.exD.wait()
+            st.optimizer_D.step(grad_scale=inv, scaler=None)
+            st.netD.prepack()
+            st.netG.prepack(fwd=False, dgrad=True)
+            st._ev_tail = torch.cuda.Event()
+            st._ev_tail.record(side)
+        st._defer_networks(st._ev_tail)
+
+    def read_log(self):
+        st = self.st
+        if not self.sync_log:
+            st.log = dict(zip(LOG_KEYS, _log_values(self.l_g_pix, self.l_g_fea, self.l_g_gan, self.aux)))
+        elif self.ev_log is not None:
+            self.ev_log.synchronize()                         # the losses, not the end of the step
+            st.log = dict(zip(LOG_KEYS, st._log_host.tolist()))
+            self.log_keep = None
+            # the default call's contract: everything it enqueued is ordered on the CURRENT stream when it returns
+            self.main.wait_event(st._ev_tail)
+        else:                                                 # (no side stream: everything is on the current stream)
+            st.log = {k: float(v) for k, v in
+                      zip(LOG_KEYS, _log_values(self.l_g_pix, self.l_g_fea, self.l_g_gan, self.aux))}
+        return st.log
