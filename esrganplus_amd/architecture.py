@@ -10,7 +10,7 @@ import math
 import torch.nn as nn
 
 from . import block as B
-from .functional import run_rrdbnet, run_rrdbnet_x8
+from .functional import run_rrdbnet, run_rrdbnet_tiled, run_rrdbnet_x8
 
 
 class _RRDBNetBase(B._PlannedModule):
@@ -97,6 +97,14 @@ class _RRDBNetBase(B._PlannedModule):
         ``functional.run_rrdbnet_x8``."""
         self._join_pending()
         return run_rrdbnet_x8(self, x, slots_per_pass)
+
+    def forward_tiled(self, x, tile=96, pad=16, tiles_per_pass=None):
+        """Tiled eval forward: windows of tile + 2 pad LR pixels inside the image, ``tiles_per_pass`` of them per image as
+        one batch, every tile's owned rectangle copied into the result -> [B, out_nc, 4H, 4W] float32 without gradient.
+        One launch plan serves every image size; exact for pad >= 15 nb + 4, an approximation below.  Always the eval
+        forward; ``self.training`` and ``requires_grad`` are left as they are.  See ``functional.run_rrdbnet_tiled``."""
+        self._join_pending()
+        return run_rrdbnet_tiled(self, x, tile, pad, tiles_per_pass)
 
 
 class RRDBNet(_RRDBNetBase):

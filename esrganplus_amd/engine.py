@@ -135,6 +135,8 @@ def set_nchw(op, ptr):
         op.u.conv.nchw_out = ptr
     elif op.kind == L.OP_DIHEDRAL:
         op.u.dihedral.nchw = ptr
+    elif op.kind == L.OP_TILE:
+        op.u.tile.nchw = ptr
     else:
         op.u.layout.nchw = ptr
 
@@ -258,10 +260,28 @@ def dihedral_op(ops, dt_e, B, C_, H, W, to_g32, k_count, g=None, slots=None):
     return ops.add(L.OP_DIHEDRAL, 'dihedral', d)
 
 
+def tile_op(ops, dt_e, B, C_, to_g32, t_count, g=None, slots=None):
+    """Tiled-inference end (esr_tile) appended to `ops`: the gather of t_count windows of each of B NCHW images into
+    buffer g (its H x W is the window shape), or the stitch of t_count x B window outputs — the fp32 NCHW tensor `slots`
+    — into B NCHW images.  Everything image-sized (H, W, tile, pad, the pass's first tile) is set per run
+    (TiledPlan.run): the op is recorded for the smallest image that has this window."""
+    d = L.esr_tile()
+    d.dtype, d.to_g32, d.scale = dt_e, to_g32, 1 if to_g32 else 4
+    d.B, d.C = B, C_
+    if to_g32:
+        d.g32 = g.view(0, C_)
+        d.H, d.W = g.H, g.W
+    else:
+        d.slots_nchw = slots.data_ptr()
+        d.H, d.W = slots.shape[2], slots.shape[3]
+    d.tile, d.pad, d.t_begin, d.t_count = max(d.H, d.W) // d.scale, 0, 0, t_count
+    return ops.add(L.OP_TILE, 'tile', d)
+
+
 class Builder:
     """Emits the fused-conv sequence of RDB / RRDB / RRDBNet into a Plan."""
 
-    def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1, x8=None):
+    def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1, x8=None, tiled=None):
         self.wp = wp
         self.B, self.H, self.W = B, H, W
         self.dt_e, self.tdtype, self.cpg = _dt(dtype)
@@ -276,6 +296,7 @@ class Builder:
         self.bufs = self.plan.bufs    # everything the ops point at stays alive with the plan
         self.zbufs = []
         self.x8 = x8                  # (images, H, W of the NCHW input): the batch is slots x images of a self-ensemble
+        self.tiled = tiled            # images: the batch is windows x images of a tiled forward, H x W the window
 
     def buf(self, C_, H=None, W=None):
         return new_buf(self.bufs, self.B, C_, H or self.H, W or self.W, self.dtype, self.device)
@@ -478,7 +499,15 @@ class Builder:
         c = _conv(d, B, 4 * H, 4 * W, u3.view(0), 64, None, e['model.10'])
         c.nchw_out_c = out_nc
         P.out_shape = (B, out_nc, 4 * H, 4 * W)
-        if self.x8 is None:
+        if self.tiled is not None:
+            # tiled forward: HR_conv1 leaves the windows' fp32 NCHW outputs in a buffer of the plan, slot-major, and the
+            # stitch copies every tile's owned rectangle into the caller's tensor
+            slots = torch.empty(P.out_shape, dtype=torch.float32, device=self.device)
+            self.bufs.append(slots)
+            c.nchw_out = slots.data_ptr()
+            P.ops.add_conv(c)
+            P.out_op = tile_op(P.ops, d, self.tiled, out_nc, 0, B // self.tiled, slots=slots)
+        elif self.x8 is None:
             P.out_op = P.ops.add_conv(c)
         else:
             # self-ensemble: HR_conv1 leaves its fp32 NCHW result (unrounded in either precision, as the ordinary plan's)
@@ -500,7 +529,9 @@ class Builder:
         self.alloc_z(explicit_z)
         xin = self.buf(in_nc)
         fea = self.buf(64)
-        if self.x8 is None:
+        if self.tiled is not None:
+            P.in_op = tile_op(P.ops, self.dt_e, self.tiled, in_nc, 1, B // self.tiled, g=xin)
+        elif self.x8 is None:
             P.in_op = self.import_nchw(xin, in_nc)
         else:
             n, xh, xw = self.x8
@@ -766,6 +797,48 @@ def build_rrdbnet_x8_plan(wp, nb, in_nc, out_nc, B, H, W, dtype, device, variant
         b = Builder(wp, slots * B, sh, sw, dtype, device, False, variant, 'net', nb, x8=(B, H, W))
         plans.append(b.rrdbnet(in_nc, out_nc, False))
     return X8Plan(plans, slots, (B, out_nc, 4 * H, 4 * W))
+
+
+def tiled_geometry(H, W, tile, pad):
+    """Tiling of an H x W image (LR pixels; include/esrgan_hip.h: esr_tile) -> (th, tw, ny, nx, tiles): the window
+    shape, the tile grid and, row-major, per tile (y0, y1, x0, x1, wy, wx): the owned rows [y0, y1) and columns
+    [x0, x1) and the top-left corner of its th x tw window."""
+    th, tw = min(tile + 2 * pad, H), min(tile + 2 * pad, W)
+    ny, nx = -(-H // tile), -(-W // tile)
+    tiles = []
+    for i in range(ny):
+        for j in range(nx):
+            tiles.append((i * tile, min((i + 1) * tile, H), j * tile, min((j + 1) * tile, W),
+                          min(max(i * tile - pad, 0), H - th), min(max(j * tile - pad, 0), W - tw)))
+    return th, tw, ny, nx, tiles
+
+
+class TiledPlan:
+    """The tiled forward of every image whose windows are th x tw, in passes of P windows per image: one inference plan
+    of batch P x B at th x tw between a gather and a stitch (esr_tile).  Nothing in it depends on the image size."""
+
+    def __init__(self, plan, P):
+        self.plan, self.P = plan, P
+
+    def run(self, x, out, tile, pad, stream):
+        H, W = x.shape[2], x.shape[3]
+        ny, nx = -(-H // tile), -(-W // tile)
+        plan = self.plan
+        arr = plan.ops.array()
+        g, s = arr[plan.in_op].u.tile, arr[plan.out_op].u.tile
+        g.H, g.W, s.H, s.W = H, W, 4 * H, 4 * W
+        g.tile = s.tile = tile
+        g.pad = s.pad = pad
+        for t0 in range(0, ny * nx, self.P):
+            g.t_begin = s.t_begin = t0           # a tail pass: the gather repeats the last tile, the stitch skips it
+            plan.run(x, out, stream)
+
+
+def build_rrdbnet_tiled_plan(wp, nb, in_nc, out_nc, B, th, tw, dtype, device, variant, P):
+    """Tiled form of build_rrdbnet_plan (eval mode): the gather in place of the NCHW import, the stitch behind HR_conv1,
+    and between them the ops of the ordinary plan of batch P x B at the window shape th x tw."""
+    b = Builder(wp, P * B, th, tw, dtype, device, False, variant, 'net', nb, tiled=B)
+    return TiledPlan(b.rrdbnet(in_nc, out_nc, False), P)
 
 
 # =================================================================================================

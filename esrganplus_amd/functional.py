@@ -543,3 +543,90 @@ def run_rrdbnet_x8(net, x, slots_per_pass=None):
     plan.run(xin, out, E.current_stream())
     order.leave(cur)
     return out
+
+
+tiled_geometry = E.tiled_geometry
+
+
+def _tiled_args(B, H, W, tile, pad, tiles_per_pass):
+    """Validated (tile, pad, P) of a tiled forward: P windows per image and pass.  Values beyond the image are cut down to
+    it, which changes no tile and no window."""
+    import operator
+    vals = []
+    for name, v, lo in (('tile', tile, 1), ('pad', pad, 0), ('tiles_per_pass', max(1, 16 // B) if tiles_per_pass is None else tiles_per_pass, 1)):
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            v = operator.index(v)
+        except TypeError:
+            raise ValueError('%s of a tiled forward must be an int >= %d, got %r' % (name, lo, v))
+        if v < lo:
+            raise ValueError('%s of a tiled forward must be an int >= %d, got %r' % (name, lo, v))
+        vals.append(v)
+    tile, pad, P = min(vals[0], max(H, W)), min(vals[1], max(H, W)), vals[2]
+    P = min(P, -(-H // tile) * -(-W // tile))
+    if P * B > 65535:
+        raise ValueError('tiles_per_pass x batch = %d x %d windows are more than one launch takes (65535)' % (P, B))
+    return tile, pad, P
+
+
+def tiled_reference(fn, x, tile, pad, tiles_per_pass=None):
+    """Pure-torch restatement of the tiled forward over a x4 forward ``fn``: the geometry of include/esrgan_hip.h
+    (esr_tile), the same passes of P = min(tiles_per_pass, tiles) windows per image, slot-major (window s of image b is
+    batch entry s B + b), a tail pass filled up by repeating the last window — so ``fn`` always sees a batch of P B
+    windows of one shape, and results are only bit-comparable between equal batch shapes — and every tile's owned
+    rectangle copied out of its window's output.  Nothing is blended: the owned rectangles are disjoint."""
+    B, _, H, W = x.shape
+    tile, pad, P = _tiled_args(B, H, W, tile, pad, tiles_per_pass)
+    th, tw, ny, nx, tiles = tiled_geometry(H, W, tile, pad)
+    out = None
+    for t0 in range(0, ny * nx, P):
+        idx = [min(t0 + s, ny * nx - 1) for s in range(P)]
+        ys = fn(torch.cat([x[:, :, tiles[t][4]:tiles[t][4] + th, tiles[t][5]:tiles[t][5] + tw] for t in idx], 0).contiguous()).float()
+        if out is None:
+            out = ys.new_empty((B, ys.shape[1], 4 * H, 4 * W))
+        for s, t in enumerate(idx):
+            if t0 + s >= ny * nx:
+                break
+            y0, y1, x0, x1, wy, wx = tiles[t]
+            out[:, :, 4 * y0:4 * y1, 4 * x0:4 * x1] = ys[s * B:(s + 1) * B, :, 4 * (y0 - wy):4 * (y1 - wy), 4 * (x0 - wx):4 * (x1 - wx)]
+    return out
+
+
+def run_rrdbnet_tiled(net, x, tile=96, pad=16, tiles_per_pass=None):
+    """Tiled eval forward of RRDBNet: the image is cut into windows of min(tile + 2 pad, H) x min(tile + 2 pad, W) LR
+    pixels that lie inside it (shifted inward at the borders, never zero-filled), P = min(tiles_per_pass, tiles) windows
+    per image run as one batch of the ordinary inference plan, and every tile's owned tile x tile rectangle is copied
+    from its window's output into the result (include/esrgan_hip.h: esr_tile; nothing is blended).  Images of any size
+    that share a window shape share one launch plan and its buffers, and the activation memory is that of P B windows
+    whatever the image.  With pad >= 15 nb + 4 the result is mathematically the whole-image forward; smaller pads, the
+    default among them for nb = 23, approximate it (profiles/tiled_inference.md).  Noise is off whatever
+    ``net.training`` is; the module's mode and every ``requires_grad`` are left untouched; the result
+    [B, out_nc, 4H, 4W] fp32 carries no gradient.  The defaults — 128 x 128 windows, max(1, 16 // B) of them per pass
+    — are the 16 x 128 x 128 batch that bench.py measures; that choice has not been measured against other pass sizes.
+    A pass costs what that batch costs, so an image the whole-image forward can take is faster through ``net(x)``
+    (339 x 510: 2 passes, 17.3 against 8.5 ms in fp16): tiling bounds memory and shares the plan, it is not a speed-up."""
+    if x.dim() == 4 and x.shape[0] == 0:
+        E.require_cuda(x, 'input')
+        return x.new_zeros((0, net.out_nc, 4 * x.shape[2], 4 * x.shape[3]), dtype=torch.float32)
+    xin = _prep_input(x, 'input')
+    B, C_, H, W = xin.shape
+    if C_ != net.in_nc:
+        raise ValueError('expected %d input channels, got %d' % (net.in_nc, C_))
+    tile, pad, P = _tiled_args(B, H, W, tile, pad, tiles_per_pass)
+    th, tw = min(tile + 2 * pad, H), min(tile + 2 * pad, W)
+    order = E.StreamOrder.of(net)
+    cur = order.enter()
+    wp = net._weights(xin.device)
+    key = ('tiled', P, B, th, tw, net.precision, wp.generation)      # no H, W: every image with this window shares it
+    plan = net._plans.get(key)
+    if plan is None:
+        if len(net._plans) >= net.max_cached_plans:
+            net._plans.clear()
+        plan = E.build_rrdbnet_tiled_plan(wp, net.nb, net.in_nc, net.out_nc, B, th, tw, net.precision, xin.device,
+                                          net.variant, P)
+        net._plans[key] = plan
+    out = torch.empty((B, net.out_nc, 4 * H, 4 * W), dtype=torch.float32, device=xin.device)
+    plan.run(xin, out, tile, pad, E.current_stream())
+    order.leave(cur)
+    return out

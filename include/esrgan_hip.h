@@ -220,6 +220,40 @@ typedef struct esr_dihedral {
   const float* slots_nchw;
 } esr_dihedral;
 
+/* Tiled inference ends: the gather cuts fixed-size windows out of an NCHW image into G32 slots, the stitch copies every
+ * tile's owned rectangle out of the windows' fp32 NCHW outputs into the caller's image.  Geometry, in LR pixels (Hl x Wl
+ * = the LR image: H x W of the gather, H / scale x W / scale of the stitch), parameters tile >= 1 and pad >= 0:
+ *   window shape  th = min(tile + 2 pad, Hl),  tw = min(tile + 2 pad, Wl)      (one shape for every tile of the image)
+ *   tile grid     ny = ceil(Hl / tile) by nx = ceil(Wl / tile), row-major, t = i nx + j
+ *   tile (i, j)   owns rows [i tile, min((i + 1) tile, Hl)); its window starts at wy = clamp(i tile - pad, 0, Hl - th);
+ *                 columns alike (wx from j, Wl, tw)
+ * A window always lies inside the image — at the borders it is shifted inward, never zero-filled — so a window edge
+ * either is an image edge (the convs' own zero padding is then the whole-image arithmetic) or lies at least `pad` pixels
+ * from every owned pixel.  On the HR side every offset is multiplied by `scale`: the owned pixels of tile (i, j) are
+ * copied from offset scale (i tile - wy), scale (j tile - wx) of its window's output.  With pad >= 15 nb + 4 (15 per
+ * RRDB, 1 each for fea_conv and LR_conv, 1.25 for the four HR-side convs) the tiled RRDBNet forward is mathematically
+ * the whole-image forward; smaller pads approximate it.  The kernels derive all of this from tile, pad and the tile
+ * index; there is no table.
+ * Slot s (0 <= s < t_count) of image b is batch index s * B + b.  C <= 8, else ESR_ERR_UNSUPPORTED.
+ *   to_g32 = 1, scale = 1  gather: slot s holds the th x tw window of tile min(t_begin + s, ny nx - 1) of nchw
+ *               [B][C][H][W], converted to dtype, as finished 32-byte channel groups at the logical pixels of the G32
+ *               view (channels >= C zero, the halo is never touched).  A tail pass repeats the last tile, so that no slot
+ *               holds stale data.
+ *   to_g32 = 0, scale = 4  stitch: slots_nchw is fp32 [t_count * B][C][4 th][4 tw] (what a conv's nchw_out leaves); the
+ *               owned rectangle of every tile t_begin + s < ny nx is copied, bit for bit, into nchw [B][C][H][W] (H, W
+ *               multiples of 4; both pointers 16-byte aligned).  Slots beyond the last tile are not read; g32 and dtype's
+ *               storage type are unused.                                                                              */
+typedef struct esr_tile {
+  int32_t dtype, to_g32;
+  int32_t B, C, H, W;      /* the full image on this op's side: LR for the gather, HR for the stitch */
+  int32_t tile, pad;       /* LR pixels */
+  int32_t scale;           /* 1: gather, 4: stitch */
+  int32_t t_begin, t_count;
+  float* nchw;
+  esr_g32 g32;
+  const float* slots_nchw;
+} esr_tile;
+
 /* Philox-4x32-7 + Box-Muller N(0,1) fill (csrc/common.h), NCHW fp32 — the exact z the fused noise epilogue uses for
  * (seed, layer); lets tests feed the same z to the oracle (GaussianNoise, block.py:117-122). */
 typedef struct esr_noise_fill {
@@ -576,7 +610,8 @@ enum esr_op_kind { ESR_OP_CONV = 1, ESR_OP_PACK = 2, ESR_OP_LAYOUT = 3, ESR_OP_N
                    ESR_OP_WGRAD = 5, ESR_OP_BN = 6, ESR_OP_POOL = 7, ESR_OP_LINEAR = 8,
                    ESR_OP_UNPERMUTE = 9, ESR_OP_PACK_BATCH = 10,
                    ESR_OP_RDB_CHAIN = 11, ESR_OP_FRAG_GATHER = 12, ESR_OP_RDB_WGRAD = 13,
-                   ESR_OP_RDB_CHAIN_BWD = 14 /* u.rdb_chain with mode 2 */, ESR_OP_DIHEDRAL = 15 };
+                   ESR_OP_RDB_CHAIN_BWD = 14 /* u.rdb_chain with mode 2 */, ESR_OP_DIHEDRAL = 15,
+                   ESR_OP_TILE = 16 };
 
 /* esr_op.flags */
 #define ESR_OPF_SIDE 1   /* on a run of consecutive ESR_OP_WGRAD ops: launch the run on the library's side
@@ -619,6 +654,7 @@ typedef struct esr_op {
     esr_frag_gather frag_gather;
     esr_rdb_wgrad rdb_wgrad;
     esr_dihedral dihedral;
+    esr_tile tile;
   } u;
 } esr_op;
 
@@ -631,6 +667,7 @@ int esr_pack_conv_weights(const esr_pack* p, esr_stream_t stream);
 int esr_convert_layout(const esr_layout* p, esr_stream_t stream);
 int esr_fill_noise(const esr_noise_fill* p, esr_stream_t stream);
 int esr_dihedral_op(const esr_dihedral* p, esr_stream_t stream);   /* added under ABI 6: a pure addition */
+int esr_tile_op(const esr_tile* p, esr_stream_t stream);           /* added under ABI 6: a pure addition */
 int esr_conv_wgrad(const esr_wgrad* p, esr_stream_t stream);
 /* n independent weight-gradient problems (disjoint dw/dbias blocks).  fp16 3x3/s1 and 1x1 entries are
  * packed, up to 8 at a time, into ONE launch (at training sizes a single conv's wgrad is ~64
@@ -728,7 +765,7 @@ int esr_graph_destroy(esr_graph_t g);
 int esr_run_ops_timed(const esr_op* ops, int32_t n, esr_stream_t stream, float* ms_out);
 
 const char* esr_last_error(void);
-int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
+int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL and esr_tile / esr_tile_op / ESR_OP_TILE were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
                                 esr_l1_loss, esr_ragan_loss, ESR_OPF_SIDE_FREE) */
 size_t esr_sizeof_op(void);
 
