@@ -22,6 +22,7 @@ OP_CONV, OP_PACK, OP_LAYOUT, OP_NOISE_FILL, OP_WGRAD, OP_BN, OP_POOL, OP_LINEAR,
 OP_RDB_CHAIN, OP_FRAG_GATHER, OP_RDB_WGRAD, OP_RDB_CHAIN_BWD = 11, 12, 13, 14
 OP_DIHEDRAL = 15
 OP_TILE = 16
+OP_TILE_X8 = 17
 BN_STATS, BN_FINALIZE, BN_APPLY, BN_BWD_REDUCE, BN_BWD_FINAL, BN_BWD_APPLY, BN_RESTAT, BN_FIN_APPLY = 0, 1, 2, 3, 4, 5, 6, 7
 NO_LAYER = 0xFFFFFFFF
 POOL_FWD, POOL_BWD, POOL_SHUFFLE, POOL_UNSHUFFLE = 0, 1, 2, 3      # esr_pool.mode
@@ -90,6 +91,11 @@ class esr_tile(C.Structure):
                 ('H', C.c_int32), ('W', C.c_int32), ('tile', C.c_int32), ('pad', C.c_int32), ('scale', C.c_int32),
                 ('t_begin', C.c_int32), ('t_count', C.c_int32), ('nchw', C.c_void_p), ('g32', esr_g32),
                 ('slots_nchw', C.c_void_p)]
+
+
+class esr_tile_x8(C.Structure):
+    _fields_ = esr_tile._fields_ + [('k_begin', C.c_int32), ('k_count', C.c_int32), ('accumulate', C.c_int32),
+                                    ('mean_scale', C.c_float)]
 
 
 class esr_noise_fill(C.Structure):
@@ -234,7 +240,8 @@ class _op_union(C.Union):
                 ('noise_fill', esr_noise_fill), ('wgrad', esr_wgrad), ('bn', esr_bn),
                 ('pool', esr_pool), ('linear', esr_linear), ('unpermute', esr_unpermute),
                 ('pack_batch', esr_pack_batch), ('rdb_chain', esr_rdb_chain), ('frag_gather', esr_frag_gather),
-                ('rdb_wgrad', esr_rdb_wgrad), ('dihedral', esr_dihedral), ('tile', esr_tile)]
+                ('rdb_wgrad', esr_rdb_wgrad), ('dihedral', esr_dihedral), ('tile', esr_tile),
+                ('tile_x8', esr_tile_x8)]
 
 
 class esr_op(C.Structure):
@@ -250,7 +257,8 @@ EXPORTS = ['esr_packed_weight_bytes', 'esr_g32_dims', 'esr_conv_forward', 'esr_p
            'esr_rdb_max_tiles_per_image', 'esr_gather_fragments', 'esr_image_metrics', 'esr_wgrad_workspace_elems',
            'esr_l1_loss_forward', 'esr_ragan_loss_forward', 'esr_rdb_wgrad_run', 'esr_rdb_wgrad_workspace_elems', 'esr_rdb_backward',
            'esr_rdb_mask_bytes', 'esr_rdb_check_abort', 'esr_debug_hold_cus', 'esr_debug_device_alias', 'esr_debug_chain_order_waits',
-           'esr_debug_mfma_probe', 'esr_debug_rdb_wgrad_follow', 'esr_dihedral_op', 'esr_tile_op']
+           'esr_debug_mfma_probe', 'esr_debug_rdb_wgrad_follow', 'esr_dihedral_op', 'esr_tile_op',
+           'esr_tile_x8_op']
 
 _lib = None
 _lock = threading.Lock()
@@ -311,7 +319,8 @@ def lib():
                          ('esr_gather_fragments', esr_frag_gather), ('esr_image_metrics', esr_img_metrics),
                          ('esr_l1_loss_forward', esr_l1_loss), ('esr_ragan_loss_forward', esr_ragan_loss),
                          ('esr_rdb_wgrad_run', esr_rdb_wgrad), ('esr_rdb_backward', esr_rdb_chain),
-                         ('esr_dihedral_op', esr_dihedral), ('esr_tile_op', esr_tile)):
+                         ('esr_dihedral_op', esr_dihedral), ('esr_tile_op', esr_tile),
+                         ('esr_tile_x8_op', esr_tile_x8)):
             getattr(L, name).argtypes = [C.POINTER(st), C.c_void_p]
         if L.esr_sizeof_op() != C.sizeof(esr_op):
             raise HipExtensionError('ABI mismatch: sizeof(esr_op) C=%d ctypes=%d'

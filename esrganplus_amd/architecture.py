@@ -10,7 +10,7 @@ import math
 import torch.nn as nn
 
 from . import block as B
-from .functional import run_rrdbnet, run_rrdbnet_tiled, run_rrdbnet_x8
+from .functional import run_rrdbnet, run_rrdbnet_tiled, run_rrdbnet_tiled_x8, run_rrdbnet_x8
 
 
 class _RRDBNetBase(B._PlannedModule):
@@ -105,6 +105,15 @@ class _RRDBNetBase(B._PlannedModule):
         forward; ``self.training`` and ``requires_grad`` are left as they are.  See ``functional.run_rrdbnet_tiled``."""
         self._join_pending()
         return run_rrdbnet_tiled(self, x, tile, pad, tiles_per_pass)
+
+    def forward_tiled_x8(self, x, tile=96, pad=16, tiles_per_pass=None, slots_per_pass=None):
+        """Tiled x8 self-ensemble: the windows of ``forward_tiled``, each transformed the eight ways of ``forward_x8``,
+        forwarded and averaged per window, every tile's owned rectangle of the mean copied into the result ->
+        [B, out_nc, 4H, 4W] float32 without gradient.  One launch plan (two for non-square windows) serves every image
+        size; mathematically ``forward_x8(x)`` for pad >= 15 nb + 4, an approximation below.  Always the eval forward;
+        ``self.training`` and ``requires_grad`` are left as they are.  See ``functional.run_rrdbnet_tiled_x8``."""
+        self._join_pending()
+        return run_rrdbnet_tiled_x8(self, x, tile, pad, tiles_per_pass, slots_per_pass)
 
 
 class RRDBNet(_RRDBNetBase):

@@ -137,6 +137,8 @@ def set_nchw(op, ptr):
         op.u.dihedral.nchw = ptr
     elif op.kind == L.OP_TILE:
         op.u.tile.nchw = ptr
+    elif op.kind == L.OP_TILE_X8:
+        op.u.tile_x8.nchw = ptr
     else:
         op.u.layout.nchw = ptr
 
@@ -278,10 +280,28 @@ def tile_op(ops, dt_e, B, C_, to_g32, t_count, g=None, slots=None):
     return ops.add(L.OP_TILE, 'tile', d)
 
 
+def tile_x8_op(ops, dt_e, B, C_, th, tw, to_g32, t_count, k_begin, k_count, g=None, slots=None):
+    """Tiled self-ensemble end (esr_tile_x8) appended to `ops`: the gather-import of k_count transformed copies of t_count
+    th x tw windows of each of B NCHW images into buffer g, or the stitch-reduce of k_count x t_count x B window outputs
+    — the fp32 NCHW tensor `slots` — into B NCHW images.  Everything image-sized (H, W, tile, pad, the pass's first tile)
+    and the pass's k range, accumulate and mean_scale are set per run (TiledX8Plan.run): the op is recorded for the
+    smallest image that has this window."""
+    d = L.esr_tile_x8()
+    d.dtype, d.to_g32, d.scale = dt_e, to_g32, 1 if to_g32 else 4
+    d.B, d.C, d.H, d.W = B, C_, th * d.scale, tw * d.scale
+    if to_g32:
+        d.g32 = g.view(0, C_)
+    else:
+        d.slots_nchw = slots.data_ptr()
+    d.tile, d.pad, d.t_begin, d.t_count = max(th, tw), 0, 0, t_count
+    d.k_begin, d.k_count, d.accumulate, d.mean_scale = k_begin, k_count, 0, 1.0
+    return ops.add(L.OP_TILE_X8, 'tile_x8', d)
+
+
 class Builder:
     """Emits the fused-conv sequence of RDB / RRDB / RRDBNet into a Plan."""
 
-    def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1, x8=None, tiled=None):
+    def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1, x8=None, tiled=None, tiled_x8=None):
         self.wp = wp
         self.B, self.H, self.W = B, H, W
         self.dt_e, self.tdtype, self.cpg = _dt(dtype)
@@ -297,6 +317,9 @@ class Builder:
         self.zbufs = []
         self.x8 = x8                  # (images, H, W of the NCHW input): the batch is slots x images of a self-ensemble
         self.tiled = tiled            # images: the batch is windows x images of a tiled forward, H x W the window
+        # (images, th, tw, first k, slots): the batch is slots x windows x images of a tiled self-ensemble, th x tw the
+        # window on the NCHW side (H x W here is tw x th for the transposed slots, first k = 4)
+        self.tiled_x8 = tiled_x8
 
     def buf(self, C_, H=None, W=None):
         return new_buf(self.bufs, self.B, C_, H or self.H, W or self.W, self.dtype, self.device)
@@ -499,7 +522,16 @@ class Builder:
         c = _conv(d, B, 4 * H, 4 * W, u3.view(0), 64, None, e['model.10'])
         c.nchw_out_c = out_nc
         P.out_shape = (B, out_nc, 4 * H, 4 * W)
-        if self.tiled is not None:
+        if self.tiled_x8 is not None:
+            # tiled self-ensemble: HR_conv1 leaves the transformed windows' fp32 NCHW outputs in a buffer of the plan, and
+            # the stitch-reduce undoes the transforms, sums and copies every tile's owned rectangle into the caller's tensor
+            n, wh, ww, k0, kc = self.tiled_x8
+            slots = torch.empty(P.out_shape, dtype=torch.float32, device=self.device)
+            self.bufs.append(slots)
+            c.nchw_out = slots.data_ptr()
+            P.ops.add_conv(c)
+            P.out_op = tile_x8_op(P.ops, d, n, out_nc, wh, ww, 0, B // (kc * n), k0, kc, slots=slots)
+        elif self.tiled is not None:
             # tiled forward: HR_conv1 leaves the windows' fp32 NCHW outputs in a buffer of the plan, slot-major, and the
             # stitch copies every tile's owned rectangle into the caller's tensor
             slots = torch.empty(P.out_shape, dtype=torch.float32, device=self.device)
@@ -529,7 +561,10 @@ class Builder:
         self.alloc_z(explicit_z)
         xin = self.buf(in_nc)
         fea = self.buf(64)
-        if self.tiled is not None:
+        if self.tiled_x8 is not None:
+            n, wh, ww, k0, kc = self.tiled_x8
+            P.in_op = tile_x8_op(P.ops, self.dt_e, n, in_nc, wh, ww, 1, B // (kc * n), k0, kc, g=xin)
+        elif self.tiled is not None:
             P.in_op = tile_op(P.ops, self.dt_e, self.tiled, in_nc, 1, B // self.tiled, g=xin)
         elif self.x8 is None:
             P.in_op = self.import_nchw(xin, in_nc)
@@ -839,6 +874,46 @@ def build_rrdbnet_tiled_plan(wp, nb, in_nc, out_nc, B, th, tw, dtype, device, va
     and between them the ops of the ordinary plan of batch P x B at the window shape th x tw."""
     b = Builder(wp, P * B, th, tw, dtype, device, False, variant, 'net', nb, tiled=B)
     return TiledPlan(b.rrdbnet(in_nc, out_nc, False), P)
+
+
+class TiledX8Plan:
+    """The tiled x8 self-ensemble of every image whose windows are th x tw: per pass of P windows per image, 8 / slots
+    runs of one inference plan of batch slots x P x B (two plans for non-square windows: th x tw for k 0..3, tw x th for
+    k 4..7) between a gather-import and a stitch-reduce (esr_tile_x8), chained through `accumulate` into the caller's
+    tensor; the last run of a pass applies the 1/8.  Nothing in it depends on the image size."""
+
+    def __init__(self, plans, slots, P):
+        self.plans, self.slots, self.P = plans, slots, P
+
+    def run(self, x, out, tile, pad, stream):
+        H, W = x.shape[2], x.shape[3]
+        ny, nx = -(-H // tile), -(-W // tile)
+        for plan in self.plans:
+            arr = plan.ops.array()
+            g, s = arr[plan.in_op].u.tile_x8, arr[plan.out_op].u.tile_x8
+            g.H, g.W, s.H, s.W = H, W, 4 * H, 4 * W
+            g.tile = s.tile = tile
+            g.pad = s.pad = pad
+        for t0 in range(0, ny * nx, self.P):
+            for k0 in range(0, 8, self.slots):
+                plan = self.plans[-1 if k0 >= 4 else 0]
+                arr = plan.ops.array()
+                g, s = arr[plan.in_op].u.tile_x8, arr[plan.out_op].u.tile_x8
+                g.t_begin = s.t_begin = t0       # a tail pass: the gather repeats the last tile, the stitch skips it
+                g.k_begin = s.k_begin = k0
+                s.accumulate, s.mean_scale = int(k0 > 0), 0.125 if k0 + self.slots == 8 else 1.0
+                plan.run(x, out, stream)
+
+
+def build_rrdbnet_tiled_x8_plan(wp, nb, in_nc, out_nc, B, th, tw, dtype, device, variant, P, slots):
+    """Tiled self-ensemble form of build_rrdbnet_plan (eval mode): the gather-import in place of the NCHW import, the
+    stitch-reduce behind HR_conv1, and between them the ops of the ordinary plan of batch slots x P x B at the window
+    shape (and, for non-square windows, a second one at the transposed shape)."""
+    plans = []
+    for k0, sh, sw in ([(0, th, tw)] if th == tw else [(0, th, tw), (4, tw, th)]):
+        b = Builder(wp, slots * P * B, sh, sw, dtype, device, False, variant, 'net', nb, tiled_x8=(B, th, tw, k0, slots))
+        plans.append(b.rrdbnet(in_nc, out_nc, False))
+    return TiledX8Plan(plans, slots, P)
 
 
 # =================================================================================================

@@ -519,7 +519,8 @@ def run_rrdbnet_x8(net, x, slots_per_pass=None):
     module's mode and every ``requires_grad`` are left untouched; the result [B, out_nc, 4H, 4W] fp32 carries no
     gradient.  B > 1 is ensembled PER IMAGE (the reference's ``cat`` + ``mean(dim=0)`` would also average across the
     images and is only meaningful at B = 1).  slots_per_pass (8, 4, 2 or 1; default ESR_X8_SLOTS, else 8 for square and 4
-    for non-square input) bounds the memory of large images: each pass runs slots x B copies."""
+    for non-square input) bounds the memory of large images: each pass runs slots x B copies.  Every pass still holds
+    whole-image plans; ``run_rrdbnet_tiled_x8`` is the ensemble per window, with the memory of a tiled forward."""
     if x.dim() == 4 and x.shape[0] == 0:
         E.require_cuda(x, 'input')
         return x.new_zeros((0, net.out_nc, 4 * x.shape[2], 4 * x.shape[3]), dtype=torch.float32)
@@ -593,6 +594,89 @@ def tiled_reference(fn, x, tile, pad, tiles_per_pass=None):
     return out
 
 
+def _tiled_x8_args(B, H, W, tile, pad, tiles_per_pass, slots_per_pass):
+    """Validated (tile, pad, P, slots) of a tiled self-ensemble: _tiled_args' checks, the slots of E.x8_slots for the
+    window shape, and P defaulting to max(1, 16 // (slots B)) windows per image and pass."""
+    tile, pad, P = _tiled_args(B, H, W, tile, pad, 1 if tiles_per_pass is None else tiles_per_pass)
+    slots = E.x8_slots(min(tile + 2 * pad, H), min(tile + 2 * pad, W), slots_per_pass)
+    if tiles_per_pass is None:
+        P = min(max(1, 16 // (slots * B)), -(-H // tile) * -(-W // tile))
+    if slots * P * B > 65535:
+        raise ValueError('slots x tiles_per_pass x batch = %d x %d x %d windows are more than one launch takes (65535)'
+                         % (slots, P, B))
+    return tile, pad, P, slots
+
+
+def tiled_x8_reference(fn, x, tile, pad, tiles_per_pass=None, slots_per_pass=None):
+    """Pure-torch restatement of the tiled x8 self-ensemble over a x4 forward ``fn``: ``tiled_reference``'s windows and
+    passes (P windows per image, slot-major, a tail pass filled up by repeating the last window), every window — pad
+    included — transformed the eight ways of ``x8_transform``, in runs of ``slots`` transforms: ``fn`` sees batches of
+    slots P B windows, entry ((k - k0) P + p) B + b, th x tw for k < 4 and tw x th for k >= 4.  The outputs are
+    inverse-transformed and summed as seven fp32 adds in k order, times 0.125 (``x8_reference``'s arithmetic), and every
+    tile's owned rectangle of that mean is copied out.  Nothing is blended."""
+    B, _, H, W = x.shape
+    tile, pad, P, slots = _tiled_x8_args(B, H, W, tile, pad, tiles_per_pass, slots_per_pass)
+    th, tw, ny, nx, tiles = tiled_geometry(H, W, tile, pad)
+    out = None
+    for t0 in range(0, ny * nx, P):
+        idx = [min(t0 + s, ny * nx - 1) for s in range(P)]
+        wins = torch.cat([x[:, :, tiles[t][4]:tiles[t][4] + th, tiles[t][5]:tiles[t][5] + tw] for t in idx], 0)
+        acc = None
+        for k0 in range(0, 8, slots):
+            ys = fn(torch.cat([x8_transform(wins, k) for k in range(k0, k0 + slots)], 0)).float().split(P * B, 0)
+            for k, y in zip(range(k0, k0 + slots), ys):
+                acc = x8_inverse(y, k) if acc is None else acc + x8_inverse(y, k)
+        mean = acc * 0.125
+        if out is None:
+            out = mean.new_empty((B, mean.shape[1], 4 * H, 4 * W))
+        for s, t in enumerate(idx):
+            if t0 + s >= ny * nx:
+                break
+            y0, y1, x0, x1, wy, wx = tiles[t]
+            out[:, :, 4 * y0:4 * y1, 4 * x0:4 * x1] = mean[s * B:(s + 1) * B, :, 4 * (y0 - wy):4 * (y1 - wy), 4 * (x0 - wx):4 * (x1 - wx)]
+    return out
+
+
+def run_rrdbnet_tiled_x8(net, x, tile=96, pad=16, tiles_per_pass=None, slots_per_pass=None):
+    """Tiled x8 self-ensemble of RRDBNet: the windows of ``run_rrdbnet_tiled`` (same geometry), each — pad included —
+    transformed the eight ways of ``run_rrdbnet_x8``, forwarded, inverse-transformed, summed in k order and times 0.125;
+    the owned rectangle of that mean is copied into the result (include/esrgan_hip.h: esr_tile_x8; nothing is blended).
+    Per window, not per image: with pad >= 15 nb + 4 this is mathematically ``forward_x8(x)``, smaller pads approximate
+    it.  One pass runs slots x P x B windows as one batch of the ordinary inference plan — slots from ``slots_per_pass``
+    (8, 4, 2 or 1; default ESR_X8_SLOTS, else 8 for square windows and 4 otherwise: a pass cannot mix th x tw and tw x th
+    slots), P = min(tiles_per_pass, tiles) — and passes of fewer than 8 slots are chained into the result.  Square
+    windows need one launch plan for all eight transforms, non-square ones two; images of any size that share a window
+    shape share them, and the activation memory is that of slots P B windows whatever the image — where ``forward_x8``
+    holds 8 B (or 2 x 4 B) copies of the whole image.  Noise is off whatever ``net.training`` is; the module's mode and
+    every ``requires_grad`` are left untouched; the result [B, out_nc, 4H, 4W] fp32 carries no gradient; B > 1 is
+    ensembled per image.  The default pass — tiles_per_pass = max(1, 16 // (slots B)) windows of 128 x 128 — is the
+    16 x 128 x 128 batch that bench.py measures; other pass sizes are unmeasured (profiles/tiled_x8.md)."""
+    if x.dim() == 4 and x.shape[0] == 0:
+        E.require_cuda(x, 'input')
+        return x.new_zeros((0, net.out_nc, 4 * x.shape[2], 4 * x.shape[3]), dtype=torch.float32)
+    xin = _prep_input(x, 'input')
+    B, C_, H, W = xin.shape
+    if C_ != net.in_nc:
+        raise ValueError('expected %d input channels, got %d' % (net.in_nc, C_))
+    tile, pad, P, slots = _tiled_x8_args(B, H, W, tile, pad, tiles_per_pass, slots_per_pass)
+    th, tw = min(tile + 2 * pad, H), min(tile + 2 * pad, W)
+    order = E.StreamOrder.of(net)
+    cur = order.enter()
+    wp = net._weights(xin.device)
+    key = ('tiled_x8', slots, P, B, th, tw, net.precision, wp.generation)   # no H, W: every image with this window shares it
+    plan = net._plans.get(key)
+    if plan is None:
+        if len(net._plans) >= net.max_cached_plans:
+            net._plans.clear()
+        plan = E.build_rrdbnet_tiled_x8_plan(wp, net.nb, net.in_nc, net.out_nc, B, th, tw, net.precision, xin.device,
+                                             net.variant, P, slots)
+        net._plans[key] = plan
+    out = torch.empty((B, net.out_nc, 4 * H, 4 * W), dtype=torch.float32, device=xin.device)
+    plan.run(xin, out, tile, pad, E.current_stream())
+    order.leave(cur)
+    return out
+
+
 def run_rrdbnet_tiled(net, x, tile=96, pad=16, tiles_per_pass=None):
     """Tiled eval forward of RRDBNet: the image is cut into windows of min(tile + 2 pad, H) x min(tile + 2 pad, W) LR
     pixels that lie inside it (shifted inward at the borders, never zero-filled), P = min(tiles_per_pass, tiles) windows
@@ -605,7 +689,8 @@ def run_rrdbnet_tiled(net, x, tile=96, pad=16, tiles_per_pass=None):
     [B, out_nc, 4H, 4W] fp32 carries no gradient.  The defaults — 128 x 128 windows, max(1, 16 // B) of them per pass
     — are the 16 x 128 x 128 batch that bench.py measures; that choice has not been measured against other pass sizes.
     A pass costs what that batch costs, so an image the whole-image forward can take is faster through ``net(x)``
-    (339 x 510: 2 passes, 17.3 against 8.5 ms in fp16): tiling bounds memory and shares the plan, it is not a speed-up."""
+    (339 x 510: 2 passes, 17.3 against 8.5 ms in fp16): tiling bounds memory and shares the plan, it is not a speed-up.
+    The x8 self-ensemble over the same windows is ``run_rrdbnet_tiled_x8``."""
     if x.dim() == 4 and x.shape[0] == 0:
         E.require_cuda(x, 'input')
         return x.new_zeros((0, net.out_nc, 4 * x.shape[2], 4 * x.shape[3]), dtype=torch.float32)

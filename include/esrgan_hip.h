@@ -254,6 +254,45 @@ typedef struct esr_tile {
   const float* slots_nchw;
 } esr_tile;
 
+/* Tiled x8 self-ensemble ends: esr_tile's windows, each turned the eight ways of esr_dihedral — per WINDOW, pad included,
+ * not per image.  Geometry is esr_tile's (window shape th x tw, tile grid ny x nx, inward shift, owned rectangles, LR
+ * pixels; H x W = the full image of this op's side); transform k = 0..7 is esr_dihedral's with the window in the place of
+ * the image, v = k & 1, h = k & 2, t = k & 4:
+ *   ys(i) = h ? n-1-i : i over the window's rows,   xs(j) = v ? m-1-j : j over its columns
+ *   gather (n x m = th x tw, win = the window of the tile):
+ *     slot_k[y][x] = win[ys(y)][xs(x)]   (k < 4, a th x tw slot)      slot_k[p][q] = win[ys(q)][xs(p)]   (k >= 4, tw x th)
+ *   stitch (n x m = 4 th x 4 tw, the window's output; (y, x) window-local HR coordinates):
+ *     R_k(o)[y][x] = o_k[ys(y)][xs(x)]   (k < 4)                      R_k(o)[y][x] = o_k[xs(x)][ys(y)]   (k >= 4)
+ * Slot k of window s (0 <= s < t_count) of image b is batch index ((k - k_begin) t_count + s) B + b: the transforms
+ * outermost, then esr_tile's slot-major windows.  A range may contain both k < 4 and k >= 4 only when th == tw (else
+ * ESR_ERR_INVALID): a pass cannot mix th x tw and tw x th slots.  C <= 8 and k_count t_count B <= 65535, else
+ * ESR_ERR_UNSUPPORTED.
+ *   to_g32 = 1, scale = 1  gather-import: every pixel of the window of tile min(t_begin + s, ny nx - 1) of nchw
+ *               [B][C][H][W] is read once and written, converted to dtype, as a finished 32-byte channel group to the
+ *               logical pixel of every slot of the range in the G32 view (th x tw for k < 4, tw x th for k >= 4; channels
+ *               >= C zero, the halo is never touched).  A tail pass repeats the last tile.
+ *   to_g32 = 0, scale = 4  stitch-reduce: slots_nchw is fp32 [k_count * t_count * B][C][4 th][4 tw] (k < 4) or
+ *               [...][4 tw][4 th] (k >= 4), what a conv's nchw_out leaves.  For every HR pixel of the owned rectangle of
+ *               every tile t_begin + s < ny nx:  acc = accumulate ? nchw : 0;  acc += R_k(o_k) for k ascending (one fp32
+ *               add per k);  nchw = acc * mean_scale.  mean_scale = 0.125 on the last range gives the mean; accumulate
+ *               chains the ranges (mean_scale = 1 before the last) and the result does not depend on how the eight slots
+ *               are split.  Nothing is blended and nothing outside the owned rectangles is written; slots beyond the last
+ *               tile are neither read nor written.  H, W multiples of 4, both pointers 16-byte aligned (esr_tile's rule);
+ *               g32 and dtype's storage type are unused.                                                             */
+typedef struct esr_tile_x8 {
+  int32_t dtype, to_g32;
+  int32_t B, C, H, W;      /* the full image on this op's side: LR for the gather, HR for the stitch */
+  int32_t tile, pad;       /* LR pixels */
+  int32_t scale;           /* 1: gather, 4: stitch */
+  int32_t t_begin, t_count;
+  float* nchw;
+  esr_g32 g32;
+  const float* slots_nchw;
+  int32_t k_begin, k_count;
+  int32_t accumulate;
+  float mean_scale;
+} esr_tile_x8;
+
 /* Philox-4x32-7 + Box-Muller N(0,1) fill (csrc/common.h), NCHW fp32 — the exact z the fused noise epilogue uses for
  * (seed, layer); lets tests feed the same z to the oracle (GaussianNoise, block.py:117-122). */
 typedef struct esr_noise_fill {
@@ -611,7 +650,7 @@ enum esr_op_kind { ESR_OP_CONV = 1, ESR_OP_PACK = 2, ESR_OP_LAYOUT = 3, ESR_OP_N
                    ESR_OP_UNPERMUTE = 9, ESR_OP_PACK_BATCH = 10,
                    ESR_OP_RDB_CHAIN = 11, ESR_OP_FRAG_GATHER = 12, ESR_OP_RDB_WGRAD = 13,
                    ESR_OP_RDB_CHAIN_BWD = 14 /* u.rdb_chain with mode 2 */, ESR_OP_DIHEDRAL = 15,
-                   ESR_OP_TILE = 16 };
+                   ESR_OP_TILE = 16, ESR_OP_TILE_X8 = 17 };
 
 /* esr_op.flags */
 #define ESR_OPF_SIDE 1   /* on a run of consecutive ESR_OP_WGRAD ops: launch the run on the library's side
@@ -655,6 +694,7 @@ typedef struct esr_op {
     esr_rdb_wgrad rdb_wgrad;
     esr_dihedral dihedral;
     esr_tile tile;
+    esr_tile_x8 tile_x8;
   } u;
 } esr_op;
 
@@ -668,6 +708,7 @@ int esr_convert_layout(const esr_layout* p, esr_stream_t stream);
 int esr_fill_noise(const esr_noise_fill* p, esr_stream_t stream);
 int esr_dihedral_op(const esr_dihedral* p, esr_stream_t stream);   /* added under ABI 6: a pure addition */
 int esr_tile_op(const esr_tile* p, esr_stream_t stream);           /* added under ABI 6: a pure addition */
+int esr_tile_x8_op(const esr_tile_x8* p, esr_stream_t stream);     /* added under ABI 6: a pure addition */
 int esr_conv_wgrad(const esr_wgrad* p, esr_stream_t stream);
 /* n independent weight-gradient problems (disjoint dw/dbias blocks).  fp16 3x3/s1 and 1x1 entries are
  * packed, up to 8 at a time, into ONE launch (at training sizes a single conv's wgrad is ~64
@@ -765,7 +806,7 @@ int esr_graph_destroy(esr_graph_t g);
 int esr_run_ops_timed(const esr_op* ops, int32_t n, esr_stream_t stream, float* ms_out);
 
 const char* esr_last_error(void);
-int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL and esr_tile / esr_tile_op / ESR_OP_TILE were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
+int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE and esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8 were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
                                 esr_l1_loss, esr_ragan_loss, ESR_OPF_SIDE_FREE) */
 size_t esr_sizeof_op(void);
 

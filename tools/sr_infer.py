@@ -1,12 +1,14 @@
 #!/usr/bin/env python
 """Inference harness reproducing the reference's ``test_image/test.py`` (lines 9-40) on the HIP path
-with PIL instead of cv2:  python tools/sr_infer.py <model.pth|synthetic> <in_dir> <out_dir> [fp16|fp32] [--x8] [--tile N[,PAD]]
+with PIL instead of cv2:  python tools/sr_infer.py <model.pth|synthetic> <in_dir> <out_dir> [fp16|fp32] [--x8] [--tile N[,PAD]] [--tile-x8 N[,PAD]]
 
 Per image: RGB /255 -> NCHW float32 -> RRDB_Net(3,3,64,23,...) -> clamp(0,1) -> *255 round -> PNG.
 --x8: the geometric self-ensemble (the reference's ``SRModel.test_x8``, codes/models/SR_model.py:82-120) in place of the
 plain forward: ``model.forward_x8``.
 --tile N[,PAD] (also --tile=N[,PAD]): the tiled forward ``model.forward_tiled(x, tile=N, pad=PAD)`` (PAD defaults to the
-method's): one launch plan for a folder of images of any size, bounded memory; not combined with --x8."""
+method's): one launch plan for a folder of images of any size, bounded memory; not combined with --x8.
+--tile-x8 N[,PAD] (also --tile-x8=N[,PAD]): the tiled self-ensemble ``model.forward_tiled_x8(x, tile=N, pad=PAD)``: the
+ensemble per window, with the tiled forward's bounded memory and shared plan; not combined with --x8 or --tile."""
 import glob
 import os
 import sys
@@ -22,20 +24,24 @@ from esrganplus_amd import architecture as arch, synth
 def main():
     argv = [a for a in sys.argv[1:] if a != '--x8']
     x8 = '--x8' in sys.argv[1:]
-    tiled = None
-    for i, a in enumerate(argv):
-        if a == '--tile' or a.startswith('--tile='):
-            val = a[7:] if '=' in a else ''.join(argv[i + 1:i + 2])
-            del argv[i:i + (1 if '=' in a else 2)]
-            try:
-                tiled = [int(v) for v in val.split(',')]
-            except ValueError:
-                tiled = []
-            if len(tiled) not in (1, 2):
-                sys.exit('sr_infer.py: --tile takes N or N,PAD (LR pixels), got %r' % val)
-            break
+    tiles = {'--tile': None, '--tile-x8': None}
+    for flag in tiles:
+        for i, a in enumerate(argv):
+            if a == flag or a.startswith(flag + '='):
+                val = a[len(flag) + 1:] if '=' in a else ''.join(argv[i + 1:i + 2])
+                del argv[i:i + (1 if '=' in a else 2)]
+                try:
+                    tiles[flag] = [int(v) for v in val.split(',')]
+                except ValueError:
+                    tiles[flag] = []
+                if len(tiles[flag]) not in (1, 2):
+                    sys.exit('sr_infer.py: %s takes N or N,PAD (LR pixels), got %r' % (flag, val))
+                break
+    tiled, tiled_x8 = tiles['--tile'], tiles['--tile-x8']
     if tiled and x8:
-        sys.exit('sr_infer.py: --tile and --x8 cannot be combined: the tiled self-ensemble is not implemented')
+        sys.exit('sr_infer.py: --tile and --x8 cannot be combined: the tiled self-ensemble is --tile-x8 N[,PAD]')
+    if tiled_x8 and (x8 or tiled):
+        sys.exit('sr_infer.py: --tile-x8 is the tiled self-ensemble by itself: it cannot be combined with --x8 or --tile')
     model_path, in_dir, out_dir = argv[0], argv[1], argv[2]
     prec = argv[3] if len(argv) > 3 else 'fp32'
     dev = torch.device('cuda')
@@ -53,7 +59,8 @@ def main():
         img = np.array(Image.open(path).convert('RGB')).astype(np.float64) / 255
         x = torch.from_numpy(np.transpose(img, (2, 0, 1))).float().unsqueeze(0).to(dev)
         with torch.no_grad():
-            y = model.forward_tiled(x, *tiled) if tiled else model.forward_x8(x) if x8 else model(x)
+            y = (model.forward_tiled_x8(x, *tiled_x8) if tiled_x8 else model.forward_tiled(x, *tiled) if tiled else
+                 model.forward_x8(x) if x8 else model(x))
             out = y.data.squeeze().float().cpu().clamp_(0, 1).numpy()
         out = (np.transpose(out, (1, 2, 0)) * 255.0).round().astype(np.uint8)
         Image.fromarray(out).save(os.path.join(out_dir, '%s_rlt.png' % base))
