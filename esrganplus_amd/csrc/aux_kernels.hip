@@ -17,7 +17,11 @@ __device__ __forceinline__ void pack_piece(const esr_pack& p, int64_t idx) {
       const int ci_f = cb * 32 + esr_pi(i);
       T* dst = (T*)p.dst + idx * EPL;
 #pragma unroll
-      for (int e = 0; e < EPL; ++e) dst[e] = (T)(p.src[(int64_t)(16 * h + 8 * c + e) * p.cin + ci_f] * (p.scale == 0.f ? 1.f : p.scale));
+      for (int e = 0; e < EPL; ++e) {
+        float y = p.src[(int64_t)(16 * h + 8 * c + e) * p.cin + ci_f] * (p.scale == 0.f ? 1.f : p.scale);
+        asm volatile("" : "+v"(y));   // two roundings, as for the gather pieces below
+        dst[e] = (T)y;
+      }
     }
     return;
   }
@@ -45,7 +49,12 @@ __device__ __forceinline__ void pack_piece(const esr_pack& p, int64_t idx) {
         if (p.fold_co0 > 0 && p.src_ks == 3)
           x += p.src[(((int64_t)ci * p.cin + p.fold_co0 + co) * 3 + (2 - kh)) * 3 + (2 - kw)];
       }
-      v[e] = (T)(x * p.scale);
+      // the product is rounded to fp32 and THEN to T for every element: left alone, hipcc converts six of a lane's eight
+      // halves that way (v_mul_f32 + v_cvt_pk_f16_f32) and two with v_fma_mixlo_f16, which rounds the exact product once
+      // — a different last bit in about one of 8000 scaled weights, by element index
+      float y = x * p.scale;
+      asm volatile("" : "+v"(y));
+      v[e] = (T)y;
     }
     T* dst = (T*)p.dst + ((((int64_t)cb * p.dst_nchunks + p.dst_chunk0 + chunk) * 9 + tap) * 64 + lane) * EPL;
 #pragma unroll
@@ -129,7 +138,7 @@ __device__ __forceinline__ void pack_piece(const esr_pack& p, int64_t idx) {
 }
 
 template <typename T>
-__global__ void pack_kernel(const esr_pack p, int nchunks, int64_t total) {
+__global__ void pack_kernel(const esr_pack p, int64_t total) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx < total) pack_piece<T>(p, idx);
 }
@@ -255,26 +264,6 @@ extern "C" size_t esr_packed_weight_bytes(int32_t cout, int32_t cin, int32_t ks,
   return cbs * chunks * ks * ks * 1024;
 }
 
-extern "C" int esr_pack_conv_weights(const esr_pack* p, esr_stream_t stream) {
-  if (!p || !p->src || !p->dst || p->cout <= 0 || p->cin <= 0 || (p->ks != 1 && p->ks != 3 && p->ks != 4) ||
-      (p->ups_dgrad && !(p->transpose_flip && p->ks == 4)) || (p->ups_fwd && (p->transpose_flip || p->gather || p->ks != 3))) {
-    esr_set_error("esr_pack_conv_weights: invalid arguments");
-    return ESR_ERR_INVALID;
-  }
-  const int cpg = p->dtype == ESR_F16 ? 16 : 8;
-  // packed geometry: rows = the packed conv's couts, K = its cins
-  const int rows = p->transpose_flip ? p->cin : p->cout;
-  const int kdim = p->transpose_flip ? p->cout : p->cin;
-  const int nchunks = (kdim + cpg - 1) / cpg;
-  const int64_t total = p->ups_fwd ? (int64_t)((rows + 31) / 32) * 4 * nchunks * 4 * 64 : (int64_t)((rows + 31) / 32) * nchunks * p->ks * p->ks * 64;
-  const int blocks = (int)((total + 255) / 256);
-  hipStream_t st = (hipStream_t)stream;
-  if (p->dtype == ESR_F16) hipLaunchKernelGGL(pack_kernel<_Float16>, dim3(blocks), dim3(256), 0, st, *p, nchunks, total);
-  else if (p->dtype == ESR_F32) hipLaunchKernelGGL(pack_kernel<float>, dim3(blocks), dim3(256), 0, st, *p, nchunks, total);
-  else { esr_set_error("esr_pack_conv_weights: bad dtype"); return ESR_ERR_INVALID; }
-  return esr_check_launch("pack_kernel");
-}
-
 extern "C" int64_t esr_pack_pieces(const esr_pack* p) {
   const int cpg = p->dtype == ESR_F16 ? 16 : 8;
   if (p->one_t) return 4 * 64;
@@ -283,6 +272,23 @@ extern "C" int64_t esr_pack_pieces(const esr_pack* p) {
   const int rows = p->transpose_flip ? p->cin : p->cout;
   const int kdim = p->transpose_flip ? p->cout : p->cin;
   return (int64_t)((rows + 31) / 32) * ((kdim + cpg - 1) / cpg) * p->ks * p->ks * 64;
+}
+
+extern "C" int esr_pack_conv_weights(const esr_pack* p, esr_stream_t stream) {
+  if (!p || !p->src || !p->dst || p->cout <= 0 || p->cin <= 0 || (p->ks != 1 && p->ks != 3 && p->ks != 4) ||
+      (p->ups_dgrad && !(p->transpose_flip && p->ks == 4)) || (p->ups_fwd && (p->transpose_flip || p->gather || p->ks != 3))) {
+    esr_set_error("esr_pack_conv_weights: invalid arguments");
+    return ESR_ERR_INVALID;
+  }
+  if (p->dtype != ESR_F16 && p->dtype != ESR_F32) { esr_set_error("esr_pack_conv_weights: bad dtype"); return ESR_ERR_INVALID; }
+  // one thread per piece pack_piece decodes: the count the batch launch uses (a gather entry's rows are dst_cout, not
+  // the forward conv's cin; one_t has four fragments)
+  const int64_t total = esr_pack_pieces(p);
+  const int blocks = (int)((total + 255) / 256);
+  hipStream_t st = (hipStream_t)stream;
+  if (p->dtype == ESR_F16) hipLaunchKernelGGL(pack_kernel<_Float16>, dim3(blocks), dim3(256), 0, st, *p, total);
+  else hipLaunchKernelGGL(pack_kernel<float>, dim3(blocks), dim3(256), 0, st, *p, total);
+  return esr_check_launch("pack_kernel");
 }
 
 extern "C" int esr_pack_conv_weights_batch(const esr_pack_batch* p, esr_stream_t stream) {

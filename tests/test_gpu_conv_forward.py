@@ -20,6 +20,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.pack_refs import subpix_conv, subpix_taps      # esr_pack.ups_fwd's pre-summed taps, shared with the pack tests
 from tests.test_gpu_conv_backward import (SENT, SLOPE, _mods, cdiv, check_buffer, conv3_branch, dev, g32, q,  # noqa: F401
                                           rel_err, rnd, run, s2_branch, upload)
 
@@ -243,34 +244,6 @@ def test_epilogue_cases_route_as_pinned():
 # ----------------------------------------------------------------------------------------------------------------
 # references
 # ----------------------------------------------------------------------------------------------------------------
-
-SUBPIX_ROWS = {0: ((0, 0), (1, 2)), 1: ((0, 1), (2, 2))}     # phase d: 3x3 rows summed into 2x2 tap 0 / 1
-
-
-def subpix_taps(w):
-    """[4][cout][cin][2][2] pre-summed taps of esr_pack.ups_fwd in w's dtype, summed in the packer's order"""
-    k = torch.zeros((4,) + tuple(w.shape[:2]) + (2, 2), dtype=w.dtype)
-    for dy in (0, 1):
-        for dx in (0, 1):
-            for a, (r0, r1) in enumerate(SUBPIX_ROWS[dy]):
-                for b, (c0, c1) in enumerate(SUBPIX_ROWS[dx]):
-                    s = torch.zeros(w.shape[:2], dtype=w.dtype)
-                    for r in range(r0, r1 + 1):
-                        for c in range(c0, c1 + 1):
-                            s = s + w[:, :, r, c]
-                    k[2 * dy + dx, :, :, a, b] = s
-    return k
-
-
-def subpix_conv(x, k):
-    """output pixel (2y+dy, 2x+dx) = 2x2 conv of phase (dy, dx) over input rows y-1+dy.., columns x-1+dx.."""
-    B, _, h, w = x.shape
-    out = torch.zeros(B, k.shape[1], 2 * h, 2 * w, dtype=x.dtype)
-    xp = F.pad(x, (1, 1, 1, 1))
-    for dy in (0, 1):
-        for dx in (0, 1):
-            out[:, :, dy::2, dx::2] = F.conv2d(xp, k[2 * dy + dx])[:, :, dy:dy + h, dx:dx + w]
-    return out
 
 
 def test_subpix_reference_is_nearest_x2_conv3():
