@@ -258,7 +258,7 @@ EXPORTS = ['esr_packed_weight_bytes', 'esr_g32_dims', 'esr_conv_forward', 'esr_p
            'esr_l1_loss_forward', 'esr_ragan_loss_forward', 'esr_rdb_wgrad_run', 'esr_rdb_wgrad_workspace_elems', 'esr_rdb_backward',
            'esr_rdb_mask_bytes', 'esr_rdb_check_abort', 'esr_debug_hold_cus', 'esr_debug_device_alias', 'esr_debug_chain_order_waits',
            'esr_debug_mfma_probe', 'esr_debug_rdb_wgrad_follow', 'esr_dihedral_op', 'esr_tile_op',
-           'esr_tile_x8_op']
+           'esr_tile_x8_op', 'esr_l2_loss_forward']
 
 _lib = None
 _lock = threading.Lock()
@@ -317,7 +317,8 @@ def lib():
                          ('esr_grad_unpermute', esr_unpermute), ('esr_adam_step', esr_adam), ('esr_amp_step', esr_amp), ('esr_resample_axis', esr_resample),
                          ('esr_pack_conv_weights_batch', esr_pack_batch), ('esr_rdb_forward', esr_rdb_chain),
                          ('esr_gather_fragments', esr_frag_gather), ('esr_image_metrics', esr_img_metrics),
-                         ('esr_l1_loss_forward', esr_l1_loss), ('esr_ragan_loss_forward', esr_ragan_loss),
+                         ('esr_l1_loss_forward', esr_l1_loss), ('esr_l2_loss_forward', esr_l1_loss),
+                         ('esr_ragan_loss_forward', esr_ragan_loss),
                          ('esr_rdb_wgrad_run', esr_rdb_wgrad), ('esr_rdb_backward', esr_rdb_chain),
                          ('esr_dihedral_op', esr_dihedral), ('esr_tile_op', esr_tile),
                          ('esr_tile_x8_op', esr_tile_x8)):

@@ -11,7 +11,9 @@ Appendix B).  What the reference does around them lives here:
   (codes/train.py:162-165) and the resume branch (train.py:27-28, 86-91; options.py:106-120) do for a
   ``train.ESRGANPlusStep``: ``{step}_G.pth`` / ``{step}_D.pth`` / ``{step}.state`` in the reference's layouts, taken
   behind whatever a pipelined step left in flight, plus — new, the reference trains in fp32 — the dynamic loss
-  scaler's state, so that a resumed fp16 run continues bit for bit (tests/test_gpu_train_step.py)."""
+  scaler's state, so that a resumed fp16 run continues bit for bit (tests/test_gpu_train_step.py).  A step without a
+  discriminator (``train.PSNRStep``, the reference's SRModel) writes and reads ``{step}_G.pth`` / ``{step}.state``
+  with one optimizer entry."""
 from collections import OrderedDict
 
 import torch
@@ -54,27 +56,36 @@ def resume_training(resume_state, optimizers, schedulers):
         s.load_state_dict(sd)
 
 
+def _step_optimizers(step):
+    if getattr(step, 'netD', None) is None:
+        return [step.optimizer_G]
+    return [step.optimizer_G, step.optimizer_D]
+
+
 def save_step(step, directory, epoch, iter_step, schedulers=()):
     """models/{iter}_G.pth, models/{iter}_D.pth, training_state/{iter}.state of a ``train.ESRGANPlusStep`` (the file
     names and dict layouts of base_model.py:50-74; `directory` plays opt['path']['models'] / ['training_state']).
     The step's side-stream tail (D's Adam, weight packs) is ordered first; the networks' ``state_dict()`` join it too.
-    Returns the three paths."""
+    A step without ``netD`` (train.PSNRStep; SR_model.py:150-151 saves G only) writes no ``_D.pth`` and one optimizer
+    entry.  Returns the paths written: (G, D, state), or (G, state)."""
     import os
     step.finish()
     os.makedirs(directory, exist_ok=True)
     pg = os.path.join(directory, '%s_G.pth' % iter_step)
     pd = os.path.join(directory, '%s_D.pth' % iter_step)
     ps = os.path.join(directory, '%s.state' % iter_step)
+    has_d = getattr(step, 'netD', None) is not None
     save_network(step.netG, pg)
-    save_network(step.netD, pd)
+    if has_d:
+        save_network(step.netD, pd)
     state = {'epoch': epoch, 'iter': iter_step,
              'schedulers': [s.state_dict() for s in schedulers],
-             'optimizers': [step.optimizer_G.state_dict(), step.optimizer_D.state_dict()]}
+             'optimizers': [o.state_dict() for o in _step_optimizers(step)]}
     if step.scaler is not None:
         # fp16 path only (no counterpart in the reference): {scale, -, good steps, -, found flags}
         state['loss_scaler'] = step.scaler.state.detach().cpu()
     torch.save(state, ps)
-    return pg, pd, ps
+    return (pg, pd, ps) if has_d else (pg, ps)
 
 
 def resume_step(step, directory, iter_step, schedulers=()):
@@ -84,9 +95,10 @@ def resume_step(step, directory, iter_step, schedulers=()):
     import os
     step.finish()
     load_network(os.path.join(directory, '%s_G.pth' % iter_step), step.netG)
-    load_network(os.path.join(directory, '%s_D.pth' % iter_step), step.netD)
+    if getattr(step, 'netD', None) is not None:
+        load_network(os.path.join(directory, '%s_D.pth' % iter_step), step.netD)
     state = torch.load(os.path.join(directory, '%s.state' % iter_step), map_location='cpu')
-    resume_training(state, [step.optimizer_G, step.optimizer_D], list(schedulers))
+    resume_training(state, _step_optimizers(step), list(schedulers))
     if step.scaler is not None:
         if 'loss_scaler' in state:
             step.scaler.state.copy_(state['loss_scaler'].to(step.scaler.state.device))

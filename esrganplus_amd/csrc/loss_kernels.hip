@@ -1,18 +1,22 @@
-// loss_kernels.hip — the three losses of the ESRGAN+ train step (SRRaGAN_model.py:124-137,150-156) with their
-// gradients, one launch each:  L1Loss (loss.py / nn.L1Loss: cri_pix, cri_fea) and the relativistic-average GAN
-// term  ( BCEWithLogits(x - mean(y), tx) + BCEWithLogits(y - mean(x), ty) ) / 2  (GANLoss 'vanilla',
+// loss_kernels.hip — the losses of the ESRGAN+ train step (SRRaGAN_model.py:124-137,150-156) with their gradients, one
+// launch each:  L1Loss / MSELoss (nn.L1Loss, nn.MSELoss: cri_pix, cri_fea 'l1' / 'l2') and the relativistic-average
+// GAN term  ( BCEWithLogits(x - mean(y), tx) + BCEWithLogits(y - mean(x), ty) ) / 2  (GANLoss 'vanilla',
 // loss.py:6-38).  As torch ops these are ~70 tiny dependent launches per step (sub, abs, mean, sigmoid, ...,
 // and their backward) — more chip time in launch gaps than in arithmetic.  HBM-bound, tiny.
 #include "common.h"
 
 namespace {
 
-// loss = weight * mean|a - b| ; grad_a = weight * sign(a - b) / n.  One pass; the last workgroup to arrive turns the
-// fp64 sum into the loss and clears the scratch for the next call.
-__global__ __launch_bounds__(256) void l1_loss_kernel(const esr_l1_loss p) {
+// L2 = false: loss = weight * mean|a - b| ; grad_a = weight * sign(a - b) / n                     (nn.L1Loss)
+// L2 = true:  loss = weight * mean (a - b)^2 ; grad_a = weight * 2 (a - b) / n                    (nn.MSELoss)
+// One pass; the last workgroup to arrive turns the fp64 sum into the loss and clears the scratch for the next call.
+// L2: d = a - b is formed in fp32 and squared in fp64 (exact there: 24 x 24 bits), so a |d| up to fp32's largest still
+// sums without overflow; the gradient's factor is ((2 weight / n) grad_scale) scale_dev, three roundings, times d.
+template <bool L2>
+__global__ __launch_bounds__(256) void pixel_loss_kernel(const esr_l1_loss p) {
   const int64_t stride = (int64_t)gridDim.x * 256 * 4;
   double s = 0.0;
-  const float gw = p.weight / (float)p.n * (p.grad_scale != 0.f ? p.grad_scale : 1.f) * (p.grad_scale_dev ? *p.grad_scale_dev : 1.f);
+  const float gw = (L2 ? 2.f * p.weight : p.weight) / (float)p.n * (p.grad_scale != 0.f ? p.grad_scale : 1.f) * (p.grad_scale_dev ? *p.grad_scale_dev : 1.f);
   // 16-byte vector accesses only when all three pointers allow them (a view with an odd storage offset takes the
   // scalar path: same sums, same order per thread)
   const bool vec = (((uintptr_t)p.a | (uintptr_t)p.b | (uintptr_t)p.grad_a) & 15) == 0;
@@ -23,15 +27,25 @@ __global__ __launch_bounds__(256) void l1_loss_kernel(const esr_l1_loss p) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float d = a[e] - b[e];
-        s += fabsf(d);
-        g[e] = d > 0.f ? gw : (d < 0.f ? -gw : 0.f);
+        if (L2) {
+          s += (double)d * (double)d;
+          g[e] = gw * d;
+        } else {
+          s += fabsf(d);
+          g[e] = d > 0.f ? gw : (d < 0.f ? -gw : 0.f);
+        }
       }
       if (p.grad_a) *(f32x4*)(p.grad_a + i0) = g;
     } else {
       for (int64_t i = i0; i < p.n && i < i0 + 4; ++i) {
         const float d = p.a[i] - p.b[i];
-        s += fabsf(d);
-        if (p.grad_a) p.grad_a[i] = d > 0.f ? gw : (d < 0.f ? -gw : 0.f);
+        if (L2) {
+          s += (double)d * (double)d;
+          if (p.grad_a) p.grad_a[i] = gw * d;
+        } else {
+          s += fabsf(d);
+          if (p.grad_a) p.grad_a[i] = d > 0.f ? gw : (d < 0.f ? -gw : 0.f);
+        }
       }
     }
   }
@@ -133,15 +147,24 @@ __global__ __launch_bounds__(256) void ragan_loss_kernel(const esr_ragan_loss p)
 
 }  // namespace
 
-extern "C" int esr_l1_loss_forward(const esr_l1_loss* p, esr_stream_t stream) {
+template <bool L2>
+static int pixel_loss_launch(const esr_l1_loss* p, esr_stream_t stream, const char* entry, const char* kernel) {
   if (!p || !p->a || !p->b || !p->loss || !p->scratch || p->n <= 0) {
-    esr_set_error("esr_l1_loss_forward: invalid arguments");
+    esr_set_error("%s: invalid arguments", entry);
     return ESR_ERR_INVALID;
   }
   int64_t wgs = (p->n + 4095) / 4096;           // 16 elements per thread
   if (wgs > 1024) wgs = 1024;
-  hipLaunchKernelGGL(l1_loss_kernel, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, *p);
-  return esr_check_launch("l1_loss_kernel");
+  hipLaunchKernelGGL(pixel_loss_kernel<L2>, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, *p);
+  return esr_check_launch(kernel);
+}
+
+extern "C" int esr_l1_loss_forward(const esr_l1_loss* p, esr_stream_t stream) {
+  return pixel_loss_launch<false>(p, stream, "esr_l1_loss_forward", "l1_loss_kernel");
+}
+
+extern "C" int esr_l2_loss_forward(const esr_l1_loss* p, esr_stream_t stream) {
+  return pixel_loss_launch<true>(p, stream, "esr_l2_loss_forward", "l2_loss_kernel");
 }
 
 extern "C" int esr_ragan_loss_forward(const esr_ragan_loss* p, esr_stream_t stream) {

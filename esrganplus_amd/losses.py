@@ -1,5 +1,5 @@
-"""The ESRGAN+ train step's losses as single launches (csrc/loss_kernels.hip): ``nn.L1Loss`` (cri_pix / cri_fea,
-SRRaGAN_model.py:124-131) and the relativistic-average GAN term built from ``GANLoss('vanilla')``
+"""The ESRGAN+ train step's losses as single launches (csrc/loss_kernels.hip): ``nn.L1Loss`` / ``nn.MSELoss`` (cri_pix /
+cri_fea 'l1' / 'l2', SRRaGAN_model.py:31-53,124-131; SR_model.py:28-34) and the relativistic-average GAN term built from ``GANLoss('vanilla')``
 (codes/models/modules/loss.py:6-38; SRRaGAN_model.py:133-137, 150-156).  Each forward launch also produces the
 gradient w.r.t. its differentiable operands; backward is one multiply by the upstream scalar.
 
@@ -39,9 +39,11 @@ def _check_operands(name, *ts):
                  '%s: operand is %s / %s' % (name, getattr(t, 'device', type(t)), getattr(t, 'dtype', '')))
 
 
-class _L1Fn(torch.autograd.Function):
+class _PixelFn(torch.autograd.Function):
+    """The autograd face of one pixel-loss entry (`entry`: 'esr_l1_loss_forward' / 'esr_l2_loss_forward')."""
+
     @staticmethod
-    def forward(ctx, a, b, weight):
+    def forward(ctx, a, b, weight, entry):
         a_, b_ = a.detach().contiguous(), b.detach().contiguous()
         loss = torch.empty((), dtype=torch.float32, device=a.device)
         grad = torch.empty_like(a_) if ctx.needs_input_grad[0] else None
@@ -49,13 +51,13 @@ class _L1Fn(torch.autograd.Function):
         p.a, p.b, p.loss, p.n, p.weight = a_.data_ptr(), b_.data_ptr(), loss.data_ptr(), a_.numel(), weight
         p.grad_a = grad.data_ptr() if grad is not None else None
         p.scratch = _dev_scratch(a.device).data_ptr()
-        L.check(L.lib().esr_l1_loss_forward(C.byref(p), C.c_void_p(E.current_stream())), 'esr_l1_loss_forward')
+        L.check(getattr(L.lib(), entry)(C.byref(p), C.c_void_p(E.current_stream())), entry)
         ctx.grad = grad
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        return (ctx.grad * g if ctx.grad is not None else None), None, None
+        return (ctx.grad * g if ctx.grad is not None else None), None, None, None
 
 
 def _as_f32(t):
@@ -69,24 +71,34 @@ def _scale_args(p, grad_scale, scale_dev):
         p.grad_scale_dev = scale_dev.data_ptr()
 
 
+def _pixel_raw(name, entry, a, b, weight, grad_out, grad_scale, scale_dev):
+    a_, b_ = a.detach().contiguous(), b.detach().contiguous()
+    _check_operands(name, a_, b_)
+    _require(a_.shape == b_.shape, '%s: shapes %s vs %s' % (name, tuple(a_.shape), tuple(b_.shape)))
+    loss = torch.empty((), dtype=torch.float32, device=a_.device)
+    p = L.esr_l1_loss()
+    p.a, p.b, p.loss, p.n, p.weight = a_.data_ptr(), b_.data_ptr(), loss.data_ptr(), a_.numel(), float(weight)
+    if grad_out is not None:
+        _require(grad_out.is_contiguous() and grad_out.dtype == torch.float32 and grad_out.numel() == a_.numel(), name + ': grad_out')
+        p.grad_a = grad_out.data_ptr()
+    p.scratch = _dev_scratch(a_.device).data_ptr()
+    _scale_args(p, grad_scale, scale_dev)
+    L.check(getattr(L.lib(), entry)(C.byref(p), C.c_void_p(E.current_stream())), entry)
+    return loss
+
+
 def l1_raw(a, b, weight, grad_out=None, grad_scale=1.0, scale_dev=None):
     """One launch, no autograd: ``(weight * mean|a - b|, grad)`` with ``grad = grad_scale [* scale_dev[0]] * weight *
     sign(a - b) / n`` written into ``grad_out`` (a contiguous fp32 tensor of a's size — e.g. the buffer a backward launch
     list reads its upstream gradient from) or not formed at all (``grad_out=None``).  The hand-written train step
     (train.ESRGANPlusStep) calls the losses this way; ``l1_loss`` is the autograd face of the same kernel."""
-    a_, b_ = a.detach().contiguous(), b.detach().contiguous()
-    _check_operands('l1_raw', a_, b_)
-    _require(a_.shape == b_.shape, 'l1_raw: shapes %s vs %s' % (tuple(a_.shape), tuple(b_.shape)))
-    loss = torch.empty((), dtype=torch.float32, device=a_.device)
-    p = L.esr_l1_loss()
-    p.a, p.b, p.loss, p.n, p.weight = a_.data_ptr(), b_.data_ptr(), loss.data_ptr(), a_.numel(), float(weight)
-    if grad_out is not None:
-        _require(grad_out.is_contiguous() and grad_out.dtype == torch.float32 and grad_out.numel() == a_.numel(), 'l1_raw: grad_out')
-        p.grad_a = grad_out.data_ptr()
-    p.scratch = _dev_scratch(a_.device).data_ptr()
-    _scale_args(p, grad_scale, scale_dev)
-    L.check(L.lib().esr_l1_loss_forward(C.byref(p), C.c_void_p(E.current_stream())), 'esr_l1_loss_forward')
-    return loss
+    return _pixel_raw('l1_raw', 'esr_l1_loss_forward', a, b, weight, grad_out, grad_scale, scale_dev)
+
+
+def l2_raw(a, b, weight, grad_out=None, grad_scale=1.0, scale_dev=None):
+    """``l1_raw`` for ``nn.MSELoss``: ``weight * mean (a - b)^2`` with ``grad = grad_scale [* scale_dev[0]] * weight *
+    2 (a - b) / n`` into ``grad_out`` (None: not formed).  One launch, the device scratch of ``l1_raw``."""
+    return _pixel_raw('l2_raw', 'esr_l2_loss_forward', a, b, weight, grad_out, grad_scale, scale_dev)
 
 
 def ragan_raw(x, y, x_is_real, y_is_real, weight, grad_x=None, grad_y=None, grad_scale=1.0, scale_dev=None,
@@ -131,14 +143,35 @@ def ragan_raw(x, y, x_is_real, y_is_real, weight, grad_x=None, grad_y=None, grad
     return loss, out
 
 
+def _pixel_loss(name, entry, a, b, weight):
+    a, b = _as_f32(a), _as_f32(b)
+    _check_operands(name, a, b)
+    _require(a.shape == b.shape, '%s: shapes %s vs %s' % (name, tuple(a.shape), tuple(b.shape)))
+    _require(not b.requires_grad, name + ': the target must not require a gradient')
+    return _PixelFn.apply(a, b, float(weight), entry)
+
+
 def l1_loss(a, b, weight=1.0):
     """``weight * F.l1_loss(a, b)``; the gradient flows to ``a`` only (``b`` is the target: var_H / real_fea — a target
     that requires a gradient is refused, not silently detached).  fp16 / bf16 operands are upcast."""
-    a, b = _as_f32(a), _as_f32(b)
-    _check_operands('l1_loss', a, b)
-    _require(a.shape == b.shape, 'l1_loss: shapes %s vs %s' % (tuple(a.shape), tuple(b.shape)))
-    _require(not b.requires_grad, 'l1_loss: the target must not require a gradient')
-    return _L1Fn.apply(a, b, float(weight))
+    return _pixel_loss('l1_loss', 'esr_l1_loss_forward', a, b, weight)
+
+
+def l2_loss(a, b, weight=1.0):
+    """``weight * F.mse_loss(a, b)``, otherwise as ``l1_loss`` (gradient to ``a`` only, fp16 / bf16 upcast)."""
+    return _pixel_loss('l2_loss', 'esr_l2_loss_forward', a, b, weight)
+
+
+# the reference's criterion names (SR_model.py:28-34, SRRaGAN_model.py:31-53) -> (raw form, autograd form)
+CRITERIA = {'l1': (l1_raw, l1_loss), 'l2': (l2_raw, l2_loss)}
+
+
+def criterion(loss_type):
+    """(raw, autograd) forms of the reference's ``pixel_criterion`` / ``feature_criterion`` names."""
+    try:
+        return CRITERIA[loss_type]
+    except (KeyError, TypeError):
+        raise NotImplementedError('Loss type [{:s}] is not recognized.'.format(str(loss_type))) from None
 
 
 class _RaGANFn(torch.autograd.Function):

@@ -42,8 +42,12 @@ def _buffer_like(buf, ref):
 
 class ESRGANPlusStep:
     def __init__(self, netG, netD, netF, lr_G=1e-4, lr_D=1e-4, beta1_G=0.9, beta1_D=0.9,
-                 pixel_weight=1e-2, feature_weight=1.0, gan_weight=5e-3, loss_scale=1.0, data_parallel=None):
+                 pixel_weight=1e-2, feature_weight=1.0, gan_weight=5e-3, loss_scale=1.0, data_parallel=None,
+                 pixel_criterion='l1', feature_criterion='l1'):
         self.netG, self.netD, self.netF = netG, netD, netF
+        # 'l1' / 'l2' (SRRaGAN_model.py:31-53): the raw and the autograd form of each criterion's one launch
+        self._pix_raw, self._pix_loss = LS.criterion(pixel_criterion)
+        self._fea_raw, self._fea_loss = LS.criterion(feature_criterion)
         self.l_pix_w, self.l_fea_w, self.l_gan_w = pixel_weight, feature_weight, gan_weight
         # data_parallel: None = follow torch.distributed (world size > 1); False inside a multi-rank job = this rank's
         # own step without any exchange (bench.py's no-exchange figure next to the data-parallel one)
@@ -257,7 +261,7 @@ class ESRGANPlusStep:
             real_fea.record_stream(main)
         fake_H = netG(var_L, z=z) if z is not None else netG(var_L)
         self.fake_H = fake_H
-        l_g_pix = LS.l1_loss(fake_H, var_H, self.l_pix_w)
+        l_g_pix = self._pix_loss(fake_H, var_H, self.l_pix_w)
         if side is not None:
             # join BEFORE netF runs on the main stream: the first netF call of a process packs its weights on the
             # side stream, and the side work finished under the generator's forward anyway
@@ -265,7 +269,7 @@ class ESRGANPlusStep:
             fake_fea = netF(fake_H)
         else:
             fake_fea, real_fea = netF.forward_pair(fake_H, var_H)
-        l_g_fea = LS.l1_loss(fake_fea, real_fea, self.l_fea_w)
+        l_g_fea = self._fea_loss(fake_fea, real_fea, self.l_fea_w)
         # both operands in ONE pass (forward_pair: per-half BatchNorm statistics, the detached ``real`` half
         # costs no backward) — the reference's call order fake, real is the group order.  shared: the same pass
         # also keeps what the D step's pair needs (forward_shared), so that pair costs no second forward
@@ -390,14 +394,14 @@ class _ManualPass:
     def pixel_loss(self, var_H):
         st = self.st
         st._gy = _buffer_like(st._gy, self.fake)
-        self.l_g_pix = LS.l1_raw(self.fake, var_H, st.l_pix_w, grad_out=st._gy, grad_scale=self.S, scale_dev=self.sdev)
+        self.l_g_pix = st._pix_raw(self.fake, var_H, st.l_pix_w, grad_out=st._gy, grad_scale=self.S, scale_dev=self.sdev)
 
     def netf_fake(self):
         st = self.st
         fake_fea, self.leaseF = st.netF._run_forward(self.fake, need_bwd=True)
         self.PF = self.leaseF.plan
-        self.l_g_fea = LS.l1_raw(fake_fea, self.real_fea, st.l_fea_w, grad_out=self.PF.gy_tensor,
-                                 grad_scale=self.S, scale_dev=self.sdev)
+        self.l_g_fea = st._fea_raw(fake_fea, self.real_fea, st.l_fea_w, grad_out=self.PF.gy_tensor,
+                                   grad_scale=self.S, scale_dev=self.sdev)
 
     def netd_forward(self, var_ref):
         st, main, n, d_early = self.st, self.main, self.n, self.d_early
@@ -567,3 +571,175 @@ class _ManualPass:
             st.log = {k: float(v) for k, v in
                       zip(LOG_KEYS, _log_values(self.l_g_pix, self.l_g_fea, self.l_g_gan, self.aux))}
         return st.log
+
+
+class PSNRStep:
+    """The PSNR-oriented pretraining step — ``SRModel.optimize_parameters`` (codes/models/SR_model.py:66-74) with the
+    set-up of its constructor (SR_model.py:24-53; codes/options/train/train_sr.json): one pixel criterion ('l1' /
+    'l2') on the generator's output, Adam(lr_G, weight_decay_G) over the parameters that train.  Stage one of the
+    ESRGAN+ recipe: its result is the `pretrain_model_G` that ``ESRGANPlusStep`` fine-tunes.
+
+    Production form (``netG.flat_param_grads``, every parameter trains): the generator's launch lists driven directly,
+    the phases of bench.py's generator loop — training forward, ONE loss launch that also writes dL/d fake_H (times the
+    loss scale) into a persistent buffer, backward, gradient exchange, fused Adam (which divides the scale out), loss
+    scaler update, weight packs.  Beside the main stream: the backward's step-independent preliminaries
+    (``functional.rrdbnet_train_prepare``) run on the side stream under the forward, and the input-gradient weight
+    packs — which only the NEXT backward reads — follow the Adam update there.  Autograd form (ESR_TRAIN_MANUAL=0, a
+    frozen parameter, a network without the flat gradient route): ``netG(var_L)``, the criterion's autograd face,
+    ``torch.autograd.backward`` with the scale."""
+
+    def __init__(self, netG, lr_G=2e-4, weight_decay_G=0, beta1_G=0.9, pixel_criterion='l1', pixel_weight=1.0,
+                 loss_scale=1.0, data_parallel=None):
+        self.netG = netG
+        self._pix_raw, self._pix_loss = LS.criterion(pixel_criterion)
+        self.l_pix_w = pixel_weight
+        self.data_parallel = DP.active() if data_parallel is None else bool(data_parallel)
+        self.scaler = None
+        if loss_scale == 'dynamic':
+            self.scaler = DynamicLossScaler(next(netG.parameters()).device)
+            loss_scale = 1.0
+        self.loss_scale = loss_scale
+        # "can optimize for a part of the model" (SR_model.py:40-44): a frozen parameter is left out
+        self.optimizer_G = FusedAdam([p for p in netG.parameters() if p.requires_grad], lr=lr_G,
+                                     betas=(beta1_G, 0.999), weight_decay=weight_decay_G if weight_decay_G else 0)
+        self.exG = DP.GradExchange(netG, enabled=self.data_parallel, measure=self.data_parallel)
+        self.log = {}
+        self.fake_H = None
+        self._steps = 0
+        self._gys = {}                     # dL/d fake_H, one buffer per (shape, device): mixed LR buckets alternate
+        self._log_host = self._ev_tail = self._scale_tensor = self._scale_value = None
+        self.overlap = ESRGANPlusStep._knob_int('ESR_TRAIN_OVERLAP', '1', (0, 1))
+        self.manual = os.environ.get('ESR_TRAIN_MANUAL', '1') != '0'
+
+    _scale_t = ESRGANPlusStep._scale_t
+
+    def _manual_ok(self):
+        netG = self.netG
+        return (self.manual and getattr(netG, 'flat_param_grads', False) and hasattr(netG, '_convs')
+                and all(p.requires_grad for p in netG._convs()[1]))
+
+    def _grad_buffer(self, fake):
+        key = (tuple(fake.shape), fake.device)
+        gy = self._gys.get(key)
+        if gy is None:
+            gy = self._gys[key] = torch.empty_like(fake)
+        return gy
+
+    def _step_manual(self, var_L, real_H, z, sync_log):
+        netG = self.netG
+        main = torch.cuda.current_stream()
+        side = E.concurrent_streams(var_L.device, 1)[0] if self.overlap >= 1 else None
+        S = float(self.loss_scale)
+        if not netG.mark_grads_stale():
+            self.optimizer_G.zero_grad(set_to_none=True)
+        ev_log = None
+        with torch.no_grad():
+            if side is not None:
+                ev0 = torch.cuda.Event()
+                ev0.record(main)                      # the previous step's Adam (it read the buffer `prepare` zeroes)
+            fake, stG = Fn.rrdbnet_train_forward(netG, var_L, z)
+            self.fake_H = fake
+            ev_prep = None
+            if side is not None:
+                side.wait_event(ev0)
+                with torch.cuda.stream(side):         # (behind the previous step's input-gradient packs, in order)
+                    Fn.rrdbnet_train_prepare(netG, stG)
+                    ev_prep = torch.cuda.Event()
+                    ev_prep.record(side)
+            gy = self._grad_buffer(fake)
+            l_pix = self._pix_raw(fake, real_H, self.l_pix_w, grad_out=gy, grad_scale=S,
+                                  scale_dev=self.scaler.state if self.scaler else None)
+            if sync_log:
+                # the host reads the loss, not the end of the step: copied right behind the loss launch
+                if self._log_host is None:
+                    self._log_host = torch.empty(1, dtype=torch.float32).pin_memory()
+                self._log_host.copy_(l_pix.reshape(1), non_blocking=True)
+                ev_log = torch.cuda.Event()
+                ev_log.record(main)
+            if ev_prep is not None:
+                main.wait_event(ev_prep)
+            Fn.rrdbnet_train_backward(netG, stG, gy)
+            self.exG.start()
+            self.exG.wait()
+            self.optimizer_G.step(grad_scale=1.0 / S, scaler=self.scaler)
+            if self.scaler:
+                self.scaler.update()
+            netG.prepack(fwd=True, dgrad=False)       # what the next forward starts with
+            if side is not None:
+                side.wait_stream(main)                # G's new weights
+                with torch.cuda.stream(side):
+                    netG.prepack(fwd=False, dgrad=True)
+                    self._ev_tail = torch.cuda.Event()
+                    self._ev_tail.record(side)
+                if hasattr(netG, '_defer_to'):
+                    netG._defer_to(self._ev_tail)     # its public entry points (forward, state_dict) join the tail
+            else:
+                netG.prepack(fwd=False, dgrad=True)
+        if not sync_log:
+            self.log = {'l_pix': l_pix}
+            return self.log
+        ev_log.synchronize()
+        self.log = {'l_pix': float(self._log_host[0])}
+        self.finish()                                 # the default call: everything ordered on the current stream
+        return self.log
+
+    def step(self, var_L, real_H, z=None, sync_log=True):
+        """One optimisation step (SR_model.py:66-74).  sync_log=False: the pipelined form — ``l_pix`` stays a device
+        tensor and the input-gradient weight packs may still be in flight on the side stream when the call returns
+        (the next step, ``finish()``, the generator's public entry points and a device synchronisation order them)."""
+        netG = self.netG
+        self._steps += 1
+        E.require_cuda(var_L, 'PSNRStep.step: var_L')         # (the generator and the fused losses have no CPU path)
+        if self._manual_ok():
+            return self._step_manual(var_L, real_H, z, sync_log)
+        if not (hasattr(netG, 'mark_grads_stale') and netG.mark_grads_stale()):
+            self.optimizer_G.zero_grad(set_to_none=True)
+        fake_H = netG(var_L, z=z) if z is not None else netG(var_L)
+        self.fake_H = fake_H
+        l_pix = self._pix_loss(fake_H, real_H, self.l_pix_w)
+        scale = self.scaler.scale if self.scaler else self._scale_t(fake_H.device)
+        torch.autograd.backward([l_pix], [scale])
+        self.exG.start()
+        self.exG.wait()
+        self.optimizer_G.step(grad_scale=1.0 / self.loss_scale, scaler=self.scaler)
+        if self.scaler:
+            self.scaler.update()
+        if hasattr(netG, 'prepack'):
+            netG.prepack(fwd=True, dgrad=True)
+        self.log = {'l_pix': float(l_pix.detach()) if sync_log else l_pix.detach()}
+        return self.log
+
+    def test(self, var_L):
+        """``SRModel.test`` (SR_model.py:76-80): the eval forward without gradient; the generator is back in training
+        mode afterwards.  Valid between pipelined steps (the generator's forward joins what they left in flight)."""
+        E.require_cuda(var_L, 'PSNRStep.test: var_L')
+        self.netG.eval()
+        try:
+            with torch.no_grad():
+                self.fake_H = self.netG(var_L)
+        finally:
+            self.netG.train()
+        return self.fake_H
+
+    def comm_reset(self):
+        self._steps = 0
+        self.exG.reset_counters()
+
+    def comm_report(self):
+        """Per step: all-reduce calls / bytes of the gradient exchange and the milliseconds the compute stream spent
+        blocked on it.  Synchronises the device."""
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        n = max(self._steps, 1)
+        return {'calls_per_step': self.exG.calls / n, 'bytes_per_step': self.exG.bytes / n,
+                'exposed_ms_per_step': self.exG.exposed_ms() / n}
+
+    def finish(self):
+        """Orders what a pipelined step left on the side stream in front of the current stream."""
+        if self._ev_tail is not None:
+            torch.cuda.current_stream().wait_event(self._ev_tail)
+
+    def state_dict(self):
+        """The optimizer's state (base_model.py:65-74 `save_training_state`), behind whatever is still in flight."""
+        self.finish()
+        return {'optimizers': [self.optimizer_G.state_dict()]}

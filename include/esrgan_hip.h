@@ -777,10 +777,15 @@ int esr_image_metrics(const esr_img_metrics* p, esr_stream_t stream);   /* repla
  * esr_l1_loss_forward: *loss = weight * mean|a - b| (nn.L1Loss, loss.py cri_pix / cri_fea);
  *   grad_a (optional) = weight * sign(a - b) / n.  scratch: 2 doubles of device memory, zero before the first
  *   call (the kernel leaves them zero).
+ * esr_l2_loss_forward: *loss = weight * mean (a - b)^2 (nn.MSELoss, cri_pix / cri_fea 'l2': SR_model.py:28-34,
+ *   SRRaGAN_model.py:31-53); grad_a (optional) = weight * 2 (a - b) / n.  The same argument struct, the same scratch
+ *   (shared with esr_l1_loss_forward: either kernel leaves it zero) and the same meaning of grad_scale /
+ *   grad_scale_dev; a - b is formed in fp32, squared and summed in fp64.
  * esr_ragan_loss_forward: *loss = weight/2 * ( BCEWithLogits(x - mean(y), tx) + BCEWithLogits(y - mean(x), ty) )
  *   (GANLoss 'vanilla' on the relativistic-average logits, loss.py:6-38); grad_x / grad_y optional (the means'
  *   dependence on the other side included); mean_x / mean_y optional outputs (the D_real / D_fake log values). */
 int esr_l1_loss_forward(const esr_l1_loss* p, esr_stream_t stream);
+int esr_l2_loss_forward(const esr_l1_loss* p, esr_stream_t stream);
 int esr_ragan_loss_forward(const esr_ragan_loss* p, esr_stream_t stream);
 
 /* Run a recorded list of ops back to back on `stream` (one host call per network pass; this is
