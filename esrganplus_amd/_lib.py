@@ -23,9 +23,12 @@ OP_RDB_CHAIN, OP_FRAG_GATHER, OP_RDB_WGRAD, OP_RDB_CHAIN_BWD = 11, 12, 13, 14
 OP_DIHEDRAL = 15
 OP_TILE = 16
 OP_TILE_X8 = 17
+OP_FOLD3 = 18
 BN_STATS, BN_FINALIZE, BN_APPLY, BN_BWD_REDUCE, BN_BWD_FINAL, BN_BWD_APPLY, BN_RESTAT, BN_FIN_APPLY = 0, 1, 2, 3, 4, 5, 6, 7
 NO_LAYER = 0xFFFFFFFF
 POOL_FWD, POOL_BWD, POOL_SHUFFLE, POOL_UNSHUFFLE = 0, 1, 2, 3      # esr_pool.mode
+POOL_SHUFFLE3, POOL_UNSHUFFLE3 = 4, 5                              # the 3x shuffle behind the folded x3 up-conv
+FOLD3_FOLD, FOLD3_UNFOLD = 0, 1                                    # esr_fold3.mode
 
 
 class esr_g32(C.Structure):
@@ -96,6 +99,11 @@ class esr_tile(C.Structure):
 class esr_tile_x8(C.Structure):
     _fields_ = esr_tile._fields_ + [('k_begin', C.c_int32), ('k_count', C.c_int32), ('accumulate', C.c_int32),
                                     ('mean_scale', C.c_float)]
+
+
+class esr_fold3(C.Structure):
+    _fields_ = [('mode', C.c_int32), ('cout', C.c_int32), ('cin', C.c_int32), ('_pad', C.c_int32),
+                ('w', C.c_void_p), ('bias', C.c_void_p), ('wf', C.c_void_p), ('bf', C.c_void_p)]
 
 
 class esr_noise_fill(C.Structure):
@@ -241,7 +249,7 @@ class _op_union(C.Union):
                 ('pool', esr_pool), ('linear', esr_linear), ('unpermute', esr_unpermute),
                 ('pack_batch', esr_pack_batch), ('rdb_chain', esr_rdb_chain), ('frag_gather', esr_frag_gather),
                 ('rdb_wgrad', esr_rdb_wgrad), ('dihedral', esr_dihedral), ('tile', esr_tile),
-                ('tile_x8', esr_tile_x8)]
+                ('tile_x8', esr_tile_x8), ('fold3', esr_fold3)]
 
 
 class esr_op(C.Structure):
@@ -258,7 +266,7 @@ EXPORTS = ['esr_packed_weight_bytes', 'esr_g32_dims', 'esr_conv_forward', 'esr_p
            'esr_l1_loss_forward', 'esr_ragan_loss_forward', 'esr_rdb_wgrad_run', 'esr_rdb_wgrad_workspace_elems', 'esr_rdb_backward',
            'esr_rdb_mask_bytes', 'esr_rdb_check_abort', 'esr_debug_hold_cus', 'esr_debug_device_alias', 'esr_debug_chain_order_waits',
            'esr_debug_mfma_probe', 'esr_debug_rdb_wgrad_follow', 'esr_dihedral_op', 'esr_tile_op',
-           'esr_tile_x8_op', 'esr_l2_loss_forward']
+           'esr_tile_x8_op', 'esr_l2_loss_forward', 'esr_fold3_op']
 
 _lib = None
 _lock = threading.Lock()
@@ -321,7 +329,7 @@ def lib():
                          ('esr_ragan_loss_forward', esr_ragan_loss),
                          ('esr_rdb_wgrad_run', esr_rdb_wgrad), ('esr_rdb_backward', esr_rdb_chain),
                          ('esr_dihedral_op', esr_dihedral), ('esr_tile_op', esr_tile),
-                         ('esr_tile_x8_op', esr_tile_x8)):
+                         ('esr_tile_x8_op', esr_tile_x8), ('esr_fold3_op', esr_fold3)):
             getattr(L, name).argtypes = [C.POINTER(st), C.c_void_p]
         if L.esr_sizeof_op() != C.sizeof(esr_op):
             raise HipExtensionError('ABI mismatch: sizeof(esr_op) C=%d ctypes=%d'

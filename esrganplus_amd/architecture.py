@@ -13,6 +13,9 @@ from . import block as B
 from .functional import run_rrdbnet, run_rrdbnet_tiled, run_rrdbnet_tiled_x8, run_rrdbnet_x8
 
 
+SUPPORTED_UPSCALE = (1, 2, 3, 4, 8)
+
+
 class _RRDBNetBase(B._PlannedModule):
     # parameter gradients leave the backward node through the module's flat store (block._PlannedModule._grad_store)
     # instead of ~770 autograd outputs; ESR_FLAT_GRADS=0 or `net.flat_param_grads = False` restores the per-tensor
@@ -26,11 +29,13 @@ class _RRDBNetBase(B._PlannedModule):
                                       'is available (block.pixelshuffle_block, SRResNet)')
         if upsample_mode != 'upconv':
             raise NotImplementedError('upsample mode [{:s}] is not found'.format(upsample_mode))
-        if (nf, upscale, norm_type, act_type.lower(), mode) != (64, 4, None, 'leakyrelu', 'CNA'):
-            raise NotImplementedError('HIP RRDBNet supports the ESRGAN+ configuration nf=64, x4, '
+        if (nf, norm_type, act_type.lower(), mode) != (64, None, 'leakyrelu', 'CNA'):
+            raise NotImplementedError('HIP RRDBNet supports the ESRGAN+ configuration nf=64, '
                                       'no norm, leakyrelu, CNA (train_ESRGANplus.json:36-45)')
-        self.in_nc, self.out_nc, self.nb = in_nc, out_nc, nb
-        n_up = int(math.log(upscale, 2))
+        if upscale not in SUPPORTED_UPSCALE:
+            # (the reference builds int(log2(upscale)) x2 stages for anything else — upscale=5 silently gives a x4 net)
+            raise NotImplementedError('HIP RRDBNet supports upscale in %s, got %r' % (SUPPORTED_UPSCALE, upscale))
+        self.in_nc, self.out_nc, self.nb, self.upscale = in_nc, out_nc, nb, int(upscale)
         fea_conv = B.conv_block(in_nc, nf, kernel_size=3, norm_type=None, act_type=None)
         # NB: the reference ignores its ``gc`` argument and always builds gc=32
         # (architecture.py:56) — so do we.
@@ -38,7 +43,10 @@ class _RRDBNetBase(B._PlannedModule):
                          norm_type=norm_type, act_type=act_type, mode='CNA',
                          extra_noise=extra_noise) for _ in range(nb)]
         lr_conv = B.conv_block(nf, nf, kernel_size=3, norm_type=norm_type, act_type=None, mode=mode)
-        ups = [B.upconv_blcok(nf, nf, act_type=act_type) for _ in range(n_up)]
+        if upscale == 3:                             # architecture.py:66-67: ONE nearest-x3 up-conv
+            ups = [B.upconv_blcok(nf, nf, 3, act_type=act_type)]
+        else:
+            ups = [B.upconv_blcok(nf, nf, act_type=act_type) for _ in range({1: 0, 2: 1, 4: 2, 8: 3}[upscale])]
         hr0 = B.conv_block(nf, nf, kernel_size=3, norm_type=None, act_type=act_type)
         hr1 = B.conv_block(nf, out_nc, kernel_size=3, norm_type=None, act_type=None)
         self.model = B.sequential(fea_conv, B.ShortcutBlock(B.sequential(*blocks, lr_conv)),
@@ -56,9 +64,17 @@ class _RRDBNetBase(B._PlannedModule):
                 out += B._rdb_convs('model.1.sub.%d.RDB%d' % (i, j), getattr(rr, 'RDB%d' % j))
         lr = m[1].sub[nb]
         out.append(('model.1.sub.%d' % nb, lr.weight, lr.bias))
-        for idx in (3, 6, 8, 10):
-            out.append(('model.%d' % idx, m[idx].weight, m[idx].bias))
+        for key in self._tail_keys():
+            c = m[int(key[6:])]
+            out.append((key, c.weight, c.bias))
         return out
+
+    def _tail_keys(self):
+        """Keys of the convs behind the trunk, in order: the up-convs, HR_conv0, HR_conv1 (x4: model.3, 6, 8, 10)."""
+        return ['model.%d' % i for i, c in enumerate(self.model) if i >= 2 and isinstance(c, nn.Conv2d)]
+
+    def _up_keys(self):
+        return self._tail_keys()[:-2]
 
     def attach_grad_sync(self, sync):
         """Data-parallel hook (dp.GradExchange): `sync(flat_slice)` starts the mean all-reduce of a finished
@@ -67,10 +83,15 @@ class _RRDBNetBase(B._PlannedModule):
 
     def _subpix_keys(self):
         # upconv_blcok (block.py:315-322) in its 4-phase 2x2 form: 16 instead of 36 MACs per 4 outputs
-        return () if os.environ.get('ESR_SUBPIX', '1') == '0' else ('model.3', 'model.6')
+        if self.upscale == 3 or os.environ.get('ESR_SUBPIX', '1') == '0':
+            return ()
+        return tuple(self._up_keys())
+
+    def _fold_keys(self):
+        return tuple(self._up_keys()) if self.upscale == 3 else ()
 
     def _dgrad_special(self):
-        return {'model.3': {'ups': True}, 'model.6': {'ups': True}}
+        return {} if self.upscale == 3 else {k: {'ups': True} for k in self._up_keys()}
 
     def _dgrad_extra(self, device):
         return self._eye_operand(device)
@@ -84,7 +105,7 @@ class _RRDBNetBase(B._PlannedModule):
         return out
 
     def forward(self, x, z=None):
-        """x: NCHW float32 in [0,1] on the MI355X -> [B, out_nc, 4H, 4W] float32.
+        """x: NCHW float32 in [0,1] on the MI355X -> [B, out_nc, sH, sW] float32, s = ``upscale``.
         ``z`` (training mode only): explicit N(0,1) tensors, one [B,64,H,W] per noise layer in
         execution order, for bit-parity tests; default = fused Philox stream."""
         self._join_pending()
@@ -92,17 +113,24 @@ class _RRDBNetBase(B._PlannedModule):
 
     def forward_x8(self, x, slots_per_pass=None):
         """Geometric self-ensemble (the reference's ``SRModel.test_x8``, codes/models/SR_model.py:82-120): the mean of the
-        eight flip / transpose variants, per image, as one batched launch plan -> [B, out_nc, 4H, 4W] float32 without
+        eight flip / transpose variants, per image, as one batched launch plan -> [B, out_nc, sH, sW] float32 without
         gradient.  Always the eval forward; ``self.training`` and ``requires_grad`` are left as they are.  See
         ``functional.run_rrdbnet_x8``."""
         self._join_pending()
         return run_rrdbnet_x8(self, x, slots_per_pass)
+
+    def _x4_only(self, what):
+        # the stitch kernels (esr_tile / esr_tile_x8) take scale 4 only: refused here, before any plan or launch
+        if self.upscale != 4:
+            raise ValueError('%s: the tiled forms are x4-only (this net has upscale=%d); use forward / forward_x8'
+                             % (what, self.upscale))
 
     def forward_tiled(self, x, tile=96, pad=16, tiles_per_pass=None):
         """Tiled eval forward: windows of tile + 2 pad LR pixels inside the image, ``tiles_per_pass`` of them per image as
         one batch, every tile's owned rectangle copied into the result -> [B, out_nc, 4H, 4W] float32 without gradient.
         One launch plan serves every image size; exact for pad >= 15 nb + 4, an approximation below.  Always the eval
         forward; ``self.training`` and ``requires_grad`` are left as they are.  See ``functional.run_rrdbnet_tiled``."""
+        self._x4_only('forward_tiled')
         self._join_pending()
         return run_rrdbnet_tiled(self, x, tile, pad, tiles_per_pass)
 
@@ -112,6 +140,7 @@ class _RRDBNetBase(B._PlannedModule):
         [B, out_nc, 4H, 4W] float32 without gradient.  One launch plan (two for non-square windows) serves every image
         size; mathematically ``forward_x8(x)`` for pad >= 15 nb + 4, an approximation below.  Always the eval forward;
         ``self.training`` and ``requires_grad`` are left as they are.  See ``functional.run_rrdbnet_tiled_x8``."""
+        self._x4_only('forward_tiled_x8')
         self._join_pending()
         return run_rrdbnet_tiled_x8(self, x, tile, pad, tiles_per_pass, slots_per_pass)
 

@@ -98,8 +98,8 @@ def conv1x1(in_planes, out_planes, stride=1):
 def upconv_blcok(in_nc, out_nc, upscale_factor=2, kernel_size=3, stride=1, bias=True,
                  pad_type='zero', norm_type=None, act_type='relu', mode='nearest', hip=False):
     """block.py:315-322 (sic: reference spelling)."""
-    if upscale_factor != 2 or mode != 'nearest':
-        raise NotImplementedError('only nearest x2 upconv is on the ESRGAN+ hot path')
+    if upscale_factor not in (2, 3) or mode != 'nearest':
+        raise NotImplementedError('only nearest x2 / x3 upconv is on the ESRGAN+ hot path')
     up = nn.Upsample(scale_factor=upscale_factor, mode=mode)
     return sequential(up, conv_block(in_nc, out_nc, kernel_size, stride, bias=bias, pad_type=pad_type,
                                      norm_type=norm_type, act_type=act_type, hip=hip))
@@ -459,7 +459,7 @@ class _PlannedModule(nn.Module):
         # convs (head / tail of the generator) are packed as plain transposes
         convs = [(k, w) for k, w, _ in self._conv_list()
                  if 'RDB' not in k and not k.startswith('rdb')] + self._dgrad_extra(device)
-        return E.DgradPack(convs, self.precision, device, self._dgrad_special(), self._dgrad_gathers())
+        return E.DgradPack(convs, self.precision, device, self._dgrad_special(), self._dgrad_gathers(), self._fold_keys())
 
     def _dgrad_weights(self, device):
         key = ('dgrad', self.precision, str(device))
@@ -470,6 +470,10 @@ class _PlannedModule(nn.Module):
 
     def _subpix_keys(self):
         """Keys of up-convs to run in the sub-pixel form (packs.WeightPack)."""
+        return ()
+
+    def _fold_keys(self):
+        """Keys of nearest-x3 up-convs, which run in their folded form (packs._Pack: entry key + '#fold')."""
         return ()
 
     def prepack(self, fwd=True, dgrad=True):
@@ -496,7 +500,7 @@ class _PlannedModule(nn.Module):
         key = (self.precision, str(device))
         wp = self._wp.get(key)
         if wp is None:
-            wp = E.WeightPack(self._conv_list(), self.precision, device, self._subpix_keys())
+            wp = E.WeightPack(self._conv_list(), self.precision, device, self._subpix_keys(), self._fold_keys())
             self._wp[key] = wp
         clean = self.__dict__.get('_weights_clean', False) or self.__dict__.pop('_prepacked_fwd', False)
         wp.ensure(E.current_stream(), force=self._force_repack or (self.training and not clean),

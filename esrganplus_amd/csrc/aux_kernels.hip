@@ -256,7 +256,73 @@ __global__ void noise_fill_kernel(const esr_noise_fill p) {
   }
 }
 
+// ---- esr_fold3: nearest-x3 + 3x3 conv as a 3x3 conv to 9 cout phase-major channels (include/esrgan_hip.h) ----
+// low-resolution offset that tap k of output phase p reads: floor((p + k - 1) / 3)
+__device__ __forceinline__ int fold3_off(int p, int k) { return p + k == 0 ? -1 : (p + k == 4 ? 1 : 0); }
+
+// one thread per folded weight (and per folded bias behind them): the sum of its 1..4 sources in (kh, kw) order
+__global__ __launch_bounds__(256) void fold3_kernel(const esr_fold3 p) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t nw = (int64_t)9 * p.cout * p.cin * 9;
+  if (idx >= nw) {
+    const int64_t o = idx - nw;
+    if (p.bf && p.bias && o < (int64_t)9 * p.cout) p.bf[o] = p.bias[o % p.cout];
+    return;
+  }
+  const int b = (int)(idx % 3), a = (int)(idx / 3 % 3);
+  const int64_t r = idx / 9;
+  const int ci = (int)(r % p.cin);
+  const int o = (int)(r / p.cin);
+  const int co = o % p.cout, ph = o / p.cout, pi = ph / 3, qi = ph % 3;
+  const float* src = p.w + ((int64_t)co * p.cin + ci) * 9;
+  float s = 0.f;
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw)
+      if (fold3_off(pi, kh) == a - 1 && fold3_off(qi, kw) == b - 1) s += src[kh * 3 + kw];
+  p.wf[idx] = s;
+}
+
+// the adjoint: one thread per weight of the 3x3 conv (and per bias behind them): nine terms in (p, q) order
+__global__ __launch_bounds__(256) void unfold3_kernel(const esr_fold3 p) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t nw = (int64_t)p.cout * p.cin * 9;
+  if (idx >= nw) {
+    const int64_t co = idx - nw;
+    if (p.bf && p.bias && co < p.cout) {
+      float s = 0.f;
+#pragma unroll
+      for (int ph = 0; ph < 9; ++ph) s += p.bf[(int64_t)ph * p.cout + co];
+      p.bias[co] = s;
+    }
+    return;
+  }
+  const int kw = (int)(idx % 3), kh = (int)(idx / 3 % 3);
+  const int64_t r = idx / 9;
+  const int ci = (int)(r % p.cin), co = (int)(r / p.cin);
+  float s = 0.f;
+#pragma unroll
+  for (int pi = 0; pi < 3; ++pi)
+#pragma unroll
+    for (int qi = 0; qi < 3; ++qi)
+      s += p.wf[((((int64_t)(pi * 3 + qi) * p.cout + co) * p.cin + ci) * 3 + fold3_off(pi, kh) + 1) * 3 + fold3_off(qi, kw) + 1];
+  p.w[idx] = s;
+}
+
 }  // namespace
+
+extern "C" int esr_fold3_op(const esr_fold3* p, esr_stream_t stream) {
+  if (!p || !p->w || !p->wf || p->cout <= 0 || p->cin <= 0 || (p->mode != 0 && p->mode != 1) || (!p->bias != !p->bf)) {
+    esr_set_error("esr_fold3_op: invalid arguments");
+    return ESR_ERR_INVALID;
+  }
+  const int64_t total = (int64_t)(p->mode == 0 ? 9 : 1) * p->cout * ((int64_t)p->cin * 9 + 1);
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  if (p->mode == 0) hipLaunchKernelGGL(fold3_kernel, grid, block, 0, (hipStream_t)stream, *p);
+  else hipLaunchKernelGGL(unfold3_kernel, grid, block, 0, (hipStream_t)stream, *p);
+  return esr_check_launch("fold3_kernel");
+}
 
 extern "C" size_t esr_packed_weight_bytes(int32_t cout, int32_t cin, int32_t ks, int32_t dtype) {
   const int cpg = dtype == ESR_F16 ? 16 : 8;

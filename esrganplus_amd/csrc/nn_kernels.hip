@@ -311,6 +311,36 @@ __global__ __launch_bounds__(256) void shuffle_kernel(const esr_pool p) {
   }
 }
 
+// The 3x pixel shuffle behind the folded nearest-x3 up-conv (esr_pool modes 4 / 5): out[b][c][3y+i][3x+j] =
+// in[b][(3i + j) C + c][y][x].  Phase-major: the high-resolution group g at the nine output pixels is the low-resolution
+// group (3i + j) C / CPG + g, whole — one thread per (low-res pixel, high-res group) copies nine 32-byte groups, and
+// writes image pixels only.  INV: the way back, gx <- g.
+template <typename T, bool INV>
+__global__ __launch_bounds__(256) void shuffle3_kernel(const esr_pool p) {
+  constexpr int CPG = DT<T>::CPG;
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  const int g = blockIdx.y, b = blockIdx.z, ng = p.C / CPG;
+  if (pix >= p.H * p.W) return;
+  const int y = pix / p.W, x = pix % p.W;
+  const esr_g32& lo = INV ? p.gx : p.x;
+  const esr_g32& hi = INV ? p.g : p.y;
+  u32x4 v[9][2];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    const char* s = INV ? (const char*)hi.ptr + pix_off(hi, b, g, 3 * y + q / 3, 3 * x + q % 3)
+                        : (const char*)lo.ptr + pix_off(lo, b, q * ng + g, y, x);
+    v[q][0] = *(const u32x4*)s;
+    v[q][1] = *(const u32x4*)(s + 16);
+  }
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    char* d = INV ? (char*)lo.ptr + pix_off(lo, b, q * ng + g, y, x)
+                  : (char*)hi.ptr + pix_off(hi, b, g, 3 * y + q / 3, 3 * x + q % 3);
+    *(u32x4*)d = v[q][0];
+    *(u32x4*)(d + 16) = v[q][1];
+  }
+}
+
 // y[b][o] = act(sum_i x[b][i] w[o][i] + bias[o]) — one block per (o, b)
 __global__ __launch_bounds__(256) void linear_fwd_kernel(const esr_linear p) {
   const int o = blockIdx.x, b = blockIdx.y;
@@ -448,6 +478,23 @@ extern "C" int esr_maxpool2(const esr_pool* p, esr_stream_t stream) {
       else hipLaunchKernelGGL((shuffle_kernel<float, true>), grid, block, 0, st, *p);
     } else { esr_set_error("esr_maxpool2: bad dtype"); return ESR_ERR_INVALID; }
     return esr_check_launch("shuffle_kernel");
+  }
+  if (p->mode == 4 || p->mode == 5) {
+    // 3x pixel shuffle / its adjoint: C = channels of the HIGH-resolution tensor, H x W = the LOW-resolution size
+    const esr_g32& lo = p->mode == 4 ? p->x : p->gx;
+    const esr_g32& hi = p->mode == 4 ? p->y : p->g;
+    if (p->C % cpg != 0 || !lo.ptr || !hi.ptr || lo.ngroups < 9 * (p->C / cpg) || hi.ngroups < p->C / cpg) {
+      esr_set_error("esr_maxpool2 (3x pixel shuffle): C must be a multiple of the channel group; x / gx hold 9 C channels, y / g hold C");
+      return ESR_ERR_INVALID;
+    }
+    if (p->dtype == ESR_F16) {
+      if (p->mode == 4) hipLaunchKernelGGL((shuffle3_kernel<_Float16, false>), grid, block, 0, st, *p);
+      else hipLaunchKernelGGL((shuffle3_kernel<_Float16, true>), grid, block, 0, st, *p);
+    } else if (p->dtype == ESR_F32) {
+      if (p->mode == 4) hipLaunchKernelGGL((shuffle3_kernel<float, false>), grid, block, 0, st, *p);
+      else hipLaunchKernelGGL((shuffle3_kernel<float, true>), grid, block, 0, st, *p);
+    } else { esr_set_error("esr_maxpool2: bad dtype"); return ESR_ERR_INVALID; }
+    return esr_check_launch("shuffle3_kernel");
   }
   if (p->dtype == ESR_F16) {
     if (p->mode == 0) hipLaunchKernelGGL((pool_kernel<_Float16, 0>), grid, block, 0, st, *p);

@@ -25,14 +25,28 @@ _STORE_FLAVOUR = int(os.environ.get('ESR_STORE_FLAVOUR', '0'))   # experiment kn
 _SIDE = L.OPF_SIDE if os.environ.get('ESR_SIDE', '1') != '0' else 0
 _SIDE_FREE = L.OPF_SIDE_FREE if os.environ.get('ESR_TAIL_WGRAD_FREE', '1') != '0' else 0     # (A/B knob, round 5)
 
+OFFSET_LIMIT = 2 ** 31    # bytes a 32-bit offset inside one image / one channel-group plane can span (G32.__init__)
+
+
 class G32:
     """[B][ngroups][Hp][Wp][cpg] activation buffer with a physical zero halo."""
 
-    def __init__(self, B, C_, H, W, dtype, device):
+    def __init__(self, B, C_, H, W, dtype, device, image_limit=False):
         self.esr_dtype, self.tdtype, self.cpg = _dt(dtype)
         self.B, self.C, self.H, self.W = B, C_, H, W
         self.ng = (C_ + self.cpg - 1) // self.cpg
         self.Hp, self.Wp = L.g32_dims(H, W)
+        # The kernels add the image's byte offset (b * batch_stride) in 64 bits, but inside an image some offsets are
+        # 32-bit: the conv kernels' staging map inside one channel-group plane (conv_mfma.hip: goff), the fp16
+        # weight-gradient kernel's across the groups of one image (wgrad.hip: soff / poff = group * group_stride + ...).
+        # Refused here, before anything is allocated: a plane (every plan) or — image_limit, the training plans, whose
+        # buffers the weight-gradient kernels read — one image's extent of OFFSET_LIMIT bytes or more.
+        extent = (self.ng if image_limit else 1) * self.Hp * self.Wp * 32
+        if extent >= OFFSET_LIMIT:
+            raise ValueError('a %d-channel %s buffer of %d x %d pixels spans %d bytes per %s: the kernels address %s with '
+                             '32-bit offsets (limit 2^31 bytes) — use a smaller image, or forward_tiled for x4 inference'
+                             % (C_, dtype, H, W, extent, 'image' if image_limit else 'channel-group plane',
+                                'one image' if image_limit else 'a plane'))
         self.t = torch.zeros(B, self.ng, self.Hp, self.Wp, self.cpg, dtype=self.tdtype, device=device)
         self.gs = self.Hp * self.Wp * 32
         self.bs = self.ng * self.gs
@@ -222,9 +236,9 @@ class Plan:
             self.ops.run(stream)
 
 
-def new_buf(bufs, B, C_, H, W, dtype, device):
+def new_buf(bufs, B, C_, H, W, dtype, device, image_limit=False):
     """A zeroed G32 buffer that the list `bufs` (a plan's or a backward pass's) keeps alive."""
-    b = G32(B, C_, H, W, dtype, device)
+    b = G32(B, C_, H, W, dtype, device, image_limit)
     bufs.append(b)
     return b
 
@@ -301,8 +315,12 @@ def tile_x8_op(ops, dt_e, B, C_, th, tw, to_g32, t_count, k_begin, k_count, g=No
 class Builder:
     """Emits the fused-conv sequence of RDB / RRDB / RRDBNet into a Plan."""
 
-    def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1, x8=None, tiled=None, tiled_x8=None):
+    image_limit = False           # G32's per-image offset bound (TrainBuilder: the weight-gradient kernels)
+
+    def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1, x8=None, tiled=None, tiled_x8=None,
+                 scale=4):
         self.wp = wp
+        self.scale = scale            # upscale of the generator: 1, 2, 4, 8 = 0..3 nearest-x2 up-convs, 3 = one folded x3
         self.B, self.H, self.W = B, H, W
         self.dt_e, self.tdtype, self.cpg = _dt(dtype)
         self.dtype = dtype
@@ -322,7 +340,7 @@ class Builder:
         self.tiled_x8 = tiled_x8
 
     def buf(self, C_, H=None, W=None):
-        return new_buf(self.bufs, self.B, C_, H or self.H, W or self.W, self.dtype, self.device)
+        return new_buf(self.bufs, self.B, C_, H or self.H, W or self.W, self.dtype, self.device, self.image_limit)
 
     def upload(self, table):
         t = upload_table(table, self.device)
@@ -504,24 +522,57 @@ class Builder:
         c.aux_out = fea.view(0, 64)
         self.plan.ops.add_conv(c)
 
+    def tail_keys(self):
+        """Keys of the convs behind the trunk, from the pack (= the module tree): (up-conv keys, HR_conv0, HR_conv1)."""
+        idx = sorted(int(k[6:]) for k in self.wp.entries if k.startswith('model.') and k[6:].isdigit() and int(k[6:]) >= 2)
+        keys = ['model.%d' % i for i in idx]
+        return keys[:-2], keys[-2], keys[-1]
+
+    def shuffle3(self, ops, z, u, H, W, inverse=False):
+        """esr_pool mode 4: u[c][3h+i][3w+j] = z[ch(c,i,j)][h][w] over H x W low-resolution pixels (64 channels of u, 576
+        of z), or mode 5, its adjoint z <- u."""
+        pl = L.esr_pool()
+        pl.dtype, pl.mode = self.dt_e, L.POOL_UNSHUFFLE3 if inverse else L.POOL_SHUFFLE3
+        pl.B, pl.C, pl.H, pl.W = self.B, 64, H, W
+        if inverse:
+            pl.x, pl.g, pl.gx = z.view(0, 576), u.view(0, 64), z.view(0, 576)
+        else:
+            pl.x, pl.y = z.view(0, 576), u.view(0, 64)
+        return ops.add(L.OP_POOL, 'pool', pl)
+
     def tail(self, x, fea, t, out_nc):
-        """LR_conv + trunk shortcut from the view x into t (None: a new buffer), 2 x (nearest x2 + conv + lrelu),
+        """LR_conv + trunk shortcut from the view x into t (None: a new buffer), the up-convs — n x (nearest x2 + conv +
+        lrelu) for x1 / x2 / x4 / x8, or for x3 the folded 64 -> 576 conv + lrelu on the LR grid and a 3x pixel shuffle —
         HR_conv0 + lrelu, HR_conv1 -> NCHW (architecture.py:66-78).  Returns the buffers the backward reads:
-        (T, U1, U2, U3)."""
+        (T, [outputs of the up-convs], U3 = HR_conv0's output)."""
         e = self.wp.entries
-        B, H, W, d = self.B, self.H, self.W, self.dt_e
+        B, H, W, d, s = self.B, self.H, self.W, self.dt_e, self.scale
         P = self.plan
+        ups, hr0, hr1 = self.tail_keys()
         t = self.buf(64) if t is None else t
         c = _conv(d, B, H, W, x, 64, t.view(0, 64), e['model.1.sub.%d' % self.nb])
         c.res1, c.alpha = fea.view(0, 64), 1.0
         P.ops.add_conv(c)
-        u1, u2, u3 = self.buf(64, 2 * H, 2 * W), self.buf(64, 4 * H, 4 * W), self.buf(64, 4 * H, 4 * W)
-        P.ops.add_conv(_conv(d, B, 2 * H, 2 * W, t.view(0), 64, u1.view(0, 64), e['model.3'], L.ACT_LRELU, upsample=1))
-        P.ops.add_conv(_conv(d, B, 4 * H, 4 * W, u1.view(0), 64, u2.view(0, 64), e['model.6'], L.ACT_LRELU, upsample=1))
-        P.ops.add_conv(_conv(d, B, 4 * H, 4 * W, u2.view(0), 64, u3.view(0, 64), e['model.8'], L.ACT_LRELU))
-        c = _conv(d, B, 4 * H, 4 * W, u3.view(0), 64, None, e['model.10'])
+        us, src, h, w = [], t, H, W
+        if s == 3:
+            self.Z3 = self.buf(576)
+            h, w = 3 * H, 3 * W
+            us.append(self.buf(64, h, w))
+            P.ops.add_conv(_conv(d, B, H, W, t.view(0), 64, self.Z3.view(0, 576), e[ups[0] + '#fold'], L.ACT_LRELU))
+            self.shuffle3(P.ops, self.Z3, us[0], H, W)
+            src = us[0]
+        else:
+            assert 2 ** len(ups) == s, (ups, s)
+            sizes = [(H << (i + 1), W << (i + 1)) for i in range(len(ups))]
+            us = [self.buf(64, hh, ww) for hh, ww in sizes]
+            for k, u, (h, w) in zip(ups, us, sizes):
+                P.ops.add_conv(_conv(d, B, h, w, src.view(0), 64, u.view(0, 64), e[k], L.ACT_LRELU, upsample=1))
+                src = u
+        u3 = self.buf(64, h, w)
+        P.ops.add_conv(_conv(d, B, h, w, src.view(0), 64, u3.view(0, 64), e[hr0], L.ACT_LRELU))
+        c = _conv(d, B, h, w, u3.view(0), 64, None, e[hr1])
         c.nchw_out_c = out_nc
-        P.out_shape = (B, out_nc, 4 * H, 4 * W)
+        P.out_shape = (B, out_nc, s * H, s * W)
         if self.tiled_x8 is not None:
             # tiled self-ensemble: HR_conv1 leaves the transformed windows' fp32 NCHW outputs in a buffer of the plan, and
             # the stitch-reduce undoes the transforms, sums and copies every tile's owned rectangle into the caller's tensor
@@ -549,13 +600,13 @@ class Builder:
             self.bufs.append(slots)
             c.nchw_out = slots.data_ptr()
             P.ops.add_conv(c)
-            P.out_op = dihedral_op(P.ops, d, n, out_nc, 4 * xh, 4 * xw, 0, B // n, slots=slots)
-            P.out_shape = (n, out_nc, 4 * xh, 4 * xw)
-        return t, u1, u2, u3
+            P.out_op = dihedral_op(P.ops, d, n, out_nc, s * xh, s * xw, 0, B // n, slots=slots)
+            P.out_shape = (n, out_nc, s * xh, s * xw)
+        return t, us, u3
 
     def rrdbnet(self, in_nc, out_nc, explicit_z):
-        """RRDBNet x4 (architecture.py:47-78): fea_conv, nb x RRDB, LR_conv + trunk shortcut,
-        2 x (nearest x2 + conv + lrelu), HR_conv0 + lrelu, HR_conv1."""
+        """RRDBNet (architecture.py:47-78): fea_conv, nb x RRDB, LR_conv + trunk shortcut, the up-convs of `scale`,
+        HR_conv0 + lrelu, HR_conv1."""
         B, H, W, nb = self.B, self.H, self.W, self.nb
         P = self.plan
         self.alloc_z(explicit_z)
@@ -786,8 +837,8 @@ def build_block_plan(kind, wp, B, H, W, dtype, device, noise, variant, explicit_
     return Builder(wp, B, H, W, dtype, device, noise, variant, kind).block_plan(explicit_z)
 
 
-def build_rrdbnet_plan(wp, nb, in_nc, out_nc, B, H, W, dtype, device, noise, variant, explicit_z):
-    return Builder(wp, B, H, W, dtype, device, noise, variant, 'net', nb).rrdbnet(in_nc, out_nc, explicit_z)
+def build_rrdbnet_plan(wp, nb, in_nc, out_nc, B, H, W, dtype, device, noise, variant, explicit_z, scale=4):
+    return Builder(wp, B, H, W, dtype, device, noise, variant, 'net', nb, scale=scale).rrdbnet(in_nc, out_nc, explicit_z)
 
 
 X8_SLOTS = (8, 4, 2, 1)
@@ -824,14 +875,14 @@ class X8Plan:
             self.bind_pass(k0).run(x, out, stream)
 
 
-def build_rrdbnet_x8_plan(wp, nb, in_nc, out_nc, B, H, W, dtype, device, variant, slots):
+def build_rrdbnet_x8_plan(wp, nb, in_nc, out_nc, B, H, W, dtype, device, variant, slots, scale=4):
     """Self-ensemble form of build_rrdbnet_plan (eval mode): the dihedral import in place of the NCHW import, the
     dihedral reduce behind HR_conv1, and between them the ops of the ordinary plan of batch slots x B."""
     plans = []
     for sh, sw in ([(H, W)] if H == W else [(H, W), (W, H)]):
-        b = Builder(wp, slots * B, sh, sw, dtype, device, False, variant, 'net', nb, x8=(B, H, W))
+        b = Builder(wp, slots * B, sh, sw, dtype, device, False, variant, 'net', nb, x8=(B, H, W), scale=scale)
         plans.append(b.rrdbnet(in_nc, out_nc, False))
-    return X8Plan(plans, slots, (B, out_nc, 4 * H, 4 * W))
+    return X8Plan(plans, slots, (B, out_nc, scale * H, scale * W))
 
 
 def tiled_geometry(H, W, tile, pad):
@@ -984,6 +1035,7 @@ class TrainPlan:
         self.bwd_streams = None      # RdbBwdStreams feeding them
         self.wgrad_arena = None      # partial sums of the deterministic weight-gradient reduction (attach_wgrad_arena)
         self.wgrad_free_arena = None   # the same for the free-running runs (attach_free_wgrad_regions)
+        self.scratch_grads = []      # fp32 gradient buffers outside grad_flat that the backward adds into: zeroed with it
         self.graph = False           # hipGraph replay with I/O bound to the static tensors below
         self.x_static = self.out_static = self.gy_static = self.gx_static = self.seed_t = None
 
@@ -1030,9 +1082,11 @@ class TrainBuilder(Builder):
     conv4 or the chain's LeakyReLU masks — and the matching backward list into a TrainPlan.  One method per step;
     build_rrdbnet_train_plan calls them in order."""
 
-    def __init__(self, wp, dp, nb, B, H, W, dtype, device, noise, variant, explicit_z, kind, segmented):
+    image_limit = True
+
+    def __init__(self, wp, dp, nb, B, H, W, dtype, device, noise, variant, explicit_z, kind, segmented, scale=4):
         self.block = kind != 'net'                  # stand-alone RRDB / dense block: no head / tail, dL/dx returned
-        super().__init__(wp, B, H, W, dtype, device, noise, variant, kind, 1 if self.block else nb)
+        super().__init__(wp, B, H, W, dtype, device, noise, variant, kind, 1 if self.block else nb, scale=scale)
         self.tp = TrainPlan()
         self.plan, self.bwd, self.bufs = self.tp.fwd, self.tp.bwd, self.tp.bufs
         self.dp = dp
@@ -1110,7 +1164,7 @@ class TrainBuilder(Builder):
             self.plan.out_op = self.export_nchw(self.XF, 64)
             self.plan.out_shape = (self.B, 64, self.H, self.W)
         else:
-            self.T, self.U1, self.U2, self.U3 = self.tail(self.XF.view(0), self.fea, None, out_nc)
+            self.T, self.Us, self.U3 = self.tail(self.XF.view(0), self.fea, None, out_nc)
 
     # ------------------------------------------------------------------ gradient storage
     def grad_store(self, net):
@@ -1165,16 +1219,17 @@ class TrainBuilder(Builder):
             self.tp.bwd_noise_ops.append(k)
         return k
 
-    def wgrad(self, key, g, gin, Hh, Ww, cout, cin, ks=3, ups=0, scale=1.0):
-        """The esr_wgrad of conv `key`: gradient view g, saved input view gin."""
+    def wgrad(self, key, g, gin, Hh, Ww, cout, cin, ks=3, ups=0, scale=1.0, dst=None):
+        """The esr_wgrad of conv `key`: gradient view g, saved input view gin.  dst: (dw, dbias) pointers of an OIHW
+        gradient outside the flat store (the folded x3 up-conv's: backward_tail)."""
         tm = self.tp.tapmajor
         wg = L.esr_wgrad()
         wg.dtype, wg.ks, wg.stride, wg.upsample = self.dt_e, ks, 1, ups
         wg.B, wg.H, wg.W = self.B, Hh, Ww
         wg.cout, wg.cin = cout, cin
         wg.g, wg.in_ = g, gin
-        wg.dw, wg.dbias = self.gptr[key]
-        if tm is not None and ks == 3:
+        wg.dw, wg.dbias = self.gptr[key] if dst is None else dst
+        if tm is not None and ks == 3 and dst is None:
             wg.dw, wg.tap_major = tm.slot(self.goff[key], cout, cin), 1
         wg.scale = scale
         return wg
@@ -1272,10 +1327,18 @@ class TrainBuilder(Builder):
             self.GY = self.buf(64)
             self.tp.gy_op = self.layout(self.bwd, self.GY, 64, 1)
         else:
-            self.GY = self.buf(out_nc, 4 * H, 4 * W)
+            s_ = self.scale
+            self.GY = self.buf(out_nc, s_ * H, s_ * W)
             self.tp.gy_op = self.layout(self.bwd, self.GY, out_nc, 1)
-            self.GA8, self.GA6 = self.buf(64, 4 * H, 4 * W), self.buf(64, 4 * H, 4 * W)
-            self.GA3 = self.buf(64, 2 * H, 2 * W)
+            # masked gradients at the outputs of HR_conv0 (x4: "GA8") and of every up-conv (x4: GA3, GA6)
+            self.GA_hr = self.buf(64, s_ * H, s_ * W)
+            self.GAs = [self.buf(64, u.H, u.W) for u in self.Us]
+            if s_ == 3:
+                # x3: the gradient of the folded conv's 576 outputs (the unshuffled GAs[0]) and, fp32 OIHW, the folded
+                # weight / bias gradient that esr_fold3 (mode 1) sums into the up-conv's slots of the flat store
+                self.G3 = self.buf(576)
+                self.DW3 = torch.zeros(576 * 64 * 9 + 576, dtype=torch.float32, device=self.device)
+                self.tp.scratch_grads.append(self.DW3)
             self.GTt = self.buf(64)                     # dL/dT (trunk output)
         # The six weight gradients of a block run on the side stream, concurrently with the NEXT block's
         # dgrad chain (both are latency-bound, ~64-workgroup launches at training sizes), and are joined
@@ -1314,26 +1377,48 @@ class TrainBuilder(Builder):
         """HR_conv1 .. LR_conv backwards: dL/dy -> the skip gradient and g_t of the last RRDB (nb = 0: dL/dfea)."""
         H, W, nb, ly = self.H, self.W, self.nb, self.layers
         dconv, add_b, wgrad = self.dconv, self.add_b, self.free_wgrad
-        T_, U1, U2, U3 = self.T, self.U1, self.U2, self.U3
-        GY, GA8, GA6, GA3, GTt = self.GY, self.GA8, self.GA6, self.GA3, self.GTt
-        # HR_conv1 (model.10): u3 -> y
-        wgrad('model.10', GY.view(0, out_nc), U3.view(0, 64), 4 * H, 4 * W, out_nc, 64)
-        c = dconv(4 * H, 4 * W, GY.view(0), out_nc, None, 'model.10')
-        c.mask, c.out2, c.mask_cb_begin = U3.view(0, 64), GA8.view(0, 64), 0
+        s_ = self.scale
+        ups, hr0, hr1 = self.tail_keys()
+        ins = [self.T] + self.Us                      # input of up-conv i (and, last, of HR_conv0)
+        GY, GA_hr, GAs, GTt, U3 = self.GY, self.GA_hr, self.GAs, self.GTt, self.U3
+        # HR_conv1: u3 -> y
+        wgrad(hr1, GY.view(0, out_nc), U3.view(0, 64), s_ * H, s_ * W, out_nc, 64)
+        c = dconv(s_ * H, s_ * W, GY.view(0), out_nc, None, hr1)
+        c.mask, c.out2, c.mask_cb_begin = U3.view(0, 64), GA_hr.view(0, 64), 0
         add_b(c)
-        # HR_conv0 (model.8): u2 -> u3 (lrelu)
-        wgrad('model.8', GA8.view(0, 64), U2.view(0, 64), 4 * H, 4 * W, 64, 64)
-        c = dconv(4 * H, 4 * W, GA8.view(0), 64, None, 'model.8')
-        c.mask, c.out2 = U2.view(0, 64), GA6.view(0, 64)
-        add_b(c)
-        # upconv 2 (model.6): up(u1) -> u2 ; adjoint = 4x4/s2 conv
-        wgrad('model.6', GA6.view(0, 64), U1.view(0, 64), 4 * H, 4 * W, 64, 64, ups=1)
-        c = dconv(2 * H, 2 * W, GA6.view(0), 64, None, 'model.6', ks=4, stride=2)
-        c.mask, c.out2 = U1.view(0, 64), GA3.view(0, 64)
-        add_b(c)
-        # upconv 1 (model.3): up(T) -> u1
-        wgrad('model.3', GA3.view(0, 64), T_.view(0, 64), 2 * H, 2 * W, 64, 64, ups=1)
-        add_b(dconv(H, W, GA3.view(0), 64, GTt.view(0, 64), 'model.3', ks=4, stride=2))
+        # HR_conv0: last up-conv's output (lrelu; x1: T, no activation) -> u3 (lrelu)
+        wgrad(hr0, GA_hr.view(0, 64), ins[-1].view(0, 64), s_ * H, s_ * W, 64, 64)
+        if self.Us:
+            c = dconv(s_ * H, s_ * W, GA_hr.view(0), 64, None, hr0)
+            c.mask, c.out2 = self.Us[-1].view(0, 64), GAs[-1].view(0, 64)
+            add_b(c)
+        else:
+            add_b(dconv(H, W, GA_hr.view(0), 64, GTt.view(0, 64), hr0))
+        if s_ == 3:
+            # folded up-conv: T -> Z3 (576, lrelu) -> shuffle3 -> us[0].  GAs[0] is already masked at 3H x 3W (lrelu
+            # commutes with the shuffle), so: its adjoint shuffle, the plain 576 <- 64 weight gradient into DW3, its
+            # unfold into the up-conv's own gradient slots, and the plain 576 -> 64 input-gradient conv
+            self.shuffle3(self.bwd, self.G3, GAs[0], H, W, inverse=True)
+            dw3 = (self.DW3.data_ptr(), self.DW3.data_ptr() + 4 * 576 * 64 * 9)
+            self.bwd.add(L.OP_WGRAD, 'wgrad', self.wgrad(ups[0], self.G3.view(0, 576), self.T.view(0, 64), H, W, 576, 64, dst=dw3))
+            f = L.esr_fold3()
+            f.mode, f.cout, f.cin = L.FOLD3_UNFOLD, 64, 64
+            f.wf, f.bf = dw3
+            f.w, f.bias = self.gptr[ups[0]]
+            self.bwd.add(L.OP_FOLD3, 'fold3', f)
+            add_b(dconv(H, W, self.G3.view(0), 576, GTt.view(0, 64), ups[0] + '#fold'))
+        for i in range(len(ups) - 1, -1, -1):
+            if s_ == 3:
+                break
+            # up-conv i: up(ins[i]) -> us[i] ; adjoint = 4x4/s2 conv
+            u = self.Us[i]
+            wgrad(ups[i], GAs[i].view(0, 64), ins[i].view(0, 64), u.H, u.W, 64, 64, ups=1)
+            if i > 0:
+                c = dconv(u.H // 2, u.W // 2, GAs[i].view(0), 64, None, ups[i], ks=4, stride=2)
+                c.mask, c.out2 = ins[i].view(0, 64), GAs[i - 1].view(0, 64)
+                add_b(c)
+            else:
+                add_b(dconv(H, W, GAs[0].view(0), 64, GTt.view(0, 64), ups[0], ks=4, stride=2))
         # LR_conv (model.1.sub.nb): XF -> T - fea
         lrk = 'model.1.sub.%d' % nb
         wgrad(lrk, GTt.view(0, 64), self.XF.view(0, 64), H, W, 64, 64)
@@ -1344,7 +1429,7 @@ class TrainBuilder(Builder):
             c.out = self.GF.view(0, 64)
             c.res1 = GTt.view(0, 64)                    # fea feeds both the trunk and the shortcut
         add_b(c, noisy=bool(nb))
-        self.close_segment([lrk, 'model.3', 'model.6', 'model.8', 'model.10'])
+        self.close_segment([lrk] + ups + [hr0, hr1])
 
     def backward_blocks(self):
         if self.fused_wgrad and not self.chained:
@@ -1534,7 +1619,7 @@ class TrainBuilder(Builder):
 
 
 def build_rrdbnet_train_plan(net, wp, dp, nb, in_nc, out_nc, B, H, W, dtype, device, noise, variant,
-                             explicit_z, kind='net', segmented=False):
+                             explicit_z, kind='net', segmented=False, scale=4):
     """RRDBNet forward keeping every RDB concat buffer (+ pre-residual activations of conv2/conv4,
     whose signs are the LeakyReLU masks) and the backward pass:
       * input gradients = the same fused conv kernel over transposed/rotated weights, with the
@@ -1545,7 +1630,7 @@ def build_rrdbnet_train_plan(net, wp, dp, nb, in_nc, out_nc, B, H, W, dtype, dev
     segmented ('net' only): the backward list records, per RRDB (and for the tail / the first conv), the op
     index after which that slice of the flat gradient buffer is final — data-parallel runs start its
     all-reduce there, under the rest of the backward (TrainPlan.segments, functional._train_backward)."""
-    bld = TrainBuilder(wp, dp, nb, B, H, W, dtype, device, noise, variant, explicit_z, kind, segmented)
+    bld = TrainBuilder(wp, dp, nb, B, H, W, dtype, device, noise, variant, explicit_z, kind, segmented, scale)
     bld.forward_head(in_nc)
     if bld.chained:
         bld.forward_blocks_chain()

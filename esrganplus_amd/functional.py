@@ -113,6 +113,8 @@ def _train_backward(tp, gy, st, noise, explicit, seed, want_gx, sync=None, prepa
         tp.grad_flat.zero_()
         if tp.tapmajor is not None:
             tp.tapmajor.tm.zero_()
+        for t in tp.scratch_grads:
+            t.zero_()
     if tp.graph:
         tp.gy_static.copy_(gy)
         if tp.bwd_streams is not None:
@@ -233,7 +235,8 @@ def _train_plan(net, wp, dp, B, H, W, dev, noise, explicit):
             tp.packs = (wp, dp)
             return tp
     tp = E.build_rrdbnet_train_plan(net, wp, dp, net.nb, net.in_nc, net.out_nc, B, H, W,
-                                    net.precision, dev, noise, net.variant, explicit, segmented=sync is not None)
+                                    net.precision, dev, noise, net.variant, explicit, segmented=sync is not None,
+                                    scale=net.upscale)
     if not explicit and E.use_graphs() and sync is None:
         tp.enable_graph((B, net.in_nc, H, W), dev)
     # The launch lists hold RAW pointers into the packed operands: the plan keeps the packs alive.  An autograd graph
@@ -350,6 +353,8 @@ def rrdbnet_train_prepare(net, s):
     tp.grad_flat.zero_()
     if tp.tapmajor is not None:
         tp.tapmajor.tm.zero_()
+    for t in tp.scratch_grads:
+        t.zero_()
     if tp.bwd_streams is not None:
         tp.bwd_streams.ensure(E.current_stream())
     s.prepared = True
@@ -429,7 +434,7 @@ def run_rrdbnet(net, x, z=None):
     """RRDBNet.forward (architecture.py:76-78) on the HIP path."""
     if x.dim() == 4 and x.shape[0] == 0:          # empty batch: torch returns an empty result
         E.require_cuda(x, 'input')
-        return x.new_zeros((0, net.out_nc, 4 * x.shape[2], 4 * x.shape[3]), dtype=torch.float32)
+        return x.new_zeros((0, net.out_nc, net.upscale * x.shape[2], net.upscale * x.shape[3]), dtype=torch.float32)
     if _needs_grad(net, x):
         E.require_cuda(x, 'input')
         B, C_, H, W = x.shape
@@ -462,7 +467,7 @@ def run_rrdbnet(net, x, z=None):
         if len(net._plans) >= net.max_cached_plans:
             net._plans.clear()
         plan = E.build_rrdbnet_plan(wp, net.nb, net.in_nc, net.out_nc, B, H, W, net.precision,
-                                    xin.device, noise, net.variant, zs is not None)
+                                    xin.device, noise, net.variant, zs is not None, scale=net.upscale)
         net._plans[key] = plan
     out = torch.empty(plan.out_shape, dtype=torch.float32, device=xin.device)
     plan.run(xin, out, E.current_stream(), _draw_seed() if (noise and zs is None) else 0, zs)
@@ -516,14 +521,14 @@ def run_rrdbnet_x8(net, x, slots_per_pass=None):
     batched launch plans: the eight flip / transpose copies of ``x`` are written straight into the plan's input buffer,
     run as one batch of 8 B (non-square input: 4 B at H x W, then 4 B at W x H), and the inverse transforms and the mean
     are one reduce into the result.  Noise is off whatever ``net.training`` is (the reference calls ``eval()`` first); the
-    module's mode and every ``requires_grad`` are left untouched; the result [B, out_nc, 4H, 4W] fp32 carries no
-    gradient.  B > 1 is ensembled PER IMAGE (the reference's ``cat`` + ``mean(dim=0)`` would also average across the
+    module's mode and every ``requires_grad`` are left untouched; the result [B, out_nc, sH, sW] fp32 (s = the net's
+    ``upscale``) carries no gradient.  B > 1 is ensembled PER IMAGE (the reference's ``cat`` + ``mean(dim=0)`` would also average across the
     images and is only meaningful at B = 1).  slots_per_pass (8, 4, 2 or 1; default ESR_X8_SLOTS, else 8 for square and 4
     for non-square input) bounds the memory of large images: each pass runs slots x B copies.  Every pass still holds
     whole-image plans; ``run_rrdbnet_tiled_x8`` is the ensemble per window, with the memory of a tiled forward."""
     if x.dim() == 4 and x.shape[0] == 0:
         E.require_cuda(x, 'input')
-        return x.new_zeros((0, net.out_nc, 4 * x.shape[2], 4 * x.shape[3]), dtype=torch.float32)
+        return x.new_zeros((0, net.out_nc, net.upscale * x.shape[2], net.upscale * x.shape[3]), dtype=torch.float32)
     xin = _prep_input(x, 'input')
     B, C_, H, W = xin.shape
     if C_ != net.in_nc:
@@ -538,7 +543,7 @@ def run_rrdbnet_x8(net, x, slots_per_pass=None):
         if len(net._plans) >= net.max_cached_plans:
             net._plans.clear()
         plan = E.build_rrdbnet_x8_plan(wp, net.nb, net.in_nc, net.out_nc, B, H, W, net.precision, xin.device,
-                                       net.variant, slots)
+                                       net.variant, slots, scale=net.upscale)
         net._plans[key] = plan
     out = torch.empty(plan.out_shape, dtype=torch.float32, device=xin.device)
     plan.run(xin, out, E.current_stream())

@@ -42,8 +42,15 @@ class _Pack:
     FULL_CHECK_EVERY = 64     # calls between full pointer comparisons (an unsampled parameter re-pointed by hand:
     #                            `p.data = t`, per-layer re-init, load_state_dict(assign=True))
 
-    def __init__(self, dtype, device, specs, watch):
+    def __init__(self, dtype, device, specs, watch, folds=()):
         # specs: (key, cout, cin, ks, packed bytes) of every entry, in arena order
+        # folds: (key, weight, bias or None) of nearest-x3 up-convs: the pack holds their folded form (esr_fold3: fp32
+        # [9 cout, cin, 3, 3] + [9 cout]) as a derived tensor, refreshed by the launch list of every re-pack in front of
+        # the pack launch, and packs it as entry key + '#fold'
+        self.folded = {}
+        for key, w, b in folds:
+            self.folded[key] = (w, b, torch.zeros((9 * w.shape[0],) + tuple(w.shape[1:]), dtype=torch.float32, device=device),
+                                torch.zeros(9 * w.shape[0], dtype=torch.float32, device=device) if b is not None else None)
         self.esr_dtype, self.tdtype, self.cpg = _dt(dtype)
         self.device = device
         self.arena = torch.zeros(sum(s[4] for s in specs), dtype=torch.uint8, device=device)
@@ -83,6 +90,12 @@ class _Pack:
             if ptrs != self._ptrs:
                 bp, self._pack_keep = L.batch_pack_op(self._packs(), self.device)
                 self.ops = L.OpList()                      # ONE launch re-packs every conv of the network
+                for w, b, wf, bf in self.folded.values():
+                    f = L.esr_fold3()
+                    f.mode, f.cout, f.cin = L.FOLD3_FOLD, w.shape[0], w.shape[1]
+                    f.w, f.bias, f.wf, f.bf = w.data_ptr(), b.data_ptr() if b is not None else None, wf.data_ptr(), \
+                        bf.data_ptr() if bf is not None else None
+                    self.ops.add(L.OP_FOLD3, 'fold3', f)
                 self.ops.add(L.OP_PACK_BATCH, 'pack_batch', bp)
                 self.generation += 1
                 self._ptrs = ptrs
@@ -101,10 +114,12 @@ class WeightPack(_Pack):
     """Forward operands of a module's convs; biases are read from the parameters themselves, except those of convs with
     cout % 32 != 0, which are copied into a padded arena behind every re-pack."""
 
-    def __init__(self, convs, dtype, device, subpix=()):
+    def __init__(self, convs, dtype, device, subpix=(), folds=()):
         # convs: list of (key, weight_param, bias_param_or_None); subpix: keys of up-convs (nearest x2 + 3x3,
         # block.py:315-322) packed in the 4-phase 2x2 form (esr_pack.ups_fwd, run with esr_conv.upsample = 3)
+        # folds: keys of nearest-x3 up-convs, also packed in their folded form as key + '#fold' (_Pack.__init__)
         dt_e = _dt(dtype)[0]
+        folds = [c for c in convs if c[0] in frozenset(folds)]
         self.subpix, self.convs = frozenset(subpix), convs
         specs = []
         for key, w, b in convs:
@@ -114,7 +129,9 @@ class WeightPack(_Pack):
             else:
                 nbytes = L.packed_weight_bytes(cout, cin, ks, dt_e)
             specs.append((key, cout, cin, ks, nbytes))
-        super().__init__(dtype, device, specs, [p for _, w, b in convs for p in (w, b) if p is not None])
+        specs += [(key + '#fold', 9 * w.shape[0], w.shape[1], 3, L.packed_weight_bytes(9 * w.shape[0], w.shape[1], 3, dt_e))
+                  for key, w, b in folds]
+        super().__init__(dtype, device, specs, [p for _, w, b in convs for p in (w, b) if p is not None], folds)
         nb_pad = sum(((w.shape[0] + 31) // 32) * 32 for _, w, b in convs if b is not None and w.shape[0] % 32)
         self.bias_arena = torch.zeros(max(nb_pad, 1), dtype=torch.float32, device=device)
         self._bias_copies = []
@@ -139,6 +156,10 @@ class WeightPack(_Pack):
             packs.append(self._pack_op(w, e.w_ptr, e.ks, ups_fwd=1 if e.subpix else 0))
             if b is not None and e.cout % 32 == 0:
                 e.bias_ptr = b.data_ptr()
+        for key, (w, b, wf, bf) in self.folded.items():
+            e = self.entries[key + '#fold']
+            packs.append(self._pack_op(wf, e.w_ptr, 3))
+            e.has_bias, e.bias_ptr = bf is not None, bf.data_ptr() if bf is not None else None
         return packs
 
     def _after_pack(self):
@@ -152,8 +173,9 @@ class DgradPack(_Pack):
     degrees (esr_pack.transpose_flip); conv5 of an RDB additionally folds the x4->x2 identity path
     (block.py:266) into its x2 output slice, and the upconvs get the 4x4/stride-2 adjoint kernel."""
 
-    def __init__(self, convs, dtype, device, special, gathers=()):
+    def __init__(self, convs, dtype, device, special, gathers=(), folds=()):
         # convs: list of (key, weight_param); special: key -> dict(sum=(dst,src,count)) / dict(ups=True)
+        # folds: keys of nearest-x3 up-convs: the transposed operand of their folded form (9 cout -> cin) as key + '#fold'
         # gathers: gather-form operands of a dense block (include/esrgan_hip.h: esr_pack.gather), each
         # (key, dst_cout, [(weight, src_co0, scale[, fold_co0]), ...]) — K = the pieces' forward couts, in order — or,
         # for the transposed 1x1 of the backward chain, (key, 'one_t', conv1x1.weight) — 4 KB of fragments
@@ -166,9 +188,11 @@ class DgradPack(_Pack):
         specs = [(key, w.shape[1], w.shape[0], 4 if special.get(key, {}).get('ups') else w.shape[2]) for key, w in convs]
         specs += [(key, dst_cout, sum(pc[0].shape[0] for pc in pieces), 3) for key, dst_cout, pieces in self.gathers]
         specs += [(key, 64, 32, 1) for key, _, w in self.ones]
+        folds = [(key, w, None) for key, w in convs if key in frozenset(folds)]
+        specs += [(key + '#fold', w.shape[1], 9 * w.shape[0], 3) for key, w, _ in folds]
         watch = ([w for _, w in convs] + [pc[0] for _, _, pieces in self.gathers for pc in pieces]
                  + [w for _, _, w in self.ones])
-        super().__init__(dtype, device, [s + (L.packed_weight_bytes(*s[1:], dt_e),) for s in specs], watch)
+        super().__init__(dtype, device, [s + (L.packed_weight_bytes(*s[1:], dt_e),) for s in specs], watch, folds)
 
     def ensure(self, stream, force=True, record_sig=False):
         """force=True: training nets, whose weights change every optimizer step.  force=False (a frozen eval-mode net,
@@ -196,6 +220,8 @@ class DgradPack(_Pack):
             if 'sum' in sp:
                 pk.sum_dst, pk.sum_src, pk.sum_count = sp['sum']
             packs.append(pk)
+        for key, (w, b, wf, bf) in self.folded.items():
+            packs.append(self._pack_op(wf, self.entries[key + '#fold'].w_ptr, 3, transpose_flip=1))
         return packs
 
 

@@ -46,8 +46,12 @@ def _conv(sd, seed, key, cout, cin, k, bias=True, gain=1.0):
         sd[key + '.bias'] = _uniform(seed, key + '.bias', (cout,), 1.0 / np.sqrt(fan_in))
 
 
-def rrdbnet_keys(nb):
-    """(key-prefix, cout, cin, k, bias) for every conv of RRDBNet x4, in state-dict order."""
+# conv indices behind the trunk (block.sequential flattens [Upsample, conv, lrelu] per up-conv, then HR_conv0, lrelu, HR_conv1)
+RRDBNET_TAIL = {1: (2, 4), 2: (3, 5, 7), 3: (3, 5, 7), 4: (3, 6, 8, 10), 8: (3, 6, 9, 11, 13)}
+
+
+def rrdbnet_keys(nb, upscale=4):
+    """(key-prefix, cout, cin, k, bias) for every conv of RRDBNet at `upscale`, in state-dict order."""
     out = [('model.0', 64, 3, 3, True)]
     for i in range(nb):
         for j in (1, 2, 3):
@@ -57,14 +61,14 @@ def rrdbnet_keys(nb):
                 out.append((p + '.conv%d.0' % k, 32, 64 + 32 * (k - 1), 3, True))
             out.append((p + '.conv5.0', 64, 192, 3, True))
     out.append(('model.1.sub.%d' % nb, 64, 64, 3, True))
-    out += [('model.3', 64, 64, 3, True), ('model.6', 64, 64, 3, True),
-            ('model.8', 64, 64, 3, True), ('model.10', 3, 64, 3, True)]
+    tail = RRDBNET_TAIL[upscale]
+    out += [('model.%d' % i, 64, 64, 3, True) for i in tail[:-1]] + [('model.%d' % tail[-1], 3, 64, 3, True)]
     return out
 
 
-def rrdbnet_state_dict(nb=23, seed=0, gain=1.0):
+def rrdbnet_state_dict(nb=23, seed=0, gain=1.0, upscale=4):
     sd = OrderedDict()
-    for key, cout, cin, k, bias in rrdbnet_keys(nb):
+    for key, cout, cin, k, bias in rrdbnet_keys(nb, upscale):
         _conv(sd, seed, key, cout, cin, k, bias, gain)
     return sd
 

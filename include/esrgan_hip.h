@@ -384,7 +384,13 @@ typedef struct esr_bn {
  * Round 5 — the same struct carries nn.PixelShuffle(2) (pixelshuffle_block, block.py:299-312; SRResNet's upsampler):
  * mode 2: y[b][c][2h+i][2w+j] = x[b][4c + 2i + j][h][w]   (C = channels of y, H x W = size of x; C % channel group == 0)
  * mode 3: its adjoint, gx[b][4c + 2i + j][h][w] = g[b][c][2h+i][2w+j], with relu_mask: times ReLU'(x) of the conv that
- *         produced x (the activation behind the shuffle commutes with it, so it rides in the conv's epilogue). */
+ *         produced x (the activation behind the shuffle commutes with it, so it rides in the conv's epilogue).
+ * Added under ABI 6 (a pure addition) — the 3x pixel shuffle behind the folded nearest-x3 up-conv (esr_fold3):
+ * mode 4: y[b][c][3h+i][3w+j] = x[b][(3i + j) C + c][h][w]   (C = channels of y, H x W = size of x; C % channel group == 0;
+ *         x has 9 C channels).  Phase-major channel order — not torch's PixelShuffle(3) — so that a thread moves whole
+ *         32-byte channel groups in either precision; only image pixels of y are written, never its zero ring.
+ * mode 5: its exact adjoint, gx[b][(3i + j) C + c][h][w] = g[b][c][3h+i][3w+j]  (relu_mask is ignored: the activation's
+ *         mask is applied at high resolution by the consumer's input-gradient conv). */
 typedef struct esr_pool {
   int32_t dtype, mode;
   int32_t B, C, H, W;           /* OUTPUT (pooled) size */
@@ -645,12 +651,30 @@ typedef struct esr_rdb_wgrad {
   int32_t _pad;
 } esr_rdb_wgrad;
 
+/* Nearest-x3 up-sampling followed by a zero-padded 3x3 conv (upconv_blcok with upscale_factor 3, block.py:315-322) IS a
+ * zero-padded 3x3 conv on the low-resolution grid to 9 cout channels followed by the 3x pixel shuffle of esr_pool mode 4:
+ * output phase p in {0,1,2} along an axis reads, for tap k in {0,1,2}, the low-resolution offset off(p,k) =
+ * floor((p + k - 1) / 3), i.e. (-1,0,0), (0,0,0), (0,0,+1).
+ * mode 0 (fold):   wf[(3p+q) cout + co][ci][a][b] = sum of w[co][ci][kh][kw] over the taps with off(p,kh) = a - 1 and
+ *                  off(q,kw) = b - 1, added in (kh, kw) order in fp32 (1 to 4 terms; 0 where no tap lands);
+ *                  bf[(3p+q) cout + co] = bias[co].
+ * mode 1 (unfold): the adjoint, for gradients: w[co][ci][kh][kw] = sum over (p, q) in order of
+ *                  wf[(3p+q) cout + co][ci][off(p,kh)+1][off(q,kw)+1];  bias[co] = sum over (p, q) of bf[(3p+q) cout + co].
+ * All tensors fp32 OIHW; bias / bf may both be NULL. */
+typedef struct esr_fold3 {
+  int32_t mode, cout, cin, _pad;
+  float* w;      /* [cout][cin][3][3]: read by mode 0, written by mode 1 */
+  float* bias;   /* [cout] */
+  float* wf;     /* [9 cout][cin][3][3]: written by mode 0, read by mode 1 */
+  float* bf;     /* [9 cout] */
+} esr_fold3;
+
 enum esr_op_kind { ESR_OP_CONV = 1, ESR_OP_PACK = 2, ESR_OP_LAYOUT = 3, ESR_OP_NOISE_FILL = 4,
                    ESR_OP_WGRAD = 5, ESR_OP_BN = 6, ESR_OP_POOL = 7, ESR_OP_LINEAR = 8,
                    ESR_OP_UNPERMUTE = 9, ESR_OP_PACK_BATCH = 10,
                    ESR_OP_RDB_CHAIN = 11, ESR_OP_FRAG_GATHER = 12, ESR_OP_RDB_WGRAD = 13,
                    ESR_OP_RDB_CHAIN_BWD = 14 /* u.rdb_chain with mode 2 */, ESR_OP_DIHEDRAL = 15,
-                   ESR_OP_TILE = 16, ESR_OP_TILE_X8 = 17 };
+                   ESR_OP_TILE = 16, ESR_OP_TILE_X8 = 17, ESR_OP_FOLD3 = 18 };
 
 /* esr_op.flags */
 #define ESR_OPF_SIDE 1   /* on a run of consecutive ESR_OP_WGRAD ops: launch the run on the library's side
@@ -695,6 +719,7 @@ typedef struct esr_op {
     esr_dihedral dihedral;
     esr_tile tile;
     esr_tile_x8 tile_x8;
+    esr_fold3 fold3;
   } u;
 } esr_op;
 
@@ -709,6 +734,7 @@ int esr_fill_noise(const esr_noise_fill* p, esr_stream_t stream);
 int esr_dihedral_op(const esr_dihedral* p, esr_stream_t stream);   /* added under ABI 6: a pure addition */
 int esr_tile_op(const esr_tile* p, esr_stream_t stream);           /* added under ABI 6: a pure addition */
 int esr_tile_x8_op(const esr_tile_x8* p, esr_stream_t stream);     /* added under ABI 6: a pure addition */
+int esr_fold3_op(const esr_fold3* p, esr_stream_t stream);         /* added under ABI 6: a pure addition */
 int esr_conv_wgrad(const esr_wgrad* p, esr_stream_t stream);
 /* n independent weight-gradient problems (disjoint dw/dbias blocks).  fp16 3x3/s1 and 1x1 entries are
  * packed, up to 8 at a time, into ONE launch (at training sizes a single conv's wgrad is ~64
@@ -811,7 +837,7 @@ int esr_graph_destroy(esr_graph_t g);
 int esr_run_ops_timed(const esr_op* ops, int32_t n, esr_stream_t stream, float* ms_out);
 
 const char* esr_last_error(void);
-int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE and esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8 were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
+int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8, and esr_fold3 / esr_fold3_op / ESR_OP_FOLD3 with esr_pool modes 4 / 5 were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
                                 esr_l1_loss, esr_ragan_loss, ESR_OPF_SIDE_FREE) */
 size_t esr_sizeof_op(void);
 

@@ -1,14 +1,16 @@
 #!/usr/bin/env python
 """Inference harness reproducing the reference's ``test_image/test.py`` (lines 9-40) on the HIP path
-with PIL instead of cv2:  python tools/sr_infer.py <model.pth|synthetic> <in_dir> <out_dir> [fp16|fp32] [--x8] [--tile N[,PAD]] [--tile-x8 N[,PAD]]
+with PIL instead of cv2:  python tools/sr_infer.py <model.pth|synthetic> <in_dir> <out_dir> [fp16|fp32] [--scale S] [--x8] [--tile N[,PAD]] [--tile-x8 N[,PAD]]
 
 Per image: RGB /255 -> NCHW float32 -> RRDB_Net(3,3,64,23,...) -> clamp(0,1) -> *255 round -> PNG.
+--scale S (also --scale=S; 1, 2, 3, 4 or 8, default 4): the ``upscale`` the network is built with.
 --x8: the geometric self-ensemble (the reference's ``SRModel.test_x8``, codes/models/SR_model.py:82-120) in place of the
 plain forward: ``model.forward_x8``.
 --tile N[,PAD] (also --tile=N[,PAD]): the tiled forward ``model.forward_tiled(x, tile=N, pad=PAD)`` (PAD defaults to the
 method's): one launch plan for a folder of images of any size, bounded memory; not combined with --x8.
 --tile-x8 N[,PAD] (also --tile-x8=N[,PAD]): the tiled self-ensemble ``model.forward_tiled_x8(x, tile=N, pad=PAD)``: the
-ensemble per window, with the tiled forward's bounded memory and shared plan; not combined with --x8 or --tile."""
+ensemble per window, with the tiled forward's bounded memory and shared plan; not combined with --x8 or --tile.
+The tiled forms are x4-only: with another --scale the script exits with the library's message."""
 import glob
 import os
 import sys
@@ -38,6 +40,15 @@ def main():
                     sys.exit('sr_infer.py: %s takes N or N,PAD (LR pixels), got %r' % (flag, val))
                 break
     tiled, tiled_x8 = tiles['--tile'], tiles['--tile-x8']
+    scale = 4
+    for i, a in enumerate(argv):
+        if a == '--scale' or a.startswith('--scale='):
+            val = a[len('--scale='):] if '=' in a else ''.join(argv[i + 1:i + 2])
+            del argv[i:i + (1 if '=' in a else 2)]
+            if val not in ('1', '2', '3', '4', '8'):
+                sys.exit('sr_infer.py: --scale takes 1, 2, 3, 4 or 8, got %r' % val)
+            scale = int(val)
+            break
     if tiled and x8:
         sys.exit('sr_infer.py: --tile and --x8 cannot be combined: the tiled self-ensemble is --tile-x8 N[,PAD]')
     if tiled_x8 and (x8 or tiled):
@@ -45,9 +56,14 @@ def main():
     model_path, in_dir, out_dir = argv[0], argv[1], argv[2]
     prec = argv[3] if len(argv) > 3 else 'fp32'
     dev = torch.device('cuda')
-    model = arch.RRDB_Net(3, 3, 64, 23, gc=32, upscale=4, norm_type=None, act_type='leakyrelu',
+    model = arch.RRDB_Net(3, 3, 64, 23, gc=32, upscale=scale, norm_type=None, act_type='leakyrelu',
                           mode='CNA', res_scale=1, upsample_mode='upconv')
-    sd = synth.rrdbnet_state_dict(23, 0) if model_path == 'synthetic' else torch.load(model_path, map_location='cpu')
+    if tiled or tiled_x8:
+        try:
+            model._x4_only('--tile-x8' if tiled_x8 else '--tile')      # the library's own refusal, before anything is loaded
+        except ValueError as e:
+            sys.exit('sr_infer.py: %s' % e)
+    sd = synth.rrdbnet_state_dict(23, 0, upscale=scale) if model_path == 'synthetic' else torch.load(model_path, map_location='cpu')
     model.load_state_dict(sd, strict=False)           # test_image/test.py:17
     model.eval()
     for _, v in model.named_parameters():
