@@ -220,6 +220,14 @@ class esr_ragan_loss(C.Structure):
                 ('grad_scale_dev', C.c_void_p)]
 
 
+class esr_gan_loss(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('y', C.c_void_p), ('grad_x', C.c_void_p), ('grad_y', C.c_void_p),
+                ('loss', C.c_void_p), ('term_x', C.c_void_p), ('term_y', C.c_void_p),
+                ('mean_x', C.c_void_p), ('mean_y', C.c_void_p), ('grad_scale_dev', C.c_void_p),
+                ('n_x', C.c_int32), ('n_y', C.c_int32), ('tx', C.c_float), ('ty', C.c_float),
+                ('kind', C.c_int32), ('weight', C.c_float), ('grad_scale', C.c_float), ('_pad', C.c_int32)]
+
+
 class esr_img_metrics(C.Structure):
     _fields_ = [('sr', C.c_void_p), ('hr', C.c_void_p), ('C', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
                 ('crop', C.c_int32), ('y_only', C.c_int32), ('_pad', C.c_int32), ('lo', C.c_float), ('hi', C.c_float),
@@ -266,7 +274,7 @@ EXPORTS = ['esr_packed_weight_bytes', 'esr_g32_dims', 'esr_conv_forward', 'esr_p
            'esr_l1_loss_forward', 'esr_ragan_loss_forward', 'esr_rdb_wgrad_run', 'esr_rdb_wgrad_workspace_elems', 'esr_rdb_backward',
            'esr_rdb_mask_bytes', 'esr_rdb_check_abort', 'esr_debug_hold_cus', 'esr_debug_device_alias', 'esr_debug_chain_order_waits',
            'esr_debug_mfma_probe', 'esr_debug_rdb_wgrad_follow', 'esr_dihedral_op', 'esr_tile_op',
-           'esr_tile_x8_op', 'esr_l2_loss_forward', 'esr_fold3_op']
+           'esr_tile_x8_op', 'esr_l2_loss_forward', 'esr_fold3_op', 'esr_gan_loss_forward']
 
 _lib = None
 _lock = threading.Lock()
@@ -326,7 +334,7 @@ def lib():
                          ('esr_pack_conv_weights_batch', esr_pack_batch), ('esr_rdb_forward', esr_rdb_chain),
                          ('esr_gather_fragments', esr_frag_gather), ('esr_image_metrics', esr_img_metrics),
                          ('esr_l1_loss_forward', esr_l1_loss), ('esr_l2_loss_forward', esr_l1_loss),
-                         ('esr_ragan_loss_forward', esr_ragan_loss),
+                         ('esr_ragan_loss_forward', esr_ragan_loss), ('esr_gan_loss_forward', esr_gan_loss),
                          ('esr_rdb_wgrad_run', esr_rdb_wgrad), ('esr_rdb_backward', esr_rdb_chain),
                          ('esr_dihedral_op', esr_dihedral), ('esr_tile_op', esr_tile),
                          ('esr_tile_x8_op', esr_tile_x8), ('esr_fold3_op', esr_fold3)):

@@ -13,7 +13,8 @@ Appendix B).  What the reference does around them lives here:
   behind whatever a pipelined step left in flight, plus — new, the reference trains in fp32 — the dynamic loss
   scaler's state, so that a resumed fp16 run continues bit for bit (tests/test_gpu_train_step.py).  A step without a
   discriminator (``train.PSNRStep``, the reference's SRModel) writes and reads ``{step}_G.pth`` / ``{step}.state``
-  with one optimizer entry."""
+  with one optimizer entry.  A step with an iteration counter (``train.SRGANStep``: its ``D_update_ratio`` /
+  ``D_init_iters`` schedule runs on it) gets it back from the ``iter`` of the ``.state`` file."""
 from collections import OrderedDict
 
 import torch
@@ -108,4 +109,7 @@ def resume_step(step, directory, iter_step, schedulers=()):
                           'static loss scale): the dynamic loss scale restarts from its initial value, so the first '
                           'steps after the resume are not bit-identical to the uninterrupted run' % iter_step,
                           RuntimeWarning, stacklevel=2)
+    if hasattr(step, 'iteration'):
+        # train.SRGANStep: its update schedule (D_update_ratio / D_init_iters) runs on the iteration count
+        step.iteration = int(state['iter'])
     return state['epoch'], state['iter']

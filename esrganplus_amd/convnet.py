@@ -97,6 +97,7 @@ class SeqPlan(BwdPass):
         self.restat = None              # OpList replaying the BatchNorm running-statistics updates (dual plans)
         self.fwd_half = self.restat1 = None  # split_forward_groups: [group 0, group 1] forward lists over a pair's halves, and
                                              # the running-statistics update the early half owes
+        self.restat0 = None             # group0_restat: the running-statistics update of ONE more call on group 0
         self.own_dp = self.own_head = None   # per-call weights: this plan's own input-gradient pack / head weights
         self.graph, self.x_static = False, None      # hipGraph replay, the input staged in x_static
         self.packs = self.keep_x = None      # kept alive with the plan: the (WeightPack, DgradPack) the lists point into,
@@ -594,6 +595,24 @@ def split_forward_groups(P, n):
         st.sums = st.sums + 2 * st.C * 8
         restat1.ops.append(o)
     P.fwd_half, P.restat1 = halves, restat1
+
+
+def group0_restat(P, n):
+    """The launch list (built once, kept in ``P.restat0``) that gives the BatchNorm buffers of a two-group dual plan
+    (batch 2n) the momentum update of ONE more forward call over group 0 with unchanged weights — the standard-GAN step's
+    third netD call (SRGAN_model.py:129, 140, 143: fake, real, fake; the forward did the first two).  Copies of
+    ``P.restat``'s launches as ``split_forward_groups`` makes ``restat1``, on group 0: B = n, groups = 1, the sums left
+    at group 0's rows; ``num_batches_tracked`` goes up by one per layer."""
+    if P.restat0 is None:
+        ops = L.OpList()
+        for i in range(len(P.restat.ops)):
+            o = L.esr_op.from_buffer_copy(P.restat.array()[i])
+            st = o.u.bn
+            assert o.kind == L.OP_BN and st.groups == 2 and st.B == 2 * n
+            st.B, st.groups = n, 1
+            ops.ops.append(o)
+        P.restat0 = ops
+    return P.restat0
 
 
 def _begin_pass(Q, gx_ptr, accumulate):

@@ -145,6 +145,61 @@ __global__ __launch_bounds__(256) void ragan_loss_kernel(const esr_ragan_loss p)
   }
 }
 
+// GANLoss.forward (loss.py:6-38) on one or two operands, the standard-GAN step's criterion (SRGAN_model.py:129-146):
+//   kind 0 (vanilla)  l(x, t) = mean_i [ max(x_i, 0) - x_i t + log1p(exp(-|x_i|)) ]   d/dx_i = (sigmoid(x_i) - t) / n
+//   kind 1 (lsgan)    l(x, t) = mean_i (x_i - t)^2                                      d/dx_i = 2 (x_i - t) / n
+// loss = weight * (l(x, tx) [+ l(y, ty)]); the gradients carry weight * grad_scale [* grad_scale_dev[0]].  One
+// workgroup (n is the discriminator's batch); the elements are formed in fp32, their sums run in fp64 (lsgan: the
+// square too, exact there).  exp(-|x|) <= 1 and the sigmoid is formed from it on either side of 0: nothing overflows.
+// No scratch: every output is written once, by thread 0.
+template <bool LS>
+__global__ __launch_bounds__(256) void gan_loss_kernel(const esr_gan_loss p) {
+  __shared__ double red[4][4];
+  const float kw = LS ? 2.f * p.weight : p.weight;
+  const float gs = p.grad_scale != 0.f ? p.grad_scale : 1.f, gsd = p.grad_scale_dev ? *p.grad_scale_dev : 1.f;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};          // sum l(x_i), sum x_i, sum l(y_i), sum y_i
+  for (int side = 0; side < 2; ++side) {
+    const float* v = side ? p.y : p.x;
+    if (!v) continue;
+    const int n = side ? p.n_y : p.n_x;
+    const float t = side ? p.ty : p.tx;
+    float* g = side ? p.grad_y : p.grad_x;
+    const float gw = kw / (float)n * gs * gsd;
+    double l = 0.0, s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+      const float x = v[i];
+      s += x;
+      if (LS) {
+        const float d = x - t;
+        l += (double)d * (double)d;
+        if (g) g[i] = gw * d;
+      } else {
+        const float e = expf(-fabsf(x));
+        l += fmaxf(x, 0.f) - x * t + log1pf(e);
+        if (g) g[i] = gw * ((x >= 0.f ? 1.f : e) / (1.f + e) - t);
+      }
+    }
+    acc[2 * side] = l;
+    acc[2 * side + 1] = s;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_down(acc[k], o);
+  if ((threadIdx.x & 63) == 0)
+    for (int k = 0; k < 4; ++k) red[threadIdx.x >> 6][k] = acc[k];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot[4];
+    for (int k = 0; k < 4; ++k) tot[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+    const double lx = tot[0] / (double)p.n_x, ly = p.y ? tot[2] / (double)p.n_y : 0.0;
+    *p.loss = (float)(lx + ly) * p.weight;
+    if (p.term_x) *p.term_x = (float)lx;
+    if (p.term_y) *p.term_y = (float)ly;
+    if (p.mean_x) *p.mean_x = (float)(tot[1] / (double)p.n_x);
+    if (p.mean_y) *p.mean_y = p.y ? (float)(tot[3] / (double)p.n_y) : 0.f;
+  }
+}
+
 }  // namespace
 
 template <bool L2>
@@ -175,4 +230,16 @@ extern "C" int esr_ragan_loss_forward(const esr_ragan_loss* p, esr_stream_t stre
   }
   hipLaunchKernelGGL(ragan_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *p);
   return esr_check_launch("ragan_loss_kernel");
+}
+
+extern "C" int esr_gan_loss_forward(const esr_gan_loss* p, esr_stream_t stream) {
+  if (!p || !p->x || p->n_x < 1 || (p->y && p->n_y < 1) || (p->kind != 0 && p->kind != 1) || !p->loss) {
+    esr_set_error("esr_gan_loss_forward: invalid arguments");
+    return ESR_ERR_INVALID;
+  }
+  if (p->kind == 1)
+    hipLaunchKernelGGL(gan_loss_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, *p);
+  else
+    hipLaunchKernelGGL(gan_loss_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, *p);
+  return esr_check_launch("gan_loss_kernel");
 }

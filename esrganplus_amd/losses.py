@@ -1,6 +1,7 @@
 """The ESRGAN+ train step's losses as single launches (csrc/loss_kernels.hip): ``nn.L1Loss`` / ``nn.MSELoss`` (cri_pix /
 cri_fea 'l1' / 'l2', SRRaGAN_model.py:31-53,124-131; SR_model.py:28-34) and the relativistic-average GAN term built from ``GANLoss('vanilla')``
-(codes/models/modules/loss.py:6-38; SRRaGAN_model.py:133-137, 150-156).  Each forward launch also produces the
+(codes/models/modules/loss.py:6-38; SRRaGAN_model.py:133-137, 150-156), and ``GANLoss`` itself ('vanilla' / 'lsgan'
+against a constant label: SRGAN_model.py:129-146).  Each forward launch also produces the
 gradient w.r.t. its differentiable operands; backward is one multiply by the upstream scalar.
 
 Same numbers as the torch formulas (tests/test_gpu_losses.py).  No fallback: operands the kernels do not cover (CPU
@@ -265,3 +266,114 @@ def ragan_loss(x, y, x_is_real, y_is_real, weight=1.0, global_mean=False):
     _require(x.numel() == y.numel(), 'ragan_loss: %d vs %d logits' % (x.numel(), y.numel()))
     fn = _RaGANGlobalFn if global_mean else _RaGANFn
     return fn.apply(x, y, 1.0 if x_is_real else 0.0, 1.0 if y_is_real else 0.0, float(weight))
+
+
+# ---- GANLoss (codes/models/modules/loss.py:6-38): the standard-GAN criterion of SRGAN_model.py --------------------
+GAN_KINDS = {'vanilla': 0, 'lsgan': 1}
+
+
+def gan_kind(gan_type):
+    """The kernel's `kind` of the reference's ``gan_type`` (lowered as GANLoss.__init__ lowers it)."""
+    name = str(gan_type).lower()
+    if name in GAN_KINDS:
+        return GAN_KINDS[name]
+    if name == 'wgan-gp':
+        raise NotImplementedError('GAN type [wgan-gp] is not supported: its gradient penalty needs a double backward '
+                                  'through the discriminator, which the planned networks do not have')
+    raise NotImplementedError('GAN type [{:s}] is not found'.format(name))
+
+
+def _gan_launch(x_, y_, tx, ty, kind, weight, gx, gy, grad_scale, scale_dev):
+    dev = x_.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    aux = torch.empty(4, dtype=torch.float32, device=dev)         # term_x, term_y, mean_x, mean_y
+    p = L.esr_gan_loss()
+    p.x, p.n_x, p.tx = x_.data_ptr(), x_.numel(), float(tx)
+    if y_ is not None:
+        p.y, p.n_y, p.ty = y_.data_ptr(), y_.numel(), float(ty)
+    p.kind, p.weight, p.loss = kind, float(weight), loss.data_ptr()
+    p.term_x, p.term_y, p.mean_x, p.mean_y = (aux.data_ptr() + 4 * i for i in range(4))
+    p.grad_x = gx.data_ptr() if gx is not None else None
+    p.grad_y = gy.data_ptr() if gy is not None else None
+    _scale_args(p, grad_scale, scale_dev)
+    L.check(L.lib().esr_gan_loss_forward(C.byref(p), C.c_void_p(E.current_stream())), 'esr_gan_loss_forward')
+    return loss, aux
+
+
+def gan_raw(x, x_is_real, gan_type, weight, grad_x=None, y=None, y_is_real=None, grad_y=None, grad_scale=1.0,
+            scale_dev=None, real_label_val=1.0, fake_label_val=0.0):
+    """``GANLoss(gan_type, real_label_val, fake_label_val)`` without autograd, one launch: ``(loss, aux)`` with
+    ``loss = weight * (l(x, x_is_real) [+ l(y, y_is_real)])`` and ``aux = [term_x, term_y, mean_x, mean_y]`` (the
+    unweighted terms and the logits' means; zeros for an absent ``y``).  The gradients w.r.t. the logits, times ``weight
+    * grad_scale [* scale_dev[0]]``, are written into ``grad_x`` / ``grad_y`` (contiguous fp32 of the operand's size;
+    None: not formed).  The two operands may differ in size."""
+    kind = gan_kind(gan_type)
+    x_ = x.detach().contiguous().view(-1)
+    y_ = y.detach().contiguous().view(-1) if y is not None else None
+    _check_operands('gan_raw', *((x_,) if y_ is None else (x_, y_)))
+    _require(x_.numel() >= 1 and (y_ is None or y_.numel() >= 1), 'gan_raw: an operand without elements')
+    _require(y_ is None or y_is_real is not None, 'gan_raw: y without y_is_real')
+    for name, g, t in (('grad_x', grad_x, x_), ('grad_y', grad_y, y_)):
+        if g is not None:
+            _require(t is not None and g.is_cuda and g.is_contiguous() and g.dtype == torch.float32
+                     and g.numel() == t.numel(), 'gan_raw: ' + name)
+    label = lambda real: real_label_val if real else fake_label_val
+    return _gan_launch(x_, y_, label(x_is_real), label(y_is_real) if y_ is not None else 0.0, kind, weight,
+                       grad_x, grad_y if y_ is not None else None, grad_scale, scale_dev)
+
+
+class _GANFn(torch.autograd.Function):
+    """The autograd face of esr_gan_loss_forward: y may be None (one operand)."""
+
+    @staticmethod
+    def forward(ctx, x, y, tx, ty, kind, weight):
+        x_ = x.detach().contiguous().view(-1)
+        y_ = y.detach().contiguous().view(-1) if y is not None else None
+        gx = torch.empty_like(x_) if ctx.needs_input_grad[0] else None
+        gy = torch.empty_like(y_) if y_ is not None and ctx.needs_input_grad[1] else None
+        loss, aux = _gan_launch(x_, y_, tx, ty, kind, weight, gx, gy, 1.0, None)
+        ctx.g = (gx, gy, x.shape, y.shape if y is not None else None)
+        ctx.mark_non_differentiable(aux)
+        return loss, aux
+
+    @staticmethod
+    def backward(ctx, g, _unused):
+        gx, gy, sx, sy = ctx.g
+        return ((gx * g).view(sx) if gx is not None else None, (gy * g).view(sy) if gy is not None else None,
+                None, None, None, None)
+
+
+def gan_pair_loss(x, x_is_real, y, y_is_real, gan_type='vanilla', weight=1.0, real_label_val=1.0, fake_label_val=0.0):
+    """``weight * (GANLoss(x, x_is_real) + GANLoss(y, y_is_real))`` as ONE launch with autograd — the D step's
+    ``l_d_real + l_d_fake`` (SRGAN_model.py:140-146).  Returns ``(loss, aux)``, aux as ``gan_raw``, detached."""
+    kind = gan_kind(gan_type)
+    x, y = _as_f32(x), _as_f32(y)
+    _check_operands('gan_pair_loss', x, y)
+    _require(x.numel() >= 1 and y.numel() >= 1, 'gan_pair_loss: an operand without elements')
+    label = lambda real: float(real_label_val if real else fake_label_val)
+    return _GANFn.apply(x, y, label(x_is_real), label(y_is_real), kind, float(weight))
+
+
+def gan_loss(x, target_is_real, gan_type='vanilla', weight=1.0, real_label_val=1.0, fake_label_val=0.0):
+    """``weight * GANLoss(gan_type, real_label_val, fake_label_val)(x, target_is_real)``: one launch that also forms the
+    gradient; backward is one multiply.  fp16 / bf16 logits are upcast."""
+    kind = gan_kind(gan_type)
+    x = _as_f32(x)
+    _check_operands('gan_loss', x)
+    _require(x.numel() >= 1, 'gan_loss: an operand without elements')
+    t = float(real_label_val if target_is_real else fake_label_val)
+    return _GANFn.apply(x, None, t, 0.0, kind, float(weight))[0]
+
+
+class GANLoss(torch.nn.Module):
+    """The reference's ``GANLoss`` (loss.py:6-38) over the fused kernel: same constructor, same ``forward(input,
+    target_is_real)`` — a loop written against the reference keeps its ``self.cri_gan`` line."""
+
+    def __init__(self, gan_type, real_label_val=1.0, fake_label_val=0.0):
+        super().__init__()
+        self.gan_type = str(gan_type).lower()
+        gan_kind(self.gan_type)
+        self.real_label_val, self.fake_label_val = real_label_val, fake_label_val
+
+    def forward(self, input, target_is_real):
+        return gan_loss(input, target_is_real, self.gan_type, 1.0, self.real_label_val, self.fake_label_val)

@@ -14,6 +14,7 @@ Launch economy (the step is a few thousand small launches): each network sees it
 gradients (``losses``), and the D step is enqueued on a second stream under the G backward (one GPU and
 data-parallel alike: the step that is measured on one GPU is the step that scales).
 """
+import contextlib
 import os
 
 import torch
@@ -743,3 +744,352 @@ class PSNRStep:
         """The optimizer's state (base_model.py:65-74 `save_training_state`), behind whatever is still in flight."""
         self.finish()
         return {'optimizers': [self.optimizer_G.state_dict()]}
+
+
+class SRGANStep:
+    """The standard-GAN step — ``SRGANModel.optimize_parameters`` (codes/models/SRGAN_model.py:113-178) with the set-up
+    of its constructor (SRGAN_model.py:29-98; codes/options/train/train_SRGAN.json): optional pixel and feature terms
+    ('l1' / 'l2'; a weight <= 0 removes the term and its log key, and ``netF`` may then be None), ``GANLoss(gan_type)``
+    ('vanilla' / 'lsgan') against constant labels, Adam for G and D with optional weight decay, and the update schedule
+    of ``D_update_ratio`` / ``D_init_iters``: G moves when ``iteration % D_update_ratio == 0 and iteration >
+    D_init_iters``, D every iteration.  ``iteration`` counts from 1 (the reference passes ``current_step``); left out, an
+    internal counter supplies it, which ``state_dict()`` carries and ``checkpoint.resume_step`` restores.
+
+    netD's BatchNorm buffers see the reference's calls in the reference's order: fake, real, fake on a G-update
+    iteration (three momentum updates, ``num_batches_tracked`` + 3), real, fake otherwise.
+
+    Hand-driven form (an ``RRDBNet`` generator with flat gradients, every parameter training — ``_manual_ok``): the
+    networks' launch lists driven directly.  On a G-update iteration netD runs ONCE over [fake; real] (the dual plan of
+    ``ESRGANPlusStep``): its second pass gives dL/d fake_H for G, its own pass D's parameter gradients, and the third
+    call's buffer update is a replay on group 0 (``convnet.group0_restat``); the loss kernels write their gradients
+    straight into the buffers the backward lists read.  Other iterations: the noise-on forward without saved
+    activations and ``netD.forward_pair(var_ref, fake)``.  Autograd form (every other generator — ``SRResNet``, the
+    generator of train_SRGAN.json —, a frozen parameter, ESR_TRAIN_MANUAL=0): the reference's three netD calls.
+
+    Data-parallel: the losses are per-sample means, so per-rank losses and the averaged gradients reproduce the global
+    batch's step; no scalar crosses the ranks.  The logged ``l_*`` / ``D_real`` / ``D_fake`` are this rank's means."""
+
+    def __init__(self, netG, netD, netF=None, lr_G=1e-4, lr_D=1e-4, beta1_G=0.9, beta1_D=0.9,
+                 weight_decay_G=0, weight_decay_D=0, pixel_weight=1e-2, feature_weight=1.0, gan_weight=5e-3,
+                 pixel_criterion='l1', feature_criterion='l1', gan_type='vanilla',
+                 D_update_ratio=1, D_init_iters=0, loss_scale=1.0, data_parallel=None):
+        self.netG, self.netD = netG, netD
+        self.l_pix_w = pixel_weight if pixel_weight and pixel_weight > 0 else 0
+        self.l_fea_w = feature_weight if feature_weight and feature_weight > 0 else 0
+        self.l_gan_w = gan_weight
+        self._pix_raw, self._pix_loss = LS.criterion(pixel_criterion) if self.l_pix_w else (None, None)
+        self._fea_raw, self._fea_loss = LS.criterion(feature_criterion) if self.l_fea_w else (None, None)
+        if self.l_fea_w and netF is None:
+            raise ValueError('SRGANStep: feature_weight > 0 needs netF')
+        self.netF = netF if self.l_fea_w else None
+        self.gan_type = str(gan_type).lower()
+        LS.gan_kind(self.gan_type)                # refuses 'wgan-gp' and unknown names
+        self.D_update_ratio = int(D_update_ratio) if D_update_ratio else 1
+        self.D_init_iters = int(D_init_iters) if D_init_iters else 0
+        self.data_parallel = DP.active() if data_parallel is None else bool(data_parallel)
+        self.scaler = None
+        if loss_scale == 'dynamic':
+            self.scaler = DynamicLossScaler(next(netG.parameters()).device)
+            loss_scale = 1.0
+        self.loss_scale = loss_scale
+        self.optimizer_G = FusedAdam([p for p in netG.parameters() if p.requires_grad], lr=lr_G,
+                                     betas=(beta1_G, 0.999), weight_decay=weight_decay_G if weight_decay_G else 0)
+        self.optimizer_D = FusedAdam(netD.parameters(), lr=lr_D, betas=(beta1_D, 0.999),
+                                     weight_decay=weight_decay_D if weight_decay_D else 0)
+        self.exG = DP.GradExchange(netG, enabled=self.data_parallel, measure=self.data_parallel)
+        self.exD = DP.GradExchange(netD, enabled=self.data_parallel, measure=self.data_parallel)
+        self.log = {}
+        self.fake_H = None
+        self.iteration = 0                 # iterations done (the next default `iteration` is this + 1)
+        self._steps = 0
+        self._gy = self._gy2 = self._ev_tail = self._scale_tensor = self._scale_value = None
+        self._g_log = {}                   # the last G update's l_g_* (the reference's log_dict keeps them)
+        self.overlap = ESRGANPlusStep._knob_int('ESR_TRAIN_OVERLAP', '1', (0, 1))
+        self.manual = os.environ.get('ESR_TRAIN_MANUAL', '1') != '0'
+
+    _scale_t = ESRGANPlusStep._scale_t
+    _side = ESRGANPlusStep._side
+    _defer_networks = ESRGANPlusStep._defer_networks
+    comm_reset = ESRGANPlusStep.comm_reset
+    comm_report = ESRGANPlusStep.comm_report
+    finish = ESRGANPlusStep.finish
+
+    @staticmethod
+    def g_update_due(iteration, D_update_ratio=1, D_init_iters=0):
+        """SRGAN_model.py:119: does the generator move at this iteration (counted from 1)?"""
+        return iteration % D_update_ratio == 0 and iteration > D_init_iters
+
+    def _manual_ok(self):
+        netG, netD, netF = self.netG, self.netD, self.netF
+        return (self.manual and getattr(netD, '_shared_ok', False) and netD.training
+                and not getattr(netD, '_per_call_weights', False)
+                and getattr(netG, 'flat_param_grads', False) and hasattr(netG, '_convs')
+                and (netF is None or hasattr(netF, '_run_forward'))
+                and all(p.requires_grad for p in netG._convs()[1]) and all(p.requires_grad for p in netD.parameters()))
+
+    def state_dict(self):
+        """The two optimizers' states (base_model.py:65-74) and the iteration counter, behind whatever is in flight."""
+        self.finish()
+        return {'optimizers': [self.optimizer_G.state_dict(), self.optimizer_D.state_dict()], 'iter': self.iteration}
+
+    def test(self, var_L):
+        """``SRGANModel.test`` (SRGAN_model.py:180-184): the eval forward without gradient; the generator is back in
+        training mode afterwards.  Valid between pipelined steps."""
+        E.require_cuda(var_L, 'SRGANStep.test: var_L')
+        self.netG.eval()
+        try:
+            with torch.no_grad():
+                self.fake_H = self.netG(var_L)
+        finally:
+            self.netG.train()
+        return self.fake_H
+
+    # ---- the two forms ----
+    def _adam(self, update_g):
+        """Both forms' tail: the optimizer steps behind their exchanges, the scaler's update, the weight packs."""
+        inv = 1.0 / self.loss_scale
+        if update_g:
+            self.exG.wait()
+            self.optimizer_G.step(grad_scale=inv, scaler=self.scaler)
+        self.exD.wait()
+        self.optimizer_D.step(grad_scale=inv, scaler=self.scaler)
+        if self.scaler:
+            self.scaler.update()
+        if update_g and hasattr(self.netG, 'prepack'):
+            self.netG.prepack(fwd=True, dgrad=True)
+        if hasattr(self.netD, 'prepack'):
+            self.netD.prepack()
+
+    def _generator(self, var_L, z):
+        return self.netG(var_L, z=z) if z is not None else self.netG(var_L)
+
+    def _step_manual(self, var_L, var_H, var_ref, z, update_g, sync_log):
+        """One iteration over the networks' launch lists; returns the device scalars (g_terms, aux).
+        With a side stream (ESR_TRAIN_OVERLAP=1, default) a G-update iteration runs, next to the main stream's chain
+        generator forward - pixel loss - netD forward - GAN loss - netD's G-step pass - generator backward - Adam(G):
+        netF(real), the backward's preliminaries and netD's `real` half under the generator's forward; netF(fake) with
+        the feature loss and its input-gradient pass next to netD's forward; the D step under the generator's backward;
+        Adam(D) and the weight packs only the next backward / netD forward read behind it (`_ev_tail`)."""
+        netG, netD, netF = self.netG, self.netD, self.netF
+        S = float(self.loss_scale)
+        sdev = self.scaler.state if self.scaler else None
+        if not update_g:
+            # nothing of G moves: the noise-on forward without saved activations; the D step as two calls in one pass,
+            # all on the caller's stream (the networks' entry points join what the last iteration left on the side stream)
+            with torch.no_grad():
+                fake = self.fake_H = self._generator(var_L, z)
+            aux = self._d_step_autograd(var_ref, fake, self.scaler.scale if self.scaler else self._scale_t(fake.device))
+            self._adam(False)
+            return {}, aux
+        n = var_L.shape[0]
+        main = torch.cuda.current_stream()
+        side = self._side(var_L.device) if self.overlap >= 1 else None
+        if not netG.mark_grads_stale():
+            self.optimizer_G.zero_grad(set_to_none=True)
+        g = {}
+        box = {}
+
+        def d_step():
+            # SRGAN_model.py:137-160: netD(real) and netD(fake.detach()) are groups 1 and 0 of the iteration's ONE pass;
+            # the first is the second call (its values, its buffer update), the second a THIRD call on unchanged weights
+            PD, out = box['PD'], box['out']
+            st = E.current_stream()
+            if box['early'] and PD.restat1.ops:
+                PD.restat1.run(st)                           # the update the early `real` half still owes (call two)
+            if PD.restat is not None and PD.restat.ops:
+                CN.group0_restat(PD, n).run(st)              # call three: fake again
+            gyt = PD.gy_tensor.view(-1)                      # plan order [fake; real]
+            _, box['aux'] = LS.gan_raw(out[n:], True, self.gan_type, 1.0, grad_x=gyt[n:], y=out[:n], y_is_real=False,
+                                       grad_y=gyt[:n], grad_scale=S, scale_dev=sdev)
+            CN.run_pass_into(PD)
+            CN.bind_param_grads(PD, netD)
+            self.exD.start()
+
+        def on_side(fn):
+            if side is None:
+                return fn()
+            with torch.cuda.stream(side):
+                return fn()
+
+        with torch.no_grad():
+            if side is not None:
+                ev0 = torch.cuda.Event()
+                ev0.record(main)                  # the inputs, and whatever the last iteration left on this stream
+            fake, stG = Fn.rrdbnet_train_forward(netG, var_L, z)
+            self.fake_H = fake
+            # ---- what does not depend on the generator: on the side stream under its forward ----
+            real_fea = ev_prep = d_early = None
+            if side is not None:
+                side.wait_event(ev0)
+                with torch.cuda.stream(side):
+                    if self.l_fea_w:
+                        real_fea = netF._run_forward(var_H, need_bwd=False)[0]
+                    Fn.rrdbnet_train_prepare(netG, stG)
+                    ev_prep = torch.cuda.Event()
+                    ev_prep.record(side)
+                    if netD._has_bn and not E.use_graphs():
+                        # netD(real): the last iteration's D-side tail (Adam, packs) sits on this stream, in front of it
+                        var_ref.record_stream(side)
+                        d_early = netD._pair_begin(var_ref) + (torch.cuda.Event(),)
+                        d_early[2].record(side)
+            else:
+                Fn.rrdbnet_train_prepare(netG, stG)
+                if self.l_fea_w:
+                    real_fea = netF._run_forward(var_H, need_bwd=False)[0]
+            # ---- pixel loss: writes dL/d fake_H's buffer ----
+            gy = self._gy = _buffer_like(self._gy, fake)
+            if self.l_pix_w:
+                g['l_g_pix'] = self._pix_raw(fake, var_H, self.l_pix_w, grad_out=gy, grad_scale=S, scale_dev=sdev)
+            if side is not None:
+                ev_fake = torch.cuda.Event()
+                ev_fake.record(main)
+            # ---- ONE netD forward for the iteration's three calls: groups (0 = fake, 1 = real) are calls one and two ----
+            if self._ev_tail is not None:
+                main.wait_event(self._ev_tail)    # the last iteration's D step, D's Adam and packs (side stream)
+            if d_early is not None:
+                PD, leaseD = d_early[0], d_early[1]
+                main.wait_event(d_early[2])
+                out = netD._pair_finish(PD, fake)
+            else:
+                netD._join_pending()
+                out, leaseD = netD._run_forward(torch.cat([fake, var_ref]), need_bwd=True,
+                                                groups=2 if netD._has_bn else 1, dual=n)
+                PD = leaseD.plan
+            box.update(PD=PD, out=out, early=d_early is not None)
+            g['l_g_gan'], _ = LS.gan_raw(out[:n], True, self.gan_type, self.l_gan_w, grad_x=PD.second.gy_tensor,
+                                         grad_scale=S, scale_dev=sdev)
+            # ---- netF(fake), the feature loss and its input-gradient pass: next to netD's forward ----
+            leaseF = ev_f = None
+            if self.l_fea_w:
+                def netf_fake():
+                    fake_fea, lease = netF._run_forward(fake, need_bwd=True)
+                    g['l_g_fea'] = self._fea_raw(fake_fea, real_fea, self.l_fea_w, grad_out=lease.plan.gy_tensor,
+                                                 grad_scale=S, scale_dev=sdev)
+                    return lease
+                if side is not None:
+                    self._gy2 = _buffer_like(self._gy2, fake)
+                    side.wait_event(ev_fake)
+                    fake.record_stream(side)
+                    with torch.cuda.stream(side):
+                        leaseF = netf_fake()
+                        CN.run_pass_into(leaseF.plan, gx_into=self._gy2, accumulate=False)
+                        ev_f = torch.cuda.Event()
+                        ev_f.record(side)
+                else:
+                    leaseF = netf_fake()
+            if side is not None:
+                out.record_stream(side)
+                side.wait_stream(main)            # all the D step waits for: netD's forward (not the passes below)
+            # ---- dL/d fake_H: the pixel loss wrote the buffer (or nobody did); the passes' last layout ops add into it ----
+            CN.run_pass_into(PD.second, gx_into=gy, accumulate=bool(self.l_pix_w))
+            if ev_f is not None:
+                main.wait_event(ev_f)
+                gy.add_(self._gy2)
+            elif leaseF is not None:
+                CN.run_pass_into(leaseF.plan, gx_into=gy, accumulate=True)
+            # the D step: under the generator's backward on the side stream — enqueued behind it by a loop that reads
+            # nothing (the host then feeds the main stream first), in front of it by one that waits for the log
+            if side is not None and sync_log:
+                on_side(d_step)
+            if ev_prep is not None:
+                main.wait_event(ev_prep)
+            Fn.rrdbnet_train_backward(netG, stG, gy)
+            self.exG.start()
+            if side is None or not sync_log:
+                on_side(d_step)
+            if leaseF is not None:
+                leaseF.release()
+            leaseD.release()
+            # ---- the tail ----
+            if side is None or self.scaler is not None:
+                if side is not None:
+                    main.wait_stream(side)
+                self._adam(True)
+                self._ev_tail = None
+            else:
+                inv = 1.0 / self.loss_scale
+                self.exG.wait()
+                self.optimizer_G.step(grad_scale=inv, scaler=None)
+                netG.prepack(fwd=True, dgrad=False)          # what the next forward starts with
+                side.wait_stream(main)                       # G's new weights (its input-gradient packs read them)
+                with torch.cuda.stream(side):
+                    self.exD.wait()
+                    self.optimizer_D.step(grad_scale=inv, scaler=None)
+                    netD.prepack()
+                    netG.prepack(fwd=False, dgrad=True)
+                    self._ev_tail = torch.cuda.Event()
+                    self._ev_tail.record(side)
+                self._defer_networks(self._ev_tail)
+                if sync_log:                                 # the default call: everything ordered on the current stream
+                    main.wait_event(self._ev_tail)
+        return g, box['aux']
+
+    def _d_step_autograd(self, var_ref, fake, scale):
+        """SRGAN_model.py:137-160 as the reference calls it: netD(real), netD(fake.detach()) — one pass, BatchNorm
+        statistics per call —, ``l_d_real + l_d_fake`` as one loss launch, backward; returns `aux`."""
+        netD = self.netD
+        for p in netD.parameters():
+            p.requires_grad = True
+        self.optimizer_D.zero_grad(set_to_none=True)
+        with torch.enable_grad():
+            pred_d_real, pred_d_fake = netD.forward_pair(var_ref, fake.detach())
+            l_d_total, aux = LS.gan_pair_loss(pred_d_real, True, pred_d_fake, False, self.gan_type, 1.0)
+        torch.autograd.backward([l_d_total], [scale])
+        self.exD.start()
+        return aux
+
+    def _step_autograd(self, var_L, var_H, var_ref, z, update_g, sync_log):
+        netG, netD, netF = self.netG, self.netD, self.netF
+        if not (hasattr(netG, 'mark_grads_stale') and netG.mark_grads_stale()):
+            self.optimizer_G.zero_grad(set_to_none=True)
+        g = {}
+        if update_g:
+            for p in netD.parameters():                   # G's pass through netD: parameters frozen
+                p.requires_grad = False
+            fake_H = self.fake_H = self._generator(var_L, z)
+            scale = self.scaler.scale if self.scaler else self._scale_t(fake_H.device)
+            if self.l_pix_w:
+                g['l_g_pix'] = self._pix_loss(fake_H, var_H, self.l_pix_w)
+            if self.l_fea_w:
+                fake_fea, real_fea = netF.forward_pair(fake_H, var_H)
+                g['l_g_fea'] = self._fea_loss(fake_fea, real_fea.detach(), self.l_fea_w)
+            g['l_g_gan'] = LS.gan_loss(netD(fake_H), True, self.gan_type, self.l_gan_w)
+            terms = list(g.values())
+            torch.autograd.backward(terms, [scale] * len(terms))
+            self.exG.start()
+            with netD.weights_unchanged() if hasattr(netD, 'weights_unchanged') else contextlib.nullcontext():
+                aux = self._d_step_autograd(var_ref, fake_H, scale)
+        else:
+            with torch.no_grad():
+                fake_H = self.fake_H = self._generator(var_L, z)
+            aux = self._d_step_autograd(var_ref, fake_H, self.scaler.scale if self.scaler else self._scale_t(fake_H.device))
+        self._adam(update_g)
+        return {k: v.detach() for k, v in g.items()}, aux
+
+    def step(self, var_L, var_H, var_ref=None, z=None, sync_log=True, iteration=None):
+        """One iteration (SRGAN_model.py:113-178).  sync_log=False: the pipelined form — the logged values stay device
+        tensors and nothing waits for the host (the next step, ``finish()`` and a device synchronisation order what is
+        in flight)."""
+        E.require_cuda(var_L, 'SRGANStep.step: var_L')        # (the networks and the fused losses have no CPU path)
+        var_ref = var_H if var_ref is None else var_ref
+        it = self.iteration + 1 if iteration is None else int(iteration)
+        self.iteration = it
+        self._steps += 1
+        update_g = self.g_update_due(it, self.D_update_ratio, self.D_init_iters)
+        form = self._step_manual if self._manual_ok() else self._step_autograd
+        g, aux = form(var_L, var_H, var_ref, z, update_g, sync_log)
+        # the log: G's entries only change when G moves (log_dict keeps the last ones); aux = l_d_real, l_d_fake, D_real, D_fake
+        vals = dict(g)
+        vals.update(zip(('l_d_real', 'l_d_fake', 'D_real', 'D_fake'), aux.unbind(0)))
+        if sync_log:
+            keys = list(vals)
+            host = torch.stack([vals[k].reshape(()).float() for k in keys]).tolist()       # one copy, one wait
+            vals = dict(zip(keys, host))
+        if update_g:
+            self._g_log = {k: vals[k] for k in g}
+        elif sync_log:
+            self._g_log = {k: float(v) for k, v in self._g_log.items()}
+        merged = dict(self._g_log)
+        merged.update({k: vals[k] for k in ('l_d_real', 'l_d_fake', 'D_real', 'D_fake')})
+        self.log = {k: merged[k] for k in LOG_KEYS if k in merged}
+        return self.log

@@ -513,6 +513,21 @@ typedef struct esr_ragan_loss {
   const float* grad_scale_dev;         /* non-NULL: multiplied in as well, read on the device */
 } esr_ragan_loss;
 
+typedef struct esr_gan_loss {
+  const float* x; const float* y;      /* n_x logits; y (n_y logits) may be NULL: one operand */
+  float* grad_x; float* grad_y;        /* may be NULL */
+  float* loss;                         /* weight * (l(x, tx) [+ l(y, ty)]) */
+  float* term_x; float* term_y;        /* optional: the two terms, unweighted (l_d_real / l_d_fake) */
+  float* mean_x; float* mean_y;        /* optional: mean(x), mean(y) (D_real / D_fake) */
+  const float* grad_scale_dev;         /* non-NULL: multiplied into the gradients as well, read on the device */
+  int32_t n_x, n_y;
+  float tx, ty;                        /* the label VALUES (GANLoss real_label_val / fake_label_val) */
+  int32_t kind;                        /* 0 = vanilla (BCE with logits), 1 = lsgan (MSE) */
+  float weight;
+  float grad_scale;                    /* grad_x / grad_y times this (loss scale); 0 = 1 */
+  int32_t _pad;
+} esr_gan_loss;
+
 typedef struct esr_img_metrics {
   const float* sr;           /* [C][H][W] fp32 */
   const float* hr;           /* same shape, or NULL: conversion only */
@@ -813,6 +828,11 @@ int esr_image_metrics(const esr_img_metrics* p, esr_stream_t stream);   /* repla
 int esr_l1_loss_forward(const esr_l1_loss* p, esr_stream_t stream);
 int esr_l2_loss_forward(const esr_l1_loss* p, esr_stream_t stream);
 int esr_ragan_loss_forward(const esr_ragan_loss* p, esr_stream_t stream);
+/* esr_gan_loss_forward: GANLoss.forward (loss.py:6-38) of the standard-GAN step (SRGAN_model.py:129-146) on one or two
+ *   operands: l(x, t) = mean BCEWithLogits(x, t) (kind 0, 'vanilla') or mean (x - t)^2 (kind 1, 'lsgan') against the
+ *   constant label t; *loss = weight * (l(x, tx) [+ l(y, ty)]); grad_x = weight * grad_scale [* grad_scale_dev[0]] *
+ *   (sigmoid(x) - tx) / n_x  resp.  ... * 2 (x - tx) / n_x, grad_y alike.  One launch, no scratch. */
+int esr_gan_loss_forward(const esr_gan_loss* p, esr_stream_t stream);
 
 /* Run a recorded list of ops back to back on `stream` (one host call per network pass; this is
  * what RRDBNet.forward — architecture.py:76-78 — becomes). */
