@@ -181,6 +181,20 @@ class esr_resample(C.Structure):
                 ('w', C.c_void_p), ('idx', C.c_void_p)]
 
 
+class esr_batch_item(C.Structure):      # rows of esr_batch.items (data.TrainSet fills them as a numpy record array)
+    _fields_ = [('hr', C.c_void_p), ('lr', C.c_void_p), ('wy', C.c_void_p), ('iy', C.c_void_p),
+                ('wx', C.c_void_p), ('ix', C.c_void_p),
+                ('hr_h', C.c_int32), ('hr_w', C.c_int32), ('lr_h', C.c_int32), ('lr_w', C.c_int32),
+                ('y0', C.c_int32), ('x0', C.c_int32), ('flags', C.c_int32),
+                ('taps_y', C.c_int32), ('taps_x', C.c_int32), ('_pad', C.c_int32)]
+
+
+class esr_batch(C.Structure):
+    _fields_ = [('B', C.c_int32), ('C', C.c_int32), ('lr_size', C.c_int32), ('scale', C.c_int32),
+                ('src_format', C.c_int32), ('swap_rb', C.c_int32),
+                ('lr_out', C.c_void_p), ('hr_out', C.c_void_p), ('items', C.c_void_p)]
+
+
 class esr_pack_batch(C.Structure):
     _fields_ = [('table', C.c_void_p), ('piece_begin', C.c_void_p), ('n', C.c_int32), ('_pad', C.c_int32),
                 ('total_pieces', C.c_int64)]
@@ -274,7 +288,8 @@ EXPORTS = ['esr_packed_weight_bytes', 'esr_g32_dims', 'esr_conv_forward', 'esr_p
            'esr_l1_loss_forward', 'esr_ragan_loss_forward', 'esr_rdb_wgrad_run', 'esr_rdb_wgrad_workspace_elems', 'esr_rdb_backward',
            'esr_rdb_mask_bytes', 'esr_rdb_check_abort', 'esr_debug_hold_cus', 'esr_debug_device_alias', 'esr_debug_chain_order_waits',
            'esr_debug_mfma_probe', 'esr_debug_rdb_wgrad_follow', 'esr_dihedral_op', 'esr_tile_op',
-           'esr_tile_x8_op', 'esr_l2_loss_forward', 'esr_fold3_op', 'esr_gan_loss_forward']
+           'esr_tile_x8_op', 'esr_l2_loss_forward', 'esr_fold3_op', 'esr_gan_loss_forward',
+           'esr_batch_assemble']
 
 _lib = None
 _lock = threading.Lock()
@@ -337,7 +352,8 @@ def lib():
                          ('esr_ragan_loss_forward', esr_ragan_loss), ('esr_gan_loss_forward', esr_gan_loss),
                          ('esr_rdb_wgrad_run', esr_rdb_wgrad), ('esr_rdb_backward', esr_rdb_chain),
                          ('esr_dihedral_op', esr_dihedral), ('esr_tile_op', esr_tile),
-                         ('esr_tile_x8_op', esr_tile_x8), ('esr_fold3_op', esr_fold3)):
+                         ('esr_tile_x8_op', esr_tile_x8), ('esr_fold3_op', esr_fold3),
+                         ('esr_batch_assemble', esr_batch)):
             getattr(L, name).argtypes = [C.POINTER(st), C.c_void_p]
         if L.esr_sizeof_op() != C.sizeof(esr_op):
             raise HipExtensionError('ABI mismatch: sizeof(esr_op) C=%d ctypes=%d'

@@ -11,7 +11,10 @@ device, so eight GPUs are not fed by eight Python processes looping over image r
 * ``paired_random_crop`` / ``augment`` — the crop + flip/rot logic on NCHW device tensors, one window / one
   set of coin flips per sample.  ``crop_and_augment`` draws from Python's ``random`` in the reference's
   per-item order (randint, randint, then the three coin flips, sample by sample: LRHR_dataset.py:96-110);
-  the two separate helpers draw all windows first, then all flips."""
+  the two separate helpers draw all windows first, then all flips.
+* ``TrainSet`` — the dataset itself on the device: a pool of decoded images of any sizes (uint8 as decoded), and per
+  batch ONE launch (``esr_batch_assemble``) that cuts the windows, flips, converts and, without LR images, resamples the
+  LR window from the HR image.  ``batch_reference`` restates it in torch on the CPU for the tests."""
 import ctypes as C
 import math
 import random
@@ -170,3 +173,309 @@ def crop_and_augment(lr, hr, lr_size, scale, hflip=True, rot=True):
     if single:
         return outl[0], outh[0]
     return torch.stack(outl), torch.stack(outh)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The device-resident training set: the pool of decoded images stays on the device as it was decoded (uint8 HWC, or
+# float32 CHW), and a batch is ONE esr_batch_assemble launch driven by a table of B items.
+# ------------------------------------------------------------------------------------------------------------------
+SCALES = (1, 2, 3, 4, 8)
+FLAG_HFLIP, FLAG_VFLIP, FLAG_TRANSPOSE = 1, 2, 4
+
+
+def modcrop(img, scale):
+    """``util.modcrop`` (util.py:191-204): drop the rows / columns beyond the largest multiple of ``scale``.
+    img: an H x W or H x W x C array (a copy is returned, as the reference does), or a [..., H, W] tensor (CHW)."""
+    if isinstance(img, torch.Tensor):
+        if img.dim() < 2:
+            raise ValueError('Wrong img ndim: [%d].' % img.dim())
+        h, w = img.shape[-2:]
+        return img[..., :h - h % scale, :w - w % scale].clone()
+    import numpy as np
+    img = np.copy(img)
+    if img.ndim not in (2, 3):
+        raise ValueError('Wrong img ndim: [%d].' % img.ndim)
+    h, w = img.shape[:2]
+    return img[:h - h % scale, :w - w % scale]
+
+
+def _item_dtype():
+    import numpy as np
+    dt = np.dtype([(n, {C.c_void_p: '<u8', C.c_int32: '<i4'}[t]) for n, t in L.esr_batch_item._fields_], align=True)
+    assert dt.itemsize == C.sizeof(L.esr_batch_item)
+    assert all(dt.fields[n][1] == getattr(L.esr_batch_item, n).offset for n, _ in L.esr_batch_item._fields_)
+    return dt
+
+
+def _as_pool_image(img, what, i):
+    """-> ('u8', HWC uint8 array of 3 channels) or ('f32', CHW float32 tensor of 3 channels); ValueError otherwise."""
+    import numpy as np
+    if isinstance(img, torch.Tensor):
+        if img.dim() != 3 or img.dtype != torch.float32 or img.shape[0] < 3:
+            raise ValueError('TrainSet: %s image %d must be a float32 CHW tensor of 3 channels, got %s %s'
+                             % (what, i, img.dtype, tuple(img.shape)))
+        return 'f32', img[:3]                                    # some images have 4 channels (util.py:83-84)
+    img = np.asarray(img)
+    if img.ndim != 3 or img.shape[2] < 3 or img.dtype != np.uint8:
+        raise ValueError('TrainSet: %s image %d must be a uint8 H x W x 3 array (grey images are not converted), got '
+                         '%s %s' % (what, i, img.dtype, img.shape))
+    return 'u8', img[:, :, :3]
+
+
+class TrainSet:
+    """The training set of ``LRHRDataset`` (codes/data/LRHR_dataset.py, phase 'train') held on the device as the pixels a
+    decoder produced, and cut into batches by one HIP launch each.
+
+    hr_images (and lr_images, when the LR side is stored rather than generated): uint8 HWC arrays as ``cv2.imread`` /
+    PIL give them, or float32 CHW tensors in [0, 1]; one set holds one kind; the images may all differ in size.  Images
+    with 4 channels keep the first three (util.py:83-84).  Without ``lr_images`` the LR window of a sample is
+    resampled from its HR image on the fly (LRHR_dataset.py:81-85: ``imresize_np(img_HR, 1 / scale)``) — evaluated on
+    the whole image's tables, so it equals the crop of the whole image's ``imresize``.  ``bgr=True``: the pool is in
+    cv2's channel order and a batch comes out RGB (LRHR_dataset.py:117-119).
+
+    Out of scope (refused with ``ValueError`` in the constructor, before the device is touched): the reference's
+    ``cv2.resize`` branches — HR sizes that are no multiple of ``scale`` (LRHR_dataset.py:74-76 resizes them
+    bilinearly; ``modcrop`` the images instead), images smaller than the window (:90-96), random scales — and
+    ``color`` conversion.
+
+    All pixels live in ONE device buffer; the resample tables are cached on the device per distinct (length, scale)."""
+
+    RING = 4        # pinned item tables: a call may rewrite a table only once the copy that read it is done
+
+    def __init__(self, hr_images, lr_images=None, scale=4, lr_size=32, use_flip=True, use_rot=True, bgr=False,
+                 device=None):
+        import numpy as np
+        if scale not in SCALES:
+            raise ValueError('TrainSet: scale must be one of %s, got %r' % (SCALES, scale))
+        if int(lr_size) < 1:
+            raise ValueError('TrainSet: lr_size must be >= 1, got %r' % (lr_size,))
+        hr_images = list(hr_images)
+        if not hr_images:
+            raise ValueError('TrainSet: no HR images')
+        if lr_images is not None:
+            lr_images = list(lr_images)
+            if len(lr_images) != len(hr_images):
+                raise ValueError('TrainSet: %d LR images for %d HR images' % (len(lr_images), len(hr_images)))
+        self.scale, self.lr_size = int(scale), int(lr_size)
+        self.use_flip, self.use_rot, self.bgr = bool(use_flip), bool(use_rot), bool(bgr)
+        kinds = set()
+        hrs, lrs = [], []
+        for i, im in enumerate(hr_images):
+            k, im = _as_pool_image(im, 'HR', i)
+            kinds.add(k)
+            hrs.append(im)
+        for i, im in enumerate(lr_images or []):
+            k, im = _as_pool_image(im, 'LR', i)
+            kinds.add(k)
+            lrs.append(im)
+        if len(kinds) != 1:
+            raise ValueError('TrainSet: one set holds one kind of image, uint8 HWC arrays or float32 CHW tensors, not both')
+        self.kind = kinds.pop()
+        hw = (lambda im: tuple(im.shape[:2])) if self.kind == 'u8' else (lambda im: tuple(im.shape[1:]))
+        self.sizes = [hw(im) for im in hrs]                        # (H, W) of every HR image
+        lr_sizes = []
+        for i, (h, w) in enumerate(self.sizes):
+            if lrs:
+                lh, lw = hw(lrs[i])
+                if (h, w) != (self.scale * lh, self.scale * lw):
+                    raise ValueError('TrainSet: HR image %d is %d x %d, not %d times its LR image of %d x %d'
+                                     % (i, h, w, self.scale, lh, lw))
+            else:
+                if h % self.scale or w % self.scale:
+                    raise ValueError('TrainSet: HR image %d is %d x %d, not a multiple of scale %d in both directions: '
+                                     'cut it with data.modcrop(img, %d) first (the reference resizes it instead, which '
+                                     'this project does not restate)' % (i, h, w, self.scale, self.scale))
+                lh, lw = h // self.scale, w // self.scale
+            if lh < self.lr_size or lw < self.lr_size:
+                raise ValueError('TrainSet: the LR side of image %d is %d x %d, smaller than the %d x %d window (the '
+                                 'reference resizes such images, which this project does not restate)'
+                                 % (i, lh, lw, self.lr_size, self.lr_size))
+            lr_sizes.append((lh, lw))
+        self.lr_sizes = lr_sizes
+        if device is not None and torch.device(device).type != 'cuda':
+            raise ValueError('TrainSet: the pool lives on the MI355X, got device %s' % (device,))
+
+        # ---- from here on the device is used ----
+        dev = torch.device('cuda') if device is None else torch.device(device)
+        self.device = torch.device('cuda', torch.cuda.current_device()) if dev.index is None else dev
+        L.lib()
+        esz = 1 if self.kind == 'u8' else 4
+        flat, offs, pos = [], [], 0
+        for im in hrs + lrs:
+            a = np.ascontiguousarray(im) if self.kind == 'u8' else im.contiguous().numpy()
+            offs.append(pos)
+            flat.append(a.reshape(-1))
+            pos += a.size
+        host = np.concatenate(flat)
+        self.pool = torch.from_numpy(host).to(self.device)          # ONE allocation, an offset per image
+        self.pool_bytes = host.size * esz
+        base = self.pool.data_ptr()
+        n = len(hrs)
+        self._tables = {}                                             # (length, scale) -> (w, idx, taps) on the device
+        rec = np.zeros(n, dtype=_item_dtype())
+        for i in range(n):
+            rec['hr'][i] = base + offs[i] * esz
+            rec['hr_h'][i], rec['hr_w'][i] = self.sizes[i]
+            rec['lr_h'][i], rec['lr_w'][i] = lr_sizes[i]
+            if lrs:
+                rec['lr'][i] = base + offs[n + i] * esz
+            else:
+                wy, iy, ty = self._table(self.sizes[i][0])
+                wx, ix, tx = self._table(self.sizes[i][1])
+                rec['wy'][i], rec['iy'][i], rec['taps_y'][i] = wy.data_ptr(), iy.data_ptr(), ty
+                rec['wx'][i], rec['ix'][i], rec['taps_x'][i] = wx.data_ptr(), ix.data_ptr(), tx
+        self._static = rec
+        self._lr_h = np.array([s[0] for s in lr_sizes], dtype=np.int64)
+        self._lr_w = np.array([s[1] for s in lr_sizes], dtype=np.int64)
+        # The item table of a call is written into a pinned host buffer and copied to a fresh device tensor on the
+        # call's stream (the caching allocator does not hand that tensor out again before the launch has read it).
+        # What the next call must not overwrite is the PINNED buffer while its copy is in flight: a ring of RING
+        # pinned tables, each guarded by an event recorded behind its copy.  A slot is waited for only when the ring
+        # has gone round, RING calls later — a wait for one small copy, not a device synchronisation.
+        self._ring = []
+        self._calls = 0
+
+    def _table(self, length):
+        key = (int(length), self.scale)
+        t = self._tables.get(key)
+        if t is None:
+            w, idx, out_len = resample_tables(length, 1.0 / self.scale)
+            assert out_len == length // self.scale and w.shape == idx.shape, (length, self.scale, out_len)
+            t = self._tables[key] = (w.to(self.device), idx.to(self.device), int(w.shape[1]))
+        return t
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def draw(self, indices):
+        """The crop windows and flips of the samples ``indices``, from Python's ``random`` in the reference's per-item
+        order (LRHR_dataset.py:102-103 then util.py:96-98): randint, randint, then the coins of the enabled options
+        -> [(y0, x0, flags)], flags = hflip | vflip << 1 | transpose << 2.  Host code only."""
+        out = []
+        for i in indices:
+            lh, lw = self.lr_sizes[i]
+            y0 = random.randint(0, max(0, lh - self.lr_size))
+            x0 = random.randint(0, max(0, lw - self.lr_size))
+            hf = self.use_flip and random.random() < 0.5
+            vf = self.use_rot and random.random() < 0.5
+            r9 = self.use_rot and random.random() < 0.5
+            out.append((y0, x0, (FLAG_HFLIP if hf else 0) | (FLAG_VFLIP if vf else 0) | (FLAG_TRANSPOSE if r9 else 0)))
+        return out
+
+    def _pinned_slot(self, nbytes):
+        k = self._calls % self.RING
+        self._calls += 1
+        if k == len(self._ring):
+            self._ring.append([None, None])
+        slot = self._ring[k]
+        if slot[1] is not None:
+            slot[1].synchronize()                     # the copy that read this slot RING calls ago
+        if slot[0] is None or slot[0].numel() < nbytes:
+            slot[0] = torch.empty(max(nbytes, 4096), dtype=torch.uint8).pin_memory()
+        return slot
+
+    def batch(self, indices, draws=None):
+        """-> (lr [B, 3, s, s], hr [B, 3, s scale, s scale]): float32 NCHW on the device, fresh tensors every call, one
+        launch on the current stream, no device synchronisation.  draws: [(y0, x0, flags)] per sample (``draw``'s
+        result; drawn now if None)."""
+        import numpy as np
+        idx = np.asarray(list(indices), dtype=np.int64).reshape(-1)
+        B = idx.size
+        if B < 1 or B > 65535:
+            raise ValueError('TrainSet.batch: %d samples (1 ... 65535)' % B)
+        if idx.min() < 0 or idx.max() >= len(self):
+            raise ValueError('TrainSet.batch: indices outside the set of %d images' % len(self))
+        if draws is None:
+            draws = self.draw(idx.tolist())
+        d = np.asarray(draws, dtype=np.int64).reshape(-1, 3)
+        if d.shape[0] != B:
+            raise ValueError('TrainSet.batch: %d draws for %d samples' % (d.shape[0], B))
+        s = self.lr_size
+        if ((d[:, 0] < 0) | (d[:, 0] > self._lr_h[idx] - s) | (d[:, 1] < 0) | (d[:, 1] > self._lr_w[idx] - s)
+                | (d[:, 2] < 0) | (d[:, 2] > 7)).any():
+            raise ValueError('TrainSet.batch: a window outside its image, or flags outside 0 ... 7')
+        with torch.cuda.device(self.device):
+            lr = torch.empty((B, 3, s, s), dtype=torch.float32, device=self.device)
+            hr = torch.empty((B, 3, s * self.scale, s * self.scale), dtype=torch.float32, device=self.device)
+            self._assemble(idx, d, lr, hr)
+        return lr, hr
+
+    def _assemble(self, idx, d, lr, hr):
+        """The launch behind ``batch``: samples idx (int64 array) with draws d (int64 [B, 3], validated by the caller)
+        into the contiguous float32 tensors lr / hr, on the current stream of the current device (= self.device)."""
+        B, s = idx.size, self.lr_size
+        assert lr.is_contiguous() and hr.is_contiguous() and lr.dtype == hr.dtype == torch.float32
+        assert lr.numel() == B * 3 * s * s and hr.numel() == lr.numel() * self.scale ** 2
+        assert lr.device == hr.device == self.device
+        rec = self._static[idx]
+        rec['y0'], rec['x0'], rec['flags'] = d[:, 0], d[:, 1], d[:, 2]
+        nbytes = rec.nbytes
+        slot = self._pinned_slot(nbytes)
+        slot[0].numpy()[:nbytes].view(rec.dtype)[:] = rec
+        table = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        table.copy_(slot[0][:nbytes], non_blocking=True)
+        if slot[1] is None:
+            slot[1] = torch.cuda.Event()
+        slot[1].record()
+        a = L.esr_batch()
+        a.B, a.C, a.lr_size, a.scale = B, 3, s, self.scale
+        a.src_format, a.swap_rb = (1 if self.kind == 'u8' else 0), int(self.bgr)
+        a.lr_out, a.hr_out, a.items = lr.data_ptr(), hr.data_ptr(), table.data_ptr()
+        L.check(L.lib().esr_batch_assemble(C.byref(a), C.c_void_p(E.current_stream())), 'esr_batch_assemble')
+        return a, table
+
+    def epoch(self, batch_size, shuffle=True, drop_last=True):
+        """Batches over one pass of the set, in a ``torch.randperm`` order when shuffled (not the order of the
+        reference's ``DataLoader``, which with workers is not reproducible either)."""
+        n = len(self)
+        order = torch.randperm(n).tolist() if shuffle else list(range(n))
+        for i in range(0, n, batch_size):
+            ids = order[i:i + batch_size]
+            if len(ids) < batch_size and drop_last:
+                return
+            yield self.batch(ids)
+
+
+def batch_reference(hr_images, lr_images, scale, lr_size, draws, bgr=False):
+    """What ``TrainSet.batch`` computes, restated with torch on the CPU in float32 — the yardstick of its tests, itself
+    pinned to the reference's ``LRHRDataset.__getitem__`` by tests/golden/batch_assemble.npz.  hr_images / lr_images:
+    the images of the batch's samples, one per draw (lr_images None: the LR window is cut from the whole image's
+    resample — the tables of ``resample_tables`` evaluated as sums over the taps, H pass then W pass).
+    -> (lr [B, 3, s, s], hr [B, 3, s scale, s scale])"""
+    import numpy as np
+
+    def chw(img):
+        if isinstance(img, torch.Tensor):
+            return img[:3].float()
+        a = np.asarray(img)[:, :, :3]
+        return torch.from_numpy(np.ascontiguousarray(np.transpose(a.astype(np.float32) / np.float32(255.), (2, 0, 1))))
+
+    def resample(x):
+        wh, ih, _ = resample_tables(x.shape[1], 1.0 / scale)
+        ww, iw, _ = resample_tables(x.shape[2], 1.0 / scale)
+        y = (x[:, ih.long(), :] * wh[None, :, :, None]).sum(2)
+        return (y[:, :, iw.long()] * ww[None, None, :, :]).sum(3)
+
+    outl, outh = [], []
+    whole = {}                                                        # the resample of an image used more than once
+    for b, (y0, x0, flags) in enumerate(draws):
+        hr = chw(hr_images[b])
+        if lr_images is not None:
+            lr = chw(lr_images[b])
+        else:
+            key = id(hr_images[b])
+            if key not in whole:
+                whole[key] = resample(hr)
+            lr = whole[key]
+        l = lr[:, y0:y0 + lr_size, x0:x0 + lr_size]
+        h = hr[:, scale * y0:scale * (y0 + lr_size), scale * x0:scale * (x0 + lr_size)]
+        assert l.shape[1:] == (lr_size, lr_size) and h.shape[1:] == (scale * lr_size, scale * lr_size), (b, y0, x0)
+        for bit, fn in ((FLAG_HFLIP, lambda t: t.flip(-1)), (FLAG_VFLIP, lambda t: t.flip(-2)),
+                        (FLAG_TRANSPOSE, lambda t: t.transpose(-1, -2))):
+            if flags & bit:
+                l, h = fn(l), fn(h)
+        if bgr:
+            l, h = l.flip(0), h.flip(0)
+        outl.append(l)
+        outh.append(h)
+    return torch.stack(outl).contiguous(), torch.stack(outh).contiguous()

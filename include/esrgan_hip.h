@@ -422,6 +422,42 @@ typedef struct esr_resample {
   const int32_t* idx;    /* [out_len][taps] */
 } esr_resample;
 
+/* One training batch cut out of a device-resident image pool in ONE launch: B calls of LRHRDataset.__getitem__
+ * (codes/data/LRHR_dataset.py:81-121) — per sample the paired crop windows, util.augment's flips (util.py:94-106),
+ * uint8 -> float32 (util.py:79) and BGR -> RGB (LRHR_dataset.py:117-119) — and, for a sample without an LR image, the
+ * LR window of imresize(hr, 1 / scale) (util.py:276-343) computed from the HR image.  Images may differ in size and
+ * kind from sample to sample.  With `crop` a sample's window (LR: lr_size^2 at (y0, x0); HR: (scale lr_size)^2 at
+ * (scale y0, scale x0)) and n its side:
+ *   out[c][i][j] = t[c][a][b],  (a, b) = (j, i) if transpose else (i, j),
+ *   t[c][a][b]   = crop[c'][vflip ? n - 1 - a : a][hflip ? n - 1 - b : b],  c' = swap_rb ? 2 - c : c.
+ * A uint8 value v converts as (float)v / 255.0f, a true division.  A generated LR pixel is the H pass then the W pass
+ * over the WHOLE image's tables (the mirror border is the image's, not the window's), each a sum over the taps in
+ * ascending order, as esr_resample_axis forms it.  The item table is DEVICE memory and the caller's contract: windows
+ * inside their images, tables of esr_resample's layout for (hr_h, 1 / scale) and (hr_w, 1 / scale), so that
+ * lr_h = hr_h / scale and lr_w = hr_w / scale.  No workspace. */
+typedef struct esr_batch_item {
+  const void* hr;            /* src_format 0: float32 [3][hr_h][hr_w] in [0,1]; 1: uint8 [hr_h][hr_w][3], rows packed */
+  const void* lr;            /* the same format, lr_h x lr_w; NULL: generate the LR window from hr */
+  const float* wy; const int32_t* iy;   /* generated LR only: [lr_h][taps_y] weights / source rows */
+  const float* wx; const int32_t* ix;   /*                    [lr_w][taps_x] weights / source columns */
+  int32_t hr_h, hr_w, lr_h, lr_w;
+  int32_t y0, x0;            /* the window's origin on the LR grid */
+  int32_t flags;             /* bit 0 hflip, bit 1 vflip, bit 2 transpose, applied in that order */
+  int32_t taps_y, taps_x;
+  int32_t _pad;
+} esr_batch_item;
+
+typedef struct esr_batch {
+  int32_t B, C;              /* C = 3, else ESR_ERR_UNSUPPORTED; B <= 65535, else ESR_ERR_UNSUPPORTED */
+  int32_t lr_size;           /* s: the LR window's side */
+  int32_t scale;             /* 1, 2, 3, 4 or 8 */
+  int32_t src_format;        /* 0: float32 CHW planes; 1: uint8 HWC */
+  int32_t swap_rb;           /* output channel c reads source channel 2 - c */
+  float* lr_out;             /* [B][3][s][s] */
+  float* hr_out;             /* [B][3][s scale][s scale] */
+  const esr_batch_item* items;   /* DEVICE table of B entries */
+} esr_batch;
+
 /* Adam over a whole network in ONE launch (torch.optim.Adam semantics, SRRaGAN_model.py:77-91:
  * amsgrad off; the reference steps ~770 parameter tensors per optimizer).  `entries` / `blocks` are
  * DEVICE tables built once per parameter set: entry e = {param pointer, offset of its gradient /
@@ -763,6 +799,7 @@ int esr_grad_unpermute(const esr_unpermute* p, esr_stream_t stream);
 int esr_adam_step(const esr_adam* p, esr_stream_t stream);
 int esr_amp_step(const esr_amp* p, esr_stream_t stream);
 int esr_resample_axis(const esr_resample* p, esr_stream_t stream);
+int esr_batch_assemble(const esr_batch* p, esr_stream_t stream);   /* added under ABI 6: a pure addition, not an op of esr_run_ops */
 int esr_pack_conv_weights_batch(const esr_pack_batch* p, esr_stream_t stream);
 /* Fused dense-block chain (replaces 5 x n_blocks esr_conv_forward launches; block.py:260-268,287-291).
  * Every launch assumes its whole grid resident.  Launches on one stream are ordered by the stream; a launch whose
@@ -857,7 +894,7 @@ int esr_graph_destroy(esr_graph_t g);
 int esr_run_ops_timed(const esr_op* ops, int32_t n, esr_stream_t stream, float* ms_out);
 
 const char* esr_last_error(void);
-int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8, and esr_fold3 / esr_fold3_op / ESR_OP_FOLD3 with esr_pool modes 4 / 5 were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
+int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8, esr_fold3 / esr_fold3_op / ESR_OP_FOLD3 with esr_pool modes 4 / 5, and esr_batch / esr_batch_item / esr_batch_assemble were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
                                 esr_l1_loss, esr_ragan_loss, ESR_OPF_SIDE_FREE) */
 size_t esr_sizeof_op(void);
 
