@@ -10,7 +10,9 @@ reference adjoint used for the up-convs, run without a GPU.
 Error bounds are relative to the reference's largest magnitude, a few times the worst error measured on an MI355X.
 Weight gradients are fp32 sums of products of stored values: both precisions at 2e-6 (worst 5.6e-7 fp32, 3.0e-7 fp16).
 Input gradients: fp32 at 4e-6 (worst 8.2e-7); fp16 at 1.5e-3, where rounding the stored fp16 result alone costs up to
-2^-11 of the scale (worst 4.2e-4)."""
+2^-11 of the scale (worst 4.2e-4).  The `exit` cases run the epilogue's third stage as engine.exit_to_conv uses it below
+an RRDB boundary — res2 with beta != 1, Philox noise on out and on out3 = v * gamma * (1 + sigma z3), the mask next to
+res2 — at the same bounds (worst 3.5e-4 fp16, 1.1e-7 fp32), in fp32 also bit for bit against explicit z2 / z3."""
 import zlib
 
 import numpy as np
@@ -20,6 +22,7 @@ import torch.nn.functional as F
 
 SENT = 1234.0          # exactly representable in fp16: marks G32 elements a kernel must not write
 SLOPE = 0.2            # ESR_LRELU_SLOPE
+SIGMA = 0.1            # GaussianNoise sigma (engine.SIGMA, what _conv sets)
 TOL_WG = 2e-6          # weight gradients, both precisions (fp32 accumulation of exact products)
 TOL_DG = {'fp32': 4e-6, 'fp16': 1.5e-3}
 
@@ -202,6 +205,8 @@ DG_CASES = [
     ('f16_general_res2', 'fp16', 2, 96, 48, '3x3', 13, 40, 0, 'general2', None, (1, 'plain', 1)),
     ('f32_general_res2', 'fp32', 2, 96, 48, '3x3', 13, 40, 0, 'general2', None, (4, 'plain', 1)),
     ('f16_sum_fold', 'fp16', 2, 64, 48, '3x3', 13, 40, 0, 'plain', (32, 0, 32), (1, 'plain', 1)),
+    ('f16_exit', 'fp16', 2, 96, 48, '3x3', 13, 40, 0, 'exit', None, (1, 'plain', 1)),
+    ('f32_exit', 'fp32', 2, 96, 48, '3x3', 13, 40, 0, 'exit', None, (4, 'plain', 1)),
 ]
 
 
@@ -237,7 +242,8 @@ def test_dgrad_cases_reach_every_branch():
         tiles = cdiv(c[7], 32) * cdiv(c[6], 16) * c[2]
         assert rw < (1 if tiles * cdiv(c[3], 32) <= 128 else (2 if tiles * cdiv(c[3], 32) <= 384 else 4)), name
     epis = {c[9] for c in DG_CASES}
-    assert {'mask_lrelu', 'mask_relu', 'general1', 'general2'} <= epis
+    assert {'mask_lrelu', 'mask_relu', 'general1', 'general2', 'exit'} <= epis
+    assert {c[1] for c in DG_CASES if c[9] == 'exit'} == {'fp16', 'fp32'}
     assert any(c[10] for c in DG_CASES)
 
 
@@ -661,6 +667,37 @@ def test_dgrad_matches_fp64(dev, case):
         neg = 0.0 if act == L.ACT_RELU else SLOPE
         c.mask, c.out2, c.mask_cb_begin, c.mask_act = mk.view(0, cin), out.view(0, cin), 0, act
         checks.append(('out2', out, cin, gx * torch.where(m > 0, 1.0, neg)))
+    elif epi == 'exit':
+        # the slice-x conv that closes a block of the per-conv backward below an RRDB boundary (engine.exit_to_conv with
+        # a skip_out), every stage at once: v = (acc * alpha + res1) * beta + res2;  v *= 1 + sigma z2;  out = v;
+        # out2 = v * act'(mask) from cout block mask_cb_begin;  out3 = v * gamma * (1 + sigma z3) — z from the fused
+        # Philox stream (layer2 != layer3), compared on the z esr_fill_noise reports for the same key
+        from esrganplus_amd import ops as O
+        f32 = lambda v_: float(np.float32(v_))
+        mcb, alpha, beta, gamma, l2, l3, seed = 1, 0.2, 0.7, 0.2, 7, 91, 0x1234_5678_9abc
+        cm = cin - 32 * mcb
+        r1 = q(rnd((B, cin, H, W), 'dg.res1', name), prec)
+        r2 = q(rnd((B, cin, H, W), 'dg.res2', name), prec)
+        m = rnd((B, cm, H, W), 'dg.mask', name)
+        m = torch.where(m.abs() < 0.3, torch.zeros_like(m), m)
+        bufs = {}
+        for key, t in (('res1', r1), ('res2', r2), ('mask', m)):
+            bufs[key] = g32(dev, prec, B, t.shape[1], H, W)
+            upload(bufs[key], t)
+        z2, z3 = (O.philox_normal((B, cin, H, W), seed, lid, dev).cpu() for lid in (l2, l3))
+        v = (gx * f32(alpha) + r1[idx].double()) * f32(beta) + r2[idx].double()
+        v = v * (1 + f32(SIGMA) * z2[idx].double())
+        out2 = g32(dev, prec, B, cdiv(cm, cpg) * cpg + cpg, H, W, SENT)
+        out3 = g32(dev, prec, B, extra, H, W, SENT)
+        c.alpha, c.res1 = alpha, bufs['res1'].view(0, cin)
+        c.beta, c.res2 = beta, bufs['res2'].view(0, cin)
+        c.noise_mode, c.seed, c.layer2, c.layer3 = L.NOISE_PHILOX, seed, l2, l3
+        c.out, c.out3, c.gamma = out.view(0, cin), out3.view(0, cin), gamma
+        c.mask, c.out2, c.mask_cb_begin, c.mask_act = bufs['mask'].view(0, cm), out2.view(0, cm), mcb, L.ACT_LRELU
+        mq = q(m, prec)[idx].double()
+        checks.append(('out', out, cin, v))
+        checks.append(('out2', out2, cm, v[:, 32 * mcb:] * torch.where(mq > 0, 1.0, SLOPE)))
+        checks.append(('out3', out3, cin, v * f32(gamma) * (1 + f32(SIGMA) * z3[idx].double())))
     else:
         # the general epilogue: v = acc * alpha + res1 [* beta + res2]; out = v; out2 = v * act'(mask) for cout blocks
         # >= mask_cb_begin, out2 / mask indexed from that block
@@ -698,3 +735,18 @@ def test_dgrad_matches_fp64(dev, case):
         assert e <= TOL_DG[prec], '%s %s: err/scale %.3e' % (name, what, e)
         check_buffer(buf, C_, '%s %s' % (name, what))
     print('dgrad %s: err/scale %.2e' % (name, worst))
+    if epi == 'exit' and prec == 'fp32':
+        # the same launch on explicit z2 / z3 holding that z: bit for bit the Philox result, in all three outputs
+        first = [buf.t.clone() for _, buf, _, _ in checks]
+        for _, buf, _, _ in checks:
+            buf.t.fill_(SENT)
+        for which, t in (('z2', z2), ('z3', z3)):
+            bufs[which] = g32(dev, prec, B, cin, H, W)
+            upload(bufs[which], t)
+            setattr(c, which, bufs[which].view(0, cin))
+        c.noise_mode = L.NOISE_EXPLICIT
+        ops = L.OpList()
+        ops.add_conv(c)
+        run(ops)
+        for (what, buf, _, _), t in zip(checks, first):
+            assert torch.equal(buf.t, t), '%s %s: explicit z differs from the Philox stream' % (name, what)
