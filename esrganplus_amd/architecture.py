@@ -10,7 +10,7 @@ import math
 import torch.nn as nn
 
 from . import block as B
-from .functional import run_rrdbnet, run_rrdbnet_tiled, run_rrdbnet_tiled_x8, run_rrdbnet_x8
+from .functional import run_rrdbnet, run_rrdbnet_tiled, run_rrdbnet_tiled_many, run_rrdbnet_tiled_x8, run_rrdbnet_x8
 
 
 SUPPORTED_UPSCALE = (1, 2, 3, 4, 8)
@@ -143,6 +143,18 @@ class _RRDBNetBase(B._PlannedModule):
         self._x4_only('forward_tiled_x8')
         self._join_pending()
         return run_rrdbnet_tiled_x8(self, x, tile, pad, tiles_per_pass, slots_per_pass)
+
+    def forward_tiled_many(self, images, tile=96, pad=16, windows_per_pass=16):
+        """Tiled eval forward over an image set: the windows of ``forward_tiled`` of every image in ``images`` ([C, H, W]
+        or [1, C, H, W] float32 tensors on one GPU, of any sizes), packed ``windows_per_pass`` to a pass across images —
+        grouped by window shape, filler only in a group's last pass — so a folder runs at the cost of full passes ->
+        a list of [out_nc, 4H, 4W] / [1, out_nc, 4H, 4W] float32 results, ranks and order as the inputs, without
+        gradient.  One launch plan per (windows per pass, window shape), whatever the images.  Always the eval forward;
+        ``self.training`` and ``requires_grad`` are left as they are.  Not covered: the x8 self-ensemble over an image
+        set, scales other than 4, blending.  See ``functional.run_rrdbnet_tiled_many``."""
+        self._x4_only('forward_tiled_many')
+        self._join_pending()
+        return run_rrdbnet_tiled_many(self, images, tile, pad, windows_per_pass)
 
 
 class RRDBNet(_RRDBNetBase):

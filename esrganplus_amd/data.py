@@ -327,13 +327,9 @@ class TrainSet:
         self._static = rec
         self._lr_h = np.array([s[0] for s in lr_sizes], dtype=np.int64)
         self._lr_w = np.array([s[1] for s in lr_sizes], dtype=np.int64)
-        # The item table of a call is written into a pinned host buffer and copied to a fresh device tensor on the
-        # call's stream (the caching allocator does not hand that tensor out again before the launch has read it).
-        # What the next call must not overwrite is the PINNED buffer while its copy is in flight: a ring of RING
-        # pinned tables, each guarded by an event recorded behind its copy.  A slot is waited for only when the ring
-        # has gone round, RING calls later — a wait for one small copy, not a device synchronisation.
-        self._ring = []
-        self._calls = 0
+        # The item table of a call goes to the device through a ring of RING pinned tables (engine.PinnedRing): one
+        # non-blocking copy, no device synchronisation.
+        self._ring = E.PinnedRing(self.RING)
 
     def _table(self, length):
         key = (int(length), self.scale)
@@ -361,18 +357,6 @@ class TrainSet:
             r9 = self.use_rot and random.random() < 0.5
             out.append((y0, x0, (FLAG_HFLIP if hf else 0) | (FLAG_VFLIP if vf else 0) | (FLAG_TRANSPOSE if r9 else 0)))
         return out
-
-    def _pinned_slot(self, nbytes):
-        k = self._calls % self.RING
-        self._calls += 1
-        if k == len(self._ring):
-            self._ring.append([None, None])
-        slot = self._ring[k]
-        if slot[1] is not None:
-            slot[1].synchronize()                     # the copy that read this slot RING calls ago
-        if slot[0] is None or slot[0].numel() < nbytes:
-            slot[0] = torch.empty(max(nbytes, 4096), dtype=torch.uint8).pin_memory()
-        return slot
 
     def batch(self, indices, draws=None):
         """-> (lr [B, 3, s, s], hr [B, 3, s scale, s scale]): float32 NCHW on the device, fresh tensors every call, one
@@ -409,14 +393,7 @@ class TrainSet:
         assert lr.device == hr.device == self.device
         rec = self._static[idx]
         rec['y0'], rec['x0'], rec['flags'] = d[:, 0], d[:, 1], d[:, 2]
-        nbytes = rec.nbytes
-        slot = self._pinned_slot(nbytes)
-        slot[0].numpy()[:nbytes].view(rec.dtype)[:] = rec
-        table = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        table.copy_(slot[0][:nbytes], non_blocking=True)
-        if slot[1] is None:
-            slot[1] = torch.cuda.Event()
-        slot[1].record()
+        table = self._ring.upload(rec, self.device)
         a = L.esr_batch()
         a.B, a.C, a.lr_size, a.scale = B, 3, s, self.scale
         a.src_format, a.swap_rb = (1 if self.kind == 'u8' else 0), int(self.bgr)

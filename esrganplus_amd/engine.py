@@ -153,6 +153,8 @@ def set_nchw(op, ptr):
         op.u.tile.nchw = ptr
     elif op.kind == L.OP_TILE_X8:
         op.u.tile_x8.nchw = ptr
+    elif op.kind == L.OP_TILE_MANY:
+        op.u.tile_many.items = ptr       # the images are named by the pass's slice of the device item table
     else:
         op.u.layout.nchw = ptr
 
@@ -160,6 +162,43 @@ def set_nchw(op, ptr):
 def upload_table(table, device):
     """A ctypes array as a device tensor (the caller keeps it alive as long as an op points at it)."""
     return torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(device)
+
+
+class PinnedRing:
+    """Small per-call tables on their way to the device without a synchronisation: a table is written into a pinned host
+    buffer and copied to a FRESH device tensor on the current stream (the caching allocator does not hand that tensor out
+    again before the launches that read it have run).  What the next call must not overwrite is the pinned buffer while
+    its copy is in flight: a ring of `n` pinned buffers, each guarded by an event recorded behind its copy.  A slot is
+    waited for only when the ring has gone round, n calls later — a wait for one small copy, not a device
+    synchronisation.  (data.TrainSet's item tables, the slot tables of the tiled forward over an image set.)"""
+
+    def __init__(self, n=4):
+        self.n, self.slots, self.calls = n, [], 0
+
+    def slot(self, nbytes):
+        """The next [pinned uint8 buffer of at least nbytes, event behind its last copy or None]."""
+        k = self.calls % self.n
+        self.calls += 1
+        if k == len(self.slots):
+            self.slots.append([None, None])
+        slot = self.slots[k]
+        if slot[1] is not None:
+            slot[1].synchronize()                     # the copy that read this slot n calls ago
+        if slot[0] is None or slot[0].numel() < nbytes:
+            slot[0] = torch.empty(max(nbytes, 4096), dtype=torch.uint8).pin_memory()
+        return slot
+
+    def upload(self, rec, device):
+        """The 1-D numpy array `rec` as a fresh uint8 device tensor: one non-blocking copy on the current stream."""
+        nbytes = rec.nbytes
+        slot = self.slot(nbytes)
+        slot[0].numpy()[:nbytes].view(rec.dtype)[:] = rec
+        table = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        table.copy_(slot[0][:nbytes], non_blocking=True)
+        if slot[1] is None:
+            slot[1] = torch.cuda.Event()
+        slot[1].record()
+        return table
 
 
 class NoiseLayers:
@@ -312,13 +351,28 @@ def tile_x8_op(ops, dt_e, B, C_, th, tw, to_g32, t_count, k_begin, k_count, g=No
     return ops.add(L.OP_TILE_X8, 'tile_x8', d)
 
 
+def tile_many_op(ops, dt_e, C_, th, tw, to_g32, n_slots, g=None, slots=None):
+    """Image-set tiled end (esr_tile_many) appended to `ops`: the gather of n_slots th x tw windows, each of an image of
+    its own, into buffer g, or the stitch of n_slots window outputs — the fp32 NCHW tensor `slots` — each into its own
+    image.  tile, pad and the pass's slice of the device item table are set per run (TiledManyPlan.run)."""
+    d = L.esr_tile_many()
+    d.dtype, d.to_g32, d.scale = dt_e, to_g32, 1 if to_g32 else 4
+    d.C, d.th, d.tw, d.n_slots = C_, th, tw, n_slots
+    if to_g32:
+        d.g32 = g.view(0, C_)
+    else:
+        d.slots_nchw = slots.data_ptr()
+    d.tile, d.pad = max(th, tw), 0
+    return ops.add(L.OP_TILE_MANY, 'tile_many', d)
+
+
 class Builder:
     """Emits the fused-conv sequence of RDB / RRDB / RRDBNet into a Plan."""
 
     image_limit = False           # G32's per-image offset bound (TrainBuilder: the weight-gradient kernels)
 
     def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1, x8=None, tiled=None, tiled_x8=None,
-                 scale=4):
+                 scale=4, tiled_many=None):
         self.wp = wp
         self.scale = scale            # upscale of the generator: 1, 2, 4, 8 = 0..3 nearest-x2 up-convs, 3 = one folded x3
         self.B, self.H, self.W = B, H, W
@@ -338,6 +392,7 @@ class Builder:
         # (images, th, tw, first k, slots): the batch is slots x windows x images of a tiled self-ensemble, th x tw the
         # window on the NCHW side (H x W here is tw x th for the transposed slots, first k = 4)
         self.tiled_x8 = tiled_x8
+        self.tiled_many = tiled_many  # slots: the batch is the windows, H x W each, of any images of a tiled forward
 
     def buf(self, C_, H=None, W=None):
         return new_buf(self.bufs, self.B, C_, H or self.H, W or self.W, self.dtype, self.device, self.image_limit)
@@ -582,6 +637,14 @@ class Builder:
             c.nchw_out = slots.data_ptr()
             P.ops.add_conv(c)
             P.out_op = tile_x8_op(P.ops, d, n, out_nc, wh, ww, 0, B // (kc * n), k0, kc, slots=slots)
+        elif self.tiled_many is not None:
+            # tiled forward over an image set: as the tiled forward below, but every slot's owned rectangle goes into the
+            # image its table entry names
+            slots = torch.empty(P.out_shape, dtype=torch.float32, device=self.device)
+            self.bufs.append(slots)
+            c.nchw_out = slots.data_ptr()
+            P.ops.add_conv(c)
+            P.out_op = tile_many_op(P.ops, d, out_nc, H, W, 0, B, slots=slots)
         elif self.tiled is not None:
             # tiled forward: HR_conv1 leaves the windows' fp32 NCHW outputs in a buffer of the plan, slot-major, and the
             # stitch copies every tile's owned rectangle into the caller's tensor
@@ -615,6 +678,8 @@ class Builder:
         if self.tiled_x8 is not None:
             n, wh, ww, k0, kc = self.tiled_x8
             P.in_op = tile_x8_op(P.ops, self.dt_e, n, in_nc, wh, ww, 1, B // (kc * n), k0, kc, g=xin)
+        elif self.tiled_many is not None:
+            P.in_op = tile_many_op(P.ops, self.dt_e, in_nc, H, W, 1, B, g=xin)
         elif self.tiled is not None:
             P.in_op = tile_op(P.ops, self.dt_e, self.tiled, in_nc, 1, B // self.tiled, g=xin)
         elif self.x8 is None:
@@ -925,6 +990,30 @@ def build_rrdbnet_tiled_plan(wp, nb, in_nc, out_nc, B, th, tw, dtype, device, va
     and between them the ops of the ordinary plan of batch P x B at the window shape th x tw."""
     b = Builder(wp, P * B, th, tw, dtype, device, False, variant, 'net', nb, tiled=B)
     return TiledPlan(b.rrdbnet(in_nc, out_nc, False), P)
+
+
+class TiledManyPlan:
+    """The tiled forward of S windows of th x tw per pass, whichever images they belong to: one inference plan of batch S
+    at th x tw between a table-driven gather and stitch (esr_tile_many).  Nothing in it depends on an image."""
+
+    def __init__(self, plan, S):
+        self.plan, self.S = plan, S
+
+    def run(self, gather_items, stitch_items, tile, pad, stream):
+        """One pass: the two uint8 device tensors hold the pass's S esr_tile_item entries (LR images / HR results)."""
+        plan = self.plan
+        arr = plan.ops.array()
+        g, s = arr[plan.in_op].u.tile_many, arr[plan.out_op].u.tile_many
+        g.tile = s.tile = tile
+        g.pad = s.pad = pad
+        plan.run(gather_items, stitch_items, stream)
+
+
+def build_rrdbnet_tiled_many_plan(wp, nb, in_nc, out_nc, S, th, tw, dtype, device, variant):
+    """Image-set form of build_rrdbnet_tiled_plan (eval mode): the ordinary plan of batch S at the window shape th x tw
+    between the table-driven gather and stitch."""
+    b = Builder(wp, S, th, tw, dtype, device, False, variant, 'net', nb, tiled_many=S)
+    return TiledManyPlan(b.rrdbnet(in_nc, out_nc, False), S)
 
 
 class TiledX8Plan:

@@ -720,3 +720,175 @@ def run_rrdbnet_tiled(net, x, tile=96, pad=16, tiles_per_pass=None):
     plan.run(xin, out, tile, pad, E.current_stream())
     order.leave(cur)
     return out
+
+
+def _tiled_many_ints(tile, pad, windows_per_pass):
+    """Validated ints (tile, pad, windows_per_pass) of a tiled forward over an image set: _tiled_args' rules and wording."""
+    import operator
+    vals = []
+    for name, v, lo in (('tile', tile, 1), ('pad', pad, 0), ('windows_per_pass', windows_per_pass, 1)):
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            v = operator.index(v)
+        except TypeError:
+            raise ValueError('%s of a tiled forward must be an int >= %d, got %r' % (name, lo, v))
+        if v < lo:
+            raise ValueError('%s of a tiled forward must be an int >= %d, got %r' % (name, lo, v))
+        vals.append(v)
+    return tuple(vals)
+
+
+def _tiled_many_groups(sizes, tile, pad, windows_per_pass):
+    """[(th, tw, S, [(image, tiles of that image)])] per window shape, in order of first appearance: the counts behind
+    ``tiled_many_passes`` without the window lists.  tile, pad, windows_per_pass are validated ints."""
+    groups = {}
+    for i, (H, W) in enumerate(sizes):
+        if H < 1 or W < 1:
+            raise ValueError('image %d of a tiled forward has no pixels: %d x %d' % (i, H, W))
+        key = (min(tile + 2 * pad, H), min(tile + 2 * pad, W))
+        groups.setdefault(key, []).append((i, -(-H // tile) * -(-W // tile)))
+    out = []
+    for (th, tw), members in groups.items():
+        S = min(windows_per_pass, sum(n for _, n in members))
+        if S > 65535:
+            raise ValueError('windows_per_pass = %d slots of %d x %d windows are more than one launch takes (65535)' % (S, th, tw))
+        out.append((th, tw, S, members))
+    return out
+
+
+def tiled_many_passes(sizes, tile, pad, windows_per_pass):
+    """The passes of a tiled forward over images of the LR sizes ``sizes`` [(H, W)]: host code only.  Windows are grouped
+    by window shape (min(tile + 2 pad, H), min(tile + 2 pad, W)) — a pass is one batch of one shape — the groups in order
+    of first appearance, inside a group the images in list order and each image's tiles row-major (``tiled_geometry``).
+    A group of n windows runs in ceil(n / S) passes of S = min(windows_per_pass, n) slots; only its last pass may hold
+    filler, which repeats the group's last window with live = 0 (gathered, so that no slot holds stale data, never
+    stitched).  -> [(th, tw, S, passes)] per group, passes a list of S-tuples (image, tile, live)."""
+    tile, pad, wpp = _tiled_many_ints(tile, pad, windows_per_pass)
+    out = []
+    for th, tw, S, members in _tiled_many_groups([(int(h), int(w)) for h, w in sizes], tile, pad, wpp):
+        wins = [(i, t, 1) for i, n in members for t in range(n)]
+        passes = []
+        for k in range(0, len(wins), S):
+            p = wins[k:k + S]
+            passes.append(tuple(p + [(wins[-1][0], wins[-1][1], 0)] * (S - len(p))))
+        out.append((th, tw, S, passes))
+    return out
+
+
+def _tiled_many_images(images, in_nc):
+    """The images of a tiled forward over an image set as a list of ([1, C, H, W] view, rank of the input): rank 3 or
+    4 with one image each, in_nc channels (None: whatever the first has), at least one pixel."""
+    out = []
+    for i, x in enumerate(images):
+        if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != 1):
+            raise ValueError('image %d of a tiled forward must be a [C, H, W] or [1, C, H, W] tensor, got %s'
+                             % (i, tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__))
+        v = x if x.dim() == 4 else x.unsqueeze(0)
+        if in_nc is None:
+            in_nc = v.shape[1]
+        if v.shape[1] != in_nc:
+            raise ValueError('image %d: expected %d input channels, got %d' % (i, in_nc, v.shape[1]))
+        if v.shape[2] < 1 or v.shape[3] < 1:
+            raise ValueError('image %d of a tiled forward has no pixels: shape %s' % (i, tuple(x.shape)))
+        out.append((v, x.dim()))
+    return out
+
+
+def tiled_many_reference(fn, images, tile, pad, windows_per_pass=16):
+    """Pure-torch restatement of the tiled forward over an image set and a x4 forward ``fn``: the passes of
+    ``tiled_many_passes``, ``fn`` called on exactly those batches — S windows of one shape, filler included — and the
+    owned rectangle of every live window copied out of its output into its image's result.  Nothing is blended.
+    -> a list of fp32 results, [C', 4H, 4W] or [1, C', 4H, 4W] as the inputs' ranks."""
+    tile, pad, wpp = _tiled_many_ints(tile, pad, windows_per_pass)
+    xs = _tiled_many_images(list(images), None)
+    geo = [tiled_geometry(v.shape[2], v.shape[3], tile, pad) for v, _ in xs]
+    outs = [None] * len(xs)
+    for th, tw, S, passes in tiled_many_passes([(v.shape[2], v.shape[3]) for v, _ in xs], tile, pad, wpp):
+        for p in passes:
+            wins = [xs[i][0][:, :, geo[i][4][t][4]:geo[i][4][t][4] + th, geo[i][4][t][5]:geo[i][4][t][5] + tw] for i, t, _ in p]
+            ys = fn(torch.cat(wins, 0).contiguous()).float()
+            for s, (i, t, live) in enumerate(p):
+                if not live:
+                    continue
+                if outs[i] is None:
+                    outs[i] = ys.new_empty((1, ys.shape[1], 4 * xs[i][0].shape[2], 4 * xs[i][0].shape[3]))
+                y0, y1, x0, x1, wy, wx = geo[i][4][t]
+                outs[i][:, :, 4 * y0:4 * y1, 4 * x0:4 * x1] = ys[s:s + 1, :, 4 * (y0 - wy):4 * (y1 - wy), 4 * (x0 - wx):4 * (x1 - wx)]
+    return [o if rank == 4 else o[0] for o, (_, rank) in zip(outs, xs)]
+
+
+def _tile_item_dtype():
+    import numpy as np
+    return np.dtype([('nchw', '<u8'), ('H', '<i4'), ('W', '<i4'), ('t', '<i4'), ('live', '<i4')])   # esr_tile_item
+
+
+def run_rrdbnet_tiled_many(net, images, tile=96, pad=16, windows_per_pass=16):
+    """Tiled eval forward of RRDBNet over an image set: ``run_rrdbnet_tiled``'s windows and geometry per image, but the
+    windows of ALL images share the passes (``tiled_many_passes``): grouped by window shape, S = min(windows_per_pass,
+    windows of the group) per pass, so a folder costs ceil(windows / S) passes per shape where a loop of
+    ``run_rrdbnet_tiled`` costs that per image; only a group's last pass holds filler (its last window again, gathered
+    but not stitched).  ``images``: a sequence of [C, H, W] or [1, C, H, W] float32 tensors on one GPU, of any sizes ->
+    a list of fp32 results [out_nc, 4H, 4W] / [1, out_nc, 4H, 4W], ranks and order as the inputs, without gradient; an
+    empty list gives [].  One launch plan per (S, window shape, precision, weight generation) — no image size in the
+    key — the ordinary inference plan of batch S between a table-driven gather and stitch (include/esrgan_hip.h:
+    esr_tile_many).  The slot table of the whole call (two 24-byte entries per slot: the LR image and the HR result) is
+    written into a pinned ring buffer and uploaded with one non-blocking copy; every pass points its two ops at its
+    slice.  Everything runs on the current stream without a device synchronisation; the results are fresh tensors.  The
+    device holds the plan's activations of S windows plus this call's inputs and outputs.  Bit-identical to
+    ``tiled_many_reference(net, ...)``; for one image, to ``run_rrdbnet_tiled(x, tile, pad, windows_per_pass)``.  Noise
+    is off whatever ``net.training`` is; the module's mode and every ``requires_grad`` are left untouched.
+    Out of scope: the x8 self-ensemble over an image set, scales other than 4, blending."""
+    import numpy as np
+    tile, pad, wpp = _tiled_many_ints(tile, pad, windows_per_pass)
+    xs = _tiled_many_images(list(images), net.in_nc)
+    if not xs:
+        return []
+    sizes = [(v.shape[2], v.shape[3]) for v, _ in xs]
+    m = max(max(s) for s in sizes)
+    tile, pad = min(tile, m), min(pad, m)          # cut down to the largest image: changes no tile and no window
+    groups = tiled_many_passes(sizes, tile, pad, wpp)      # refuses more than 65535 slots per pass
+    dev = xs[0][0].device
+    for i, (v, _) in enumerate(xs):
+        if v.device != dev:
+            raise ValueError('image %d is on %s, image 0 on %s: a tiled forward runs on one device' % (i, v.device, dev))
+    if dev.type != 'cuda':
+        raise ValueError('the images of a tiled forward are on %s: the HIP path needs tensors on an MI355X; there is '
+                         'no CPU fallback' % (dev,))
+    xin = [v.detach().contiguous().float() for v, _ in xs]
+    order = E.StreamOrder.of(net)
+    cur = order.enter()
+    wp = net._weights(dev)
+    outs = [torch.empty((1, net.out_nc, 4 * H, 4 * W), dtype=torch.float32, device=dev) for H, W in sizes]
+    # one table for the call: the gather's entries of every pass of every group, then the stitch's
+    flat = [w for _, _, _, passes in groups for p in passes for w in p]
+    n = len(flat)
+    idx = np.fromiter((w[0] for w in flat), dtype=np.int64, count=n)
+    rec = np.zeros(2 * n, dtype=_tile_item_dtype())
+    rec['nchw'][:n] = np.array([x.data_ptr() for x in xin], dtype=np.uint64)[idx]
+    rec['nchw'][n:] = np.array([o.data_ptr() for o in outs], dtype=np.uint64)[idx]
+    hw = np.array(sizes, dtype=np.int32)[idx]
+    rec['H'][:n] = rec['H'][n:] = hw[:, 0]
+    rec['W'][:n] = rec['W'][n:] = hw[:, 1]
+    rec['t'][:n] = rec['t'][n:] = np.fromiter((w[1] for w in flat), dtype=np.int32, count=n)
+    rec['live'][:n] = rec['live'][n:] = np.fromiter((w[2] for w in flat), dtype=np.int32, count=n)
+    rings = net.__dict__.setdefault('_table_rings', {})
+    ring = rings.get(dev.index)
+    if ring is None:
+        ring = rings[dev.index] = E.PinnedRing()
+    table = ring.upload(rec, dev)
+    isz, stream, at = rec.dtype.itemsize, E.current_stream(), 0
+    for th, tw, S, passes in groups:
+        key = ('tiled_many', S, th, tw, net.precision, wp.generation)    # no H, W: whatever images have this window
+        plan = net._plans.get(key)
+        if plan is None:
+            if len(net._plans) >= net.max_cached_plans:
+                net._plans.clear()
+            plan = E.build_rrdbnet_tiled_many_plan(wp, net.nb, net.in_nc, net.out_nc, S, th, tw, net.precision, dev,
+                                                   net.variant)
+            net._plans[key] = plan
+        for _ in passes:
+            plan.run(table[at * isz:(at + S) * isz], table[(n + at) * isz:(n + at + S) * isz], tile, pad, stream)
+            at += S
+    order.leave(cur)
+    return [o if rank == 4 else o[0] for o, (_, rank) in zip(outs, xs)]

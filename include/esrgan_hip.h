@@ -293,6 +293,42 @@ typedef struct esr_tile_x8 {
   float mean_scale;
 } esr_tile_x8;
 
+/* Tiled inference over an image SET: the windows of many images, of any sizes, share one pass.  Geometry is esr_tile's,
+ * per image: slot s (0 <= s < n_slots, = batch index s; there is no B) belongs to tile items[s].t of the image
+ * items[s].nchw, whose tile grid ny x nx, inward shift and owned rectangle the kernels derive from that image's H, W and
+ * this op's tile, pad — the table holds no geometry.  Every item's window, min(tile + 2 pad, H) x min(tile + 2 pad, W),
+ * must be the op's th x tw: a pass holds windows of one shape.  The table lives in DEVICE memory (n_slots entries, read
+ * by the launch, so it must stay valid until the launch has run); this entry cannot read it, and whoever fills it
+ * guarantees per item: nchw a live fp32 image of C x H x W (gather) / C x 4H x 4W (stitch, 16-byte aligned), H, W >= 1,
+ * the window shape above, 0 <= t < ny nx, and for the stitch that no two live items name the same tile of one image.
+ * functional.run_rrdbnet_tiled_many builds it from validated sizes.  C <= 8 and n_slots <= 65535, else
+ * ESR_ERR_UNSUPPORTED.
+ *   to_g32 = 1, scale = 1  gather: slot s holds the th x tw window of its item's tile, converted to dtype, as finished
+ *               32-byte channel groups at the logical pixels of the G32 view (channels >= C zero, the halo is never
+ *               touched) — esr_tile's arithmetic and writes.  `live` is not read: a filler slot is filled like any other,
+ *               so that no slot holds stale data.
+ *   to_g32 = 0, scale = 4  stitch: slots_nchw is fp32 [n_slots][C][4 th][4 tw] (16-byte aligned); for every item with
+ *               live != 0 the owned rectangle of its tile is copied, bit for bit, into ITS image.  Slots with live == 0
+ *               are neither read nor written; g32 and dtype's storage type are unused.                                 */
+typedef struct esr_tile_item {   /* one slot of one pass; lives in DEVICE memory */
+  float*  nchw;                  /* gather: the LR image [C][H][W]; stitch: the HR result [C][4H][4W] */
+  int32_t H, W;                  /* LR size of that image (on both sides) */
+  int32_t t;                     /* tile index in that image's own ny x nx grid */
+  int32_t live;                  /* 0: a filler slot — the gather fills it, the stitch skips it */
+} esr_tile_item;
+
+typedef struct esr_tile_many {
+  int32_t dtype, to_g32;
+  int32_t C;
+  int32_t tile, pad;             /* LR pixels */
+  int32_t scale;                 /* 1: gather, 4: stitch */
+  int32_t th, tw;                /* the window shape every item has */
+  int32_t n_slots;               /* batch entries = slots, one image per slot */
+  const esr_tile_item* items;    /* n_slots entries, device memory */
+  esr_g32 g32;
+  const float* slots_nchw;
+} esr_tile_many;
+
 /* Philox-4x32-7 + Box-Muller N(0,1) fill (csrc/common.h), NCHW fp32 — the exact z the fused noise epilogue uses for
  * (seed, layer); lets tests feed the same z to the oracle (GaussianNoise, block.py:117-122). */
 typedef struct esr_noise_fill {
@@ -725,7 +761,7 @@ enum esr_op_kind { ESR_OP_CONV = 1, ESR_OP_PACK = 2, ESR_OP_LAYOUT = 3, ESR_OP_N
                    ESR_OP_UNPERMUTE = 9, ESR_OP_PACK_BATCH = 10,
                    ESR_OP_RDB_CHAIN = 11, ESR_OP_FRAG_GATHER = 12, ESR_OP_RDB_WGRAD = 13,
                    ESR_OP_RDB_CHAIN_BWD = 14 /* u.rdb_chain with mode 2 */, ESR_OP_DIHEDRAL = 15,
-                   ESR_OP_TILE = 16, ESR_OP_TILE_X8 = 17, ESR_OP_FOLD3 = 18 };
+                   ESR_OP_TILE = 16, ESR_OP_TILE_X8 = 17, ESR_OP_FOLD3 = 18, ESR_OP_TILE_MANY = 19 };
 
 /* esr_op.flags */
 #define ESR_OPF_SIDE 1   /* on a run of consecutive ESR_OP_WGRAD ops: launch the run on the library's side
@@ -771,6 +807,7 @@ typedef struct esr_op {
     esr_tile tile;
     esr_tile_x8 tile_x8;
     esr_fold3 fold3;
+    esr_tile_many tile_many;
   } u;
 } esr_op;
 
@@ -786,6 +823,7 @@ int esr_dihedral_op(const esr_dihedral* p, esr_stream_t stream);   /* added unde
 int esr_tile_op(const esr_tile* p, esr_stream_t stream);           /* added under ABI 6: a pure addition */
 int esr_tile_x8_op(const esr_tile_x8* p, esr_stream_t stream);     /* added under ABI 6: a pure addition */
 int esr_fold3_op(const esr_fold3* p, esr_stream_t stream);         /* added under ABI 6: a pure addition */
+int esr_tile_many_op(const esr_tile_many* p, esr_stream_t stream); /* added under ABI 6: a pure addition */
 int esr_conv_wgrad(const esr_wgrad* p, esr_stream_t stream);
 /* n independent weight-gradient problems (disjoint dw/dbias blocks).  fp16 3x3/s1 and 1x1 entries are
  * packed, up to 8 at a time, into ONE launch (at training sizes a single conv's wgrad is ~64
@@ -894,7 +932,7 @@ int esr_graph_destroy(esr_graph_t g);
 int esr_run_ops_timed(const esr_op* ops, int32_t n, esr_stream_t stream, float* ms_out);
 
 const char* esr_last_error(void);
-int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8, esr_fold3 / esr_fold3_op / ESR_OP_FOLD3 with esr_pool modes 4 / 5, and esr_batch / esr_batch_item / esr_batch_assemble were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
+int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8, esr_fold3 / esr_fold3_op / ESR_OP_FOLD3 with esr_pool modes 4 / 5, esr_batch / esr_batch_item / esr_batch_assemble, and esr_tile_many / esr_tile_item / esr_tile_many_op / ESR_OP_TILE_MANY were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
                                 esr_l1_loss, esr_ragan_loss, ESR_OPF_SIDE_FREE) */
 size_t esr_sizeof_op(void);
 

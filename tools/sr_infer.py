@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Inference harness reproducing the reference's ``test_image/test.py`` (lines 9-40) on the HIP path
-with PIL instead of cv2:  python tools/sr_infer.py <model.pth|synthetic> <in_dir> <out_dir> [fp16|fp32] [--scale S] [--x8] [--tile N[,PAD]] [--tile-x8 N[,PAD]]
+with PIL instead of cv2:  python tools/sr_infer.py <model.pth|synthetic> <in_dir> <out_dir> [fp16|fp32] [--scale S] [--x8] [--tile N[,PAD]] [--tile-x8 N[,PAD]] [--tile-many N[,PAD]]
 
 Per image: RGB /255 -> NCHW float32 -> RRDB_Net(3,3,64,23,...) -> clamp(0,1) -> *255 round -> PNG.
 --scale S (also --scale=S; 1, 2, 3, 4 or 8, default 4): the ``upscale`` the network is built with.
@@ -10,6 +10,11 @@ plain forward: ``model.forward_x8``.
 method's): one launch plan for a folder of images of any size, bounded memory; not combined with --x8.
 --tile-x8 N[,PAD] (also --tile-x8=N[,PAD]): the tiled self-ensemble ``model.forward_tiled_x8(x, tile=N, pad=PAD)``: the
 ensemble per window, with the tiled forward's bounded memory and shared plan; not combined with --x8 or --tile.
+--tile-many N[,PAD] (also --tile-many=N[,PAD]): the tiled forward over the folder,
+``model.forward_tiled_many(images, tile=N, pad=PAD)``: the windows of different images share the passes, so small and
+odd-sized images run at the cost of full passes.  Images are queued until they hold at least 4 x 16 windows (or the
+folder ends), run in one call and written; the output of each image is that of the call it ran in.  Not combined with
+--x8, --tile or --tile-x8.
 The tiled forms are x4-only: with another --scale the script exits with the library's message."""
 import glob
 import os
@@ -26,7 +31,7 @@ from esrganplus_amd import architecture as arch, synth
 def main():
     argv = [a for a in sys.argv[1:] if a != '--x8']
     x8 = '--x8' in sys.argv[1:]
-    tiles = {'--tile': None, '--tile-x8': None}
+    tiles = {'--tile': None, '--tile-x8': None, '--tile-many': None}
     for flag in tiles:
         for i, a in enumerate(argv):
             if a == flag or a.startswith(flag + '='):
@@ -39,7 +44,7 @@ def main():
                 if len(tiles[flag]) not in (1, 2):
                     sys.exit('sr_infer.py: %s takes N or N,PAD (LR pixels), got %r' % (flag, val))
                 break
-    tiled, tiled_x8 = tiles['--tile'], tiles['--tile-x8']
+    tiled, tiled_x8, tiled_many = tiles['--tile'], tiles['--tile-x8'], tiles['--tile-many']
     scale = 4
     for i, a in enumerate(argv):
         if a == '--scale' or a.startswith('--scale='):
@@ -53,14 +58,17 @@ def main():
         sys.exit('sr_infer.py: --tile and --x8 cannot be combined: the tiled self-ensemble is --tile-x8 N[,PAD]')
     if tiled_x8 and (x8 or tiled):
         sys.exit('sr_infer.py: --tile-x8 is the tiled self-ensemble by itself: it cannot be combined with --x8 or --tile')
+    if tiled_many and (x8 or tiled or tiled_x8):
+        sys.exit('sr_infer.py: --tile-many is the tiled forward over the folder by itself: it cannot be combined with '
+                 '--x8, --tile or --tile-x8')
     model_path, in_dir, out_dir = argv[0], argv[1], argv[2]
     prec = argv[3] if len(argv) > 3 else 'fp32'
     dev = torch.device('cuda')
     model = arch.RRDB_Net(3, 3, 64, 23, gc=32, upscale=scale, norm_type=None, act_type='leakyrelu',
                           mode='CNA', res_scale=1, upsample_mode='upconv')
-    if tiled or tiled_x8:
+    if tiled or tiled_x8 or tiled_many:
         try:
-            model._x4_only('--tile-x8' if tiled_x8 else '--tile')      # the library's own refusal, before anything is loaded
+            model._x4_only('--tile-x8' if tiled_x8 else '--tile-many' if tiled_many else '--tile')      # the library's own refusal, before anything is loaded
         except ValueError as e:
             sys.exit('sr_infer.py: %s' % e)
     sd = synth.rrdbnet_state_dict(23, 0, upscale=scale) if model_path == 'synthetic' else torch.load(model_path, map_location='cpu')
@@ -70,6 +78,8 @@ def main():
         v.requires_grad = False
     model = model.to(dev).set_precision(prec)
     os.makedirs(out_dir, exist_ok=True)
+    if tiled_many:
+        return run_tile_many(model, dev, in_dir, out_dir, *tiled_many)
     for idx, path in enumerate(sorted(glob.glob(os.path.join(in_dir, '*'))), 1):
         base = os.path.splitext(os.path.basename(path))[0]
         img = np.array(Image.open(path).convert('RGB')).astype(np.float64) / 255
@@ -81,6 +91,33 @@ def main():
         out = (np.transpose(out, (1, 2, 0)) * 255.0).round().astype(np.uint8)
         Image.fromarray(out).save(os.path.join(out_dir, '%s_rlt.png' % base))
         print(idx, base, img.shape[:2], '->', out.shape[:2])
+
+
+def run_tile_many(model, dev, in_dir, out_dir, tile, pad=16):
+    """--tile-many: the folder through ``forward_tiled_many`` in flushes of at least 4 x 16 windows; the same per-image
+    arithmetic, files and lines as the loop of ``main``."""
+    queue, windows = [], 0
+
+    def flush():
+        with torch.no_grad():
+            ys = model.forward_tiled_many([x for _, _, _, x in queue], tile, pad)
+            outs = [y.data.squeeze().float().cpu().clamp_(0, 1).numpy() for y in ys]
+        for (idx, base, shape, _), out in zip(queue, outs):
+            out = (np.transpose(out, (1, 2, 0)) * 255.0).round().astype(np.uint8)
+            Image.fromarray(out).save(os.path.join(out_dir, '%s_rlt.png' % base))
+            print(idx, base, shape, '->', out.shape[:2])
+        del queue[:]
+
+    for idx, path in enumerate(sorted(glob.glob(os.path.join(in_dir, '*'))), 1):
+        base = os.path.splitext(os.path.basename(path))[0]
+        img = np.array(Image.open(path).convert('RGB')).astype(np.float64) / 255
+        queue.append((idx, base, img.shape[:2], torch.from_numpy(np.transpose(img, (2, 0, 1))).float().unsqueeze(0).to(dev)))
+        windows += -(-img.shape[0] // max(tile, 1)) * -(-img.shape[1] // max(tile, 1))
+        if windows >= 4 * 16:
+            flush()
+            windows = 0
+    if queue:
+        flush()
 
 
 if __name__ == '__main__':
