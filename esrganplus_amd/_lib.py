@@ -25,6 +25,7 @@ OP_TILE = 16
 OP_TILE_X8 = 17
 OP_FOLD3 = 18
 OP_TILE_MANY = 19
+CHAIN_VARIANT_REGULAR, CHAIN_VARIANT_TRACED = 1, 2     # esr_debug_chain_last_variant (| rows per wave << 8)
 BN_STATS, BN_FINALIZE, BN_APPLY, BN_BWD_REDUCE, BN_BWD_FINAL, BN_BWD_APPLY, BN_RESTAT, BN_FIN_APPLY = 0, 1, 2, 3, 4, 5, 6, 7
 NO_LAYER = 0xFFFFFFFF
 POOL_FWD, POOL_BWD, POOL_SHUFFLE, POOL_UNSHUFFLE = 0, 1, 2, 3      # esr_pool.mode
@@ -298,7 +299,7 @@ EXPORTS = ['esr_packed_weight_bytes', 'esr_g32_dims', 'esr_conv_forward', 'esr_p
            'esr_abi_version', 'esr_sizeof_op', 'esr_rdb_forward', 'esr_rdb_workspace_bytes', 'esr_rdb_weight_stream_bytes',
            'esr_rdb_max_tiles_per_image', 'esr_gather_fragments', 'esr_image_metrics', 'esr_wgrad_workspace_elems',
            'esr_l1_loss_forward', 'esr_ragan_loss_forward', 'esr_rdb_wgrad_run', 'esr_rdb_wgrad_workspace_elems', 'esr_rdb_backward',
-           'esr_rdb_mask_bytes', 'esr_rdb_check_abort', 'esr_debug_hold_cus', 'esr_debug_device_alias', 'esr_debug_chain_order_waits',
+           'esr_rdb_mask_bytes', 'esr_rdb_check_abort', 'esr_debug_hold_cus', 'esr_debug_device_alias', 'esr_debug_chain_order_waits', 'esr_debug_chain_last_variant', 'esr_debug_chain_force_general',
            'esr_debug_mfma_probe', 'esr_debug_rdb_wgrad_follow', 'esr_dihedral_op', 'esr_tile_op',
            'esr_tile_x8_op', 'esr_l2_loss_forward', 'esr_fold3_op', 'esr_gan_loss_forward',
            'esr_batch_assemble', 'esr_tile_many_op']
@@ -351,6 +352,7 @@ def lib():
         L.esr_rdb_mask_bytes.argtypes = [C.c_int32] * 3
         L.esr_debug_chain_order_waits.restype = C.c_uint64
         L.esr_debug_device_alias.argtypes = [C.c_int32]
+        L.esr_debug_chain_force_general.argtypes = [C.c_int32]
         L.esr_rdb_wgrad_workspace_elems.restype = C.c_int64
         L.esr_rdb_wgrad_workspace_elems.argtypes = [C.c_int32] * 4
         for name, st in (('esr_conv_forward', esr_conv), ('esr_pack_conv_weights', esr_pack),

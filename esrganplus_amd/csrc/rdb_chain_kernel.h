@@ -475,6 +475,13 @@ template <int K> __device__ __forceinline__ void halo_issue(const ImgView& v, in
 #pragma unroll
   for (int c = 0; c < K; ++c) h.q[c] = __builtin_amdgcn_raw_buffer_load_b128(v.r, hsrc >= 0 ? (g0 + c) * v.gs + hsrc : 0, 0, 16);
 }
+// the registers start a new, undefined life here (no instruction).  The bulk hooks fill them under `if (early)` and the
+// code behind the bulk under `if (!early)`; left at that, the compiler sees a path on which they keep their previous
+// contents and carries those through the block tail into the next block — where no register is free: a scratch spill.
+template <int K> __device__ __forceinline__ void halo_fresh(HaloRegs<K>& h) {
+#pragma unroll
+  for (int c = 0; c < K; ++c) asm volatile("" : "=v"(h.q[c]));
+}
 template <int K> __device__ __forceinline__ void halo_put(char* smem, int slot0, int hsrc, int hdst, const HaloRegs<K>& h) {
   if (hsrc >= 0) {
 #pragma unroll
@@ -815,7 +822,11 @@ template <typename T, int A, int B> __device__ __forceinline__ void wait_units(c
 // step.  Source and LDS address of a run are set up ONCE per unit; the requests themselves differ only in the
 // instruction's immediate offset, which the LDS-DMA adds to the global AND the LDS address (i * 1024 here): a
 // request is one instruction in the shadow of the MFMA issued before it, not an address computation.
-struct Ahead { const char* src; char* dst; int cnt; };
+// src = the block's stream (wave-uniform, in SGPRs anyway) + ONE 32-bit per-lane offset: the request takes the
+// SGPR-base + VGPR-offset form, and what the compiler keeps per unit (hoisted out of the block loop, i.e. in a spilled
+// lane that is re-read every block) is one word, not a 64-bit sum.  dst = the LDS address as a provably uniform word:
+// M0 is a plain s_mov per request (a VGPR-resident address costs a v_readfirstlane in front of each).
+struct Ahead { const char* src; uint32_t dst; int cnt; };
 template <typename S, int I>
 __device__ __forceinline__ Ahead ahead_of(const WStream& s, const Tile& t, char* smem, uint32_t lane16) {
   constexpr int J = I + AH;
@@ -825,8 +836,9 @@ __device__ __forceinline__ Ahead ahead_of(const WStream& s, const Tile& t, char*
   Ahead a;
   a.cnt = (((t.wave + 1) * dj.nf) >> 2) - start;
   if ((wrap && !s.wnext) || (ESR_ABL & 1)) a.cnt = 0;
-  a.src = (wrap ? s.wnext : s.w) + (dj.off + start) * 1024 + (size_t)lane16;
-  a.dst = smem + WOFF + ((s.ring + J) & (WR - 1)) * WSLOT + start * 1024;
+  a.src = (wrap ? s.wnext : s.w) + (size_t)((uint32_t)((dj.off + start) * 1024) + lane16);
+  a.dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem + WOFF +
+                                                       ((s.ring + J) & (WR - 1)) * WSLOT + start * 1024));
   return a;
 }
 // SURE = requests every wave issues unconditionally (nf >> 2 of a unit of this block; none when the unit may
@@ -836,7 +848,7 @@ template <int I_, int SURE = 0, int MAXC = 4> __device__ __forceinline__ void is
   if constexpr (I_ < 4 && I_ < MAXC) {
     if (I_ < SURE || I_ < a.cnt)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)a.src,
-                                       (__attribute__((address_space(3))) void*)a.dst, 16, I_ * 1024, 0);
+                                       (__attribute__((address_space(3))) void*)(uintptr_t)a.dst, 16, I_ * 1024, 0);
   }
 }
 template <typename S, int I> constexpr int sure_ahead() {
@@ -1087,7 +1099,7 @@ __device__ __forceinline__ void run_units_s(Acc24& acc, const WStream& s, char* 
     const uint32_t lbn = lds_rows + S::slot(dn) * ASLOT + colofs[S::nkw(dn) == 3 ? 0 : dn.kw];
     const uint32_t lwn = lds0 + WOFF + ((s.ring + I + 1) & (WR - 1)) * WSLOT + lane16;
     const Ahead ah = ahead_of<S, I>(s, t, smem, lane16);
-    auto issue = [&](auto SI) __attribute__((always_inline)) { issue_one<decltype(SI)::value, sure_ahead<S, I>()>(ah); };
+    auto issue = [&](auto SI) __attribute__((always_inline)) { issue_one<decltype(SI)::value, sure_ahead<S, I>(), most_ahead<S, I>()>(ah); };
     if constexpr (I > I0) hook(std::integral_constant<int, I - 1>{}, PhC<PH_IN>{});
     if constexpr (I + 1 < I1) hook(std::integral_constant<int, I>{}, PhC<PH_START>{});
     auto mid = [&]() __attribute__((always_inline)) {
@@ -1206,8 +1218,10 @@ struct PS {
 struct PSB : PS {
   int band_rows, band_margin, img_H;
 };
-template <typename PT>
+// TRC false (the production fp16 instantiations): no stamp, no test, no event counter
+template <bool TRC = true, typename PT>
 __device__ __forceinline__ void trace_ev(const PT& p, int tile, int& ev) {
+  if constexpr (!TRC) return;
   if (p.trace && ev >= 0 && ev < 64 && threadIdx.x == 0) p.trace[(int64_t)tile * 64 + ev] = (ESR_ABL & 16) ? __builtin_amdgcn_s_memtime() : __builtin_amdgcn_s_memrealtime();
   if (ev >= 0) ++ev;
 }
@@ -1227,7 +1241,10 @@ __device__ __forceinline__ void publish(unsigned* flags, int tile, unsigned epoc
 
 // wave 0, lanes 0..7 poll one neighbour each (relaxed, agent scope) until all reached `epoch`.
 // Returns false (whole workgroup) on abort / time-out.
-template <typename PT = esr_rdb_chain>
+// NBR_LDS (fp16 path): the flag each lane polls comes from the table stage_nbr() left in the LDS (absent neighbours:
+// the tile's own flag, which is up) instead of being worked out again from the tile's coordinates — those sit in
+// spilled SGPRs by then, five reloads per poll site.
+template <bool NBR_LDS = false, typename PT = esr_rdb_chain>
 __device__ __forceinline__ bool wait_neighbours(unsigned* ws, unsigned epoch, char* smem, const Tile& t,
                                                 const PT* tp = nullptr, int* ev = nullptr, int tile_ = 0) {
   if constexpr ((ESR_ABL & 1024) != 0) { if (tp) trace_ev(*tp, tile_, *ev); __syncthreads(); return true; }   // "free hand-off" bound
@@ -1235,7 +1252,10 @@ __device__ __forceinline__ bool wait_neighbours(unsigned* ws, unsigned epoch, ch
     // the neighbour this lane polls (lanes 0..7)
     const int lane = t.lane();
     int my_nbr_tile = -1;
-    if (lane < 8) {
+    if constexpr (NBR_LDS) {
+      const int off = lds_word(smem, LDS_NBR + lane * 4);
+      if (lane < 8) my_nbr_tile = (off >> 2) - WS_HDR;
+    } else if (lane < 8) {
       const int k = lane < 4 ? lane : lane + 1;
       const int ny = t.ty + k / 3 - 1, nx = t.tx + k % 3 - 1;
       if (ny >= 0 && ny < t.tiles_y && nx >= 0 && nx < t.tiles_x) my_nbr_tile = (t.b * t.tiles_y + ny) * t.tiles_x + nx;
@@ -1247,17 +1267,20 @@ __device__ __forceinline__ bool wait_neighbours(unsigned* ws, unsigned epoch, ch
       if (!ok) ok = __hip_atomic_load((gu32*)(ws + WS_HDR + my_nbr_tile), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= epoch;
       if (__all(ok)) break;
       // the abort word is a second dependent round trip: look at it (and at the clock) every 16th turn only
-      if ((it & 15u) == 0u && ((__builtin_amdgcn_s_memrealtime() - t0) > 100000000ull ||      // 1 s of the 100 MHz counter
-                               __hip_atomic_load((gu32*)(ws + WS_ABORT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
+      if (__builtin_expect((it & 15u) == 0u && ((__builtin_amdgcn_s_memrealtime() - t0) > 100000000ull ||      // 1 s of the 100 MHz counter
+                               __hip_atomic_load((gu32*)(ws + WS_ABORT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u), 0)) {
         dead = true;
         break;
       }
     }
     if (lane == 0) {
-      if (dead) {
+      if (__builtin_expect(dead, 0)) {
         __hip_atomic_store((gu32*)(ws + WS_ABORT), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // sticky report for the host (pinned memory, read without a synchronisation at the library's next entry)
-        unsigned* const ha = *(unsigned* volatile*)(smem + LDS_CTRL + 48);
+        // (two asm LDS reads: a compiler-visible read of `smem` here keeps its generic address in a VGPR pair from the
+        // kernel's first instruction to this cold path, through every MFMA segment — a scratch spill)
+        const uint64_t ha_lo = (uint32_t)lds_word(smem, LDS_CTRL + 48), ha_hi = (uint32_t)lds_word(smem, LDS_CTRL + 52);
+        unsigned* const ha = (unsigned*)((ha_hi << 32) | ha_lo);
         if (ha) __hip_atomic_store(ha, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
       *(volatile int*)(smem + LDS_CTRL + 16) = dead ? 1 : 0;
@@ -1330,14 +1353,15 @@ template <typename T> struct RowsRaw { typename Ch16<T>::Raw q[R]; };
 // `live` false: the same loads at an offset past num_records — the buffer range check answers 0 without touching
 // memory.  The RRDB residual rows are fetched this way in EVERY block: a load under `if (has_res2)` whose result is
 // used under another `if (has_res2)` makes hipcc send the rows through scratch one by one, each behind a vmcnt(0).
-template <typename T, typename PT>
+// REG: the tile lies inside the image, nothing to clamp
+template <typename T, bool REG = false, typename PT>
 __device__ __forceinline__ void load_rows(const ImgView& v, int cb, const PT& p, const Tile& t, RowsRaw<T>& o, bool live = true) {
   const int lane = t.lane();
   const int ox = t.ox0 + (lane & 31), oyb = t.oy0 + t.wave * R, wp32 = p.dense.wp * 32;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    const int oy = oyb + r < p.H ? oyb + r : p.H - 1;            // clamped: rows / columns past the image are not used
-    const int off = (oy + 1) * wp32 + (ox < p.W ? ox + 1 : 1) * 32;
+    const int oy = (REG || oyb + r < p.H) ? oyb + r : p.H - 1;   // clamped: rows / columns past the image are not used
+    const int off = (oy + 1) * wp32 + ((REG || ox < p.W) ? ox + 1 : 1) * 32;
     Ch16<T>::load(v, live ? cb : 0, lane >> 5, live ? off : (int)0x80000000u, o.q[r]);
   }
 }
@@ -1378,7 +1402,7 @@ struct BlkS {
 // lrelu(acc + bias) for the lane's channel e (set: slope 0.2) — as 8 bytes per lane into the tile's mask record (mask_base: this tile's record, MASK_TILE bytes;
 // slice 0..3 = a1..a4): x2 and x4 carry residuals, so the sign of their pre-activation cannot be read off the
 // stored slice.
-template <typename T, int BLK, int MODE, int LW = 0, bool NOISE = true, bool TRAIN = false, typename PT = esr_rdb_chain>
+template <typename T, int BLK, int MODE, int LW = 0, bool NOISE = true, bool TRAIN = false, bool REG = false, typename PT = esr_rdb_chain>
 __device__ __forceinline__ void epilogue(Acc24& acc, const PT& p, const BlkS& blk, const Bias16& bias,
                                          const ImgView& out, int out_cb, int ch_cb, const RowsRaw<T>* ex,
                                          const RowsRaw<T>* r2, bool has_res2, const Tile& t, char* smem = nullptr,
@@ -1393,7 +1417,8 @@ __device__ __forceinline__ void epilogue(Acc24& acc, const PT& p, const BlkS& bl
   const f32x4 (&bq)[4] = bias.q;
   const int wp32 = p.dense.wp * 32;
   constexpr bool BAND = std::is_same_v<PT, PSB>;
-  const bool ragged = BAND || t.oy0 + TH > p.H || t.ox0 + TW > p.W;      // wave-uniform
+  static_assert(!(REG && BAND), "a band has rows outside the image");
+  const bool ragged = !REG && (BAND || t.oy0 + TH > p.H || t.ox0 + TW > p.W);      // wave-uniform
   const uint32_t layer1 = blk.layer1, layer2 = blk.layer2;
   const bool n1 = MODE == 3 && NOISE && p.noise_mode == ESR_NOISE_PHILOX && layer1 != ESR_NO_LAYER;
   const bool n2 = MODE == 3 && NOISE && p.noise_mode == ESR_NOISE_PHILOX && layer2 != ESR_NO_LAYER && has_res2;
@@ -1465,7 +1490,7 @@ __device__ __forceinline__ void epilogue(Acc24& acc, const PT& p, const BlkS& bl
       }
     }
     // pixels beyond the image: offset 2^31 lies past num_records (2^31 - 1), the buffer range check drops the store
-    bool live = oy < p.H && ox < p.W;          // a pixel of the image
+    bool live = REG || (oy < p.H && ox < p.W); // a pixel of the image
     bool inside = live;                        // ... that this epilogue stores
     if constexpr (BAND) {
       // a band's view covers band_margin rows of its neighbours (recomputed here, owned there) and, at the ends of
@@ -1691,12 +1716,18 @@ __device__ __forceinline__ void tail_bwd(Acc24& acc, const PT& p, const BlkS& bl
 // scratch around every hand-off of the training forward (a vmcnt(0) per reload with weight DMAs in flight, +0.9 us
 // per phase), and the inference kernel spilled 64 KB per tile and block on behalf of a noisy tail it never ran
 // (2.5 GB of HBM writes per launch, profiles/r03_experiments.md).
-template <typename T, int DIR = 0, bool BAND = false, int NZ = -1>
+// TRC: the trace stamps (esr_rdb_chain.trace; tools/chain_trace*.py, the ESR_ABL timing builds).  The fp16 launches run
+// the instantiations without them unless the launch asks for a trace (rdb_traced*.hip hold the traced ones): 32 stamp
+// sites, each a run-time test + address arithmetic + store in code where nothing hides an instruction.
+// REG (fp16 inference, no bands): every tile lies inside the image (H a multiple of TH, W of TW — the host checks),
+// so nothing is ragged, every pixel is live and the row / column clamps fold away.
+template <typename T, int DIR = 0, bool BAND = false, int NZ = -1, bool TRC = true, bool REG = false>
 __global__ __launch_bounds__(NT, 1) void rdb_chain_kernel(const esr_rdb_chain p, const int ntiles, const int tiles_x,
                                                           const int tiles_y, unsigned* const host_abort) {
   using CF = Cfg<T>;
   static_assert(DIR == 0 || sizeof(T) == 2, "training forward / backward chains: fp16");
   static_assert(DIR == 0 || !BAND, "row bands: inference forward only");
+  static_assert(!REG || (DIR == 0 && !BAND && sizeof(T) == 2), "regular geometry: fp16 inference without bands");
   __shared__ __attribute__((aligned(16))) char smem[DIR == 2 ? LDS_BYTES_BWD : LDS_BYTES];
   unsigned* const ws = (unsigned*)p.workspace;
   unsigned* const flags = ws + WS_HDR;
@@ -1715,7 +1746,7 @@ __global__ __launch_bounds__(NT, 1) void rdb_chain_kernel(const esr_rdb_chain p,
     // the Philox key is resolved here, once (graph replay reads it from device memory)
     ps.sigma = p.sigma; ps.seed = p.seed_dev ? __builtin_nontemporal_load(p.seed_dev) : p.seed; ps.seed_dev = nullptr;
     ps.dense.wp = __builtin_amdgcn_readfirstlane(p.dense.wp);
-    ps.trace = p.trace;
+    if constexpr (TRC) ps.trace = p.trace; else ps.trace = nullptr;
     ps.band_rows = __builtin_amdgcn_readfirstlane(p.band_rows); ps.band_margin = __builtin_amdgcn_readfirstlane(p.band_margin);
     ps.img_H = __builtin_amdgcn_readfirstlane(p.img_H);
   }
@@ -1761,7 +1792,7 @@ __global__ __launch_bounds__(NT, 1) void rdb_chain_kernel(const esr_rdb_chain p,
       const ImgView xin0 = img_view(p.blocks[0].x_in, t.b);
       const bool noisy = NZ != 0 && p.noise_mode != ESR_NOISE_OFF;
       RowsRaw<T> c0, c1;
-      load_rows<T>(xin0, 0, q, t, c0); load_rows<T>(xin0, 1, q, t, c1);
+      load_rows<T, REG>(xin0, 0, q, t, c0); load_rows<T, REG>(xin0, 1, q, t, c1);
       // (backward: g_x's accumulators start at g_t itself; training forward: always the folded form)
       const float cs = DIR == 2 ? 1.f : ((noisy && DIR == 0) ? 0.f : 5.f);
       sfor<R>([&](auto RR) __attribute__((always_inline)) {
@@ -1781,9 +1812,9 @@ __global__ __launch_bounds__(NT, 1) void rdb_chain_kernel(const esr_rdb_chain p,
     }
     for (int rb = 0; rb < p.n_blocks; ++rb) {
       const esr_rdb_block& blk = p.blocks[rb];
-      ev = rb == 1 ? 0 : -1;
-      ws_.dbg = ((ESR_ABL & 32) && rb == 1 && q.trace) ? q.trace + (int64_t)tile * 64 + 32 : nullptr;
-      trace_ev(q, tile, ev);
+      if constexpr (TRC) ev = rb == 1 ? 0 : -1;
+      if constexpr (TRC && (ESR_ABL & 32) != 0) ws_.dbg = (rb == 1 && q.trace) ? q.trace + (int64_t)tile * 64 + 32 : nullptr;
+      trace_ev<TRC>(q, tile, ev);
       const char* const w = uniform_ptr(blk.w);
       const char* const xin_b = (const char*)blk.x_in.ptr + (int64_t)t.b * blk.x_in.batch_stride;
       const ImgView xin = img_view(blk.x_in, t.b), xout = img_view(blk.x_out, t.b);
@@ -1847,16 +1878,17 @@ if constexpr (DIR == 2) {
               lds_old2(pr.tag, pr.hsrc);
               early = (ESR_ABL & 1024) ? 1 : __builtin_amdgcn_readfirstlane((int)(pr.tag == epoch));
               if (early) halo_issue<CF::KD>(dblk, g0, (int)pr.hsrc, hq);
+              else halo_fresh(hq);
             }
           }
         };
         auto finish_halo = [&](int g0, int slot0) __attribute__((always_inline)) -> bool {
           const int hsrc = lds_word(smem, LDS_HALO + t.tid() * 8), hdst = lds_word(smem, LDS_HALO + t.tid() * 8 + 4);
-          if (!early) {
-            if (!wait_neighbours(ws, epoch, smem, t, &q, &ev, tile)) return false;
+          if (__builtin_expect(!early, 0)) {   // a late neighbour: the blocking poll sits behind the loop
+            if (!wait_neighbours<true>(ws, epoch, smem, t, TRC ? &q : nullptr, &ev, tile)) return false;
             halo_issue<CF::KD>(dblk, g0, hsrc, hq);
           } else {
-            trace_ev(q, tile, ev);
+            trace_ev<TRC>(q, tile, ev);
           }
           halo_put<CF::KD>(smem, slot0, hsrc, hdst, hq);
           __syncthreads();
@@ -1864,7 +1896,7 @@ if constexpr (DIR == 2) {
         };
         mask_dma(3, 0);                      // a4's masks (first epilogue), a3's (second)
         mask_dma(2, 1);
-        if (rb == 0) {
+        if (__builtin_expect(rb == 0, 0)) {     // once per tile: laid out behind the block loop
           sfor<AH>([&](auto UI) __attribute__((always_inline)) {
             const Ahead ah = ahead_of<S, decltype(UI)::value - AH>(ws_, t, smem, (uint32_t)t.lane() * 16u);
             sfor<4>([&](auto X) __attribute__((always_inline)) { issue_one<decltype(X)::value>(ah); });
@@ -1874,54 +1906,54 @@ if constexpr (DIR == 2) {
           });
           wait_vm<0>();
         } else {
-          if (!wait_neighbours(ws, epoch, smem, t, &q, &ev, tile)) return;
+          if (!wait_neighbours<true>(ws, epoch, smem, t, TRC ? &q : nullptr, &ev, tile)) return;
           halo_fetch<CF::KX>(xin, 0, smem, t);
         }
         __syncthreads();
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         // ---------------- g_x4 -> g_a4 (kept in registers: g_t still occupies the slots)
         seg_open(acc);
         run_units_s<S, S::first(U_CRIT, 1), S::end(U_CRIT, 1), false, false>(acc, ws_, smem, t);
         seg_close(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         prewait_units<S, S::first(U_BULK, 1)>(ws_);     // bulk_1's first weights, in front of the epilogue's stores
         mfma_drain();
         RowsRaw<T> s1;
         epilogue_bwd<T, 0, 2>(acc, q, dblk, 0, t, smem, 0, &s1, 0);
         ++epoch;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         seg_open(acc);
         run_units_s<S, S::first(U_BULK, 1), S::end(U_BULK, 1), true, false, true>(acc, ws_, smem, t, [&](auto IDX, auto PH) __attribute__((always_inline)) { bulk_hook(IDX, PH, std::integral_constant<int, S::first(U_BULK, 1)>{}, std::integral_constant<int, S::end(U_BULK, 1)>{}, 0, 1, 0); });
         seg_close(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         __builtin_amdgcn_s_barrier();          // every wave done reading g_t in slots 0, 1
         { const int lane = t.lane(); int opx, osw; t.own(lane, opx, osw);
 #pragma unroll
           for (int r = 0; r < R; ++r) lds_put_row(smem, lane >> 5, r, s1.q[r].q, opx, osw); }
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         if (!finish_halo(0, 0)) return;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         // ---------------- g_x3 -> g_a3
         seg_open(acc);
         run_units_s<S, S::first(U_CRIT, 2), S::end(U_CRIT, 2), false, false>(acc, ws_, smem, t);
         seg_close(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         prewait_units<S, S::first(U_BULK, 2)>(ws_);     // bulk_2's first weights, in front of the epilogue's stores
         mfma_drain();
         epilogue_bwd<T, 1, 1>(acc, q, dblk, 1, t, smem, 2, nullptr, 1);
         ++epoch;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         seg_open(acc);
         run_units_s<S, S::first(U_BULK, 2), S::end(U_BULK, 2), true, false, true>(acc, ws_, smem, t, [&](auto IDX, auto PH) __attribute__((always_inline)) { bulk_hook(IDX, PH, std::integral_constant<int, S::first(U_BULK, 2)>{}, std::integral_constant<int, S::end(U_BULK, 2)>{}, CF::KD, 0, 1); });
         seg_close(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         if (!finish_halo(CF::KD, 2)) return;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         // ---------------- g_x2: unmasked -> aux and, through the transposed 1x1, into g_x; masked -> g_a2
         seg_open(acc);
         run_units_s<S, S::first(U_CRIT, 3), S::end(U_CRIT, 3), false, false>(acc, ws_, smem, t);
         seg_close(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         { OneT one;
           load_1x1t<S>(one, ws_, smem, t);
           prewait_units<S, S::first(U_BULK, 3)>(ws_);     // bulk_3's first weights, in front of the epilogue's stores
@@ -1929,43 +1961,43 @@ if constexpr (DIR == 2) {
           epilogue_bwd<T, 2, 1, true>(acc, q, dblk, 2, t, smem, 0, nullptr, 0, &aux, &one);
           seg_close(acc); }                 // (the epilogue's own MFMAs into g_x)
         ++epoch;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         seg_open<3>(acc);
         run_units_s<S, S::first(U_BULK, 3), S::end(U_BULK, 3), true, false, true>(acc, ws_, smem, t, [&](auto IDX, auto PH) __attribute__((always_inline)) { bulk_hook(IDX, PH, std::integral_constant<int, S::first(U_BULK, 3)>{}, std::integral_constant<int, S::end(U_BULK, 3)>{}, 2 * CF::KD, -1, 0); });
         seg_close<3>(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         if (!finish_halo(2 * CF::KD, 0)) return;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         // ---------------- g_x1 -> g_a1
         seg_open<3>(acc);
         run_units_s<S, S::first(U_CRIT, 4), S::end(U_CRIT, 4), false, false>(acc, ws_, smem, t);
         seg_close<3>(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         prewait_units<S, S::first(U_BULK, 4)>(ws_);     // bulk_4's first weights, in front of the epilogue's stores
         mfma_drain();
         epilogue_bwd<T, 3, 1>(acc, q, dblk, 3, t, smem, 2, nullptr, 1);
         ++epoch;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         seg_open<4>(acc);
         run_units_s<S, S::first(U_BULK, 4), S::end(U_BULK, 4), true, false, true>(acc, ws_, smem, t, [&](auto IDX, auto PH) __attribute__((always_inline)) { bulk_hook(IDX, PH, std::integral_constant<int, S::first(U_BULK, 4)>{}, std::integral_constant<int, S::end(U_BULK, 4)>{}, 3 * CF::KD, -1, 0); });
         seg_close<4>(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         if (!finish_halo(3 * CF::KD, 2)) return;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         RowsRaw<T> tr0, tr1;
         // ---------------- g_x; block tail
         seg_open<4>(acc);
         run_units_s<S, S::first(U_CRIT, 5), S::end(U_CRIT, 5)>(acc, ws_, smem, t);
         seg_close<4>(acc);
         load_rows<T>(res2, 0, q, t, tr0, has_res2); load_rows<T>(res2, 1, q, t, tr1, has_res2);   // (see the forward)
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         mfma_drain();
         tail_bwd<T, 4>(acc, q, bs, xout, 0, &tr0, has_res2, out_a, has_out_a, t, smem, 0);
         tail_bwd<T, 5>(acc, q, bs, xout, 1, &tr1, has_res2, out_a, has_out_a, t, smem, 2);
         pin_acc45(acc);
-        publish(flags, tile, ++epoch, t, &q, &ev);
+        publish(flags, tile, ++epoch, t, TRC ? &q : nullptr, &ev);
         ws_.ring = (ws_.ring + S::N) & (WR - 1);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         } else {
         // =========================== fp16: own pixels stay in the LDS ===========================
         using S = Sched<T>;
@@ -2007,24 +2039,25 @@ if constexpr (DIR == 2) {
               lds_old2(pr.tag, pr.hsrc);
               early = (ESR_ABL & 1024) ? 1 : __builtin_amdgcn_readfirstlane((int)(pr.tag == epoch));
               if (early) halo_issue<CF::KD>(dblk, g0, (int)pr.hsrc, hq);
+              else halo_fresh(hq);
             }
           }
         };
         // after the bulk: the halo of stage g0 into slots slot0..
         auto finish_halo = [&](int g0, int slot0) __attribute__((always_inline)) -> bool {
           const int hsrc = lds_word(smem, LDS_HALO + t.tid() * 8), hdst = lds_word(smem, LDS_HALO + t.tid() * 8 + 4);
-          if (!early) {
-            if (!wait_neighbours(ws, epoch, smem, t, &q, &ev, tile)) return false;
+          if (__builtin_expect(!early, 0)) {   // a late neighbour: the blocking poll sits behind the loop
+            if (!wait_neighbours<true>(ws, epoch, smem, t, TRC ? &q : nullptr, &ev, tile)) return false;
             halo_issue<CF::KD>(dblk, g0, hsrc, hq);
           } else {
-            trace_ev(q, tile, ev);
+            trace_ev<TRC>(q, tile, ev);
           }
           halo_put<CF::KD>(smem, slot0, hsrc, hdst, hq);
           __syncthreads();
           return true;
         };
         stage_bias(bs.bias, smem, t);          // every wave is past the previous block's tail (publish)
-        if (rb == 0) {
+        if (__builtin_expect(rb == 0, 0)) {     // once per tile: laid out behind the block loop
           // the chain's input comes from another launch: stage all of x (with halo) by DMA, and start
           // the weight stream (its first three units)
           sfor<AH>([&](auto UI) __attribute__((always_inline)) {
@@ -2037,28 +2070,28 @@ if constexpr (DIR == 2) {
           wait_vm<0>();
         } else {
           // own pixels were written by the previous block's epilogue; weights are in flight already
-          if (!wait_neighbours(ws, epoch, smem, t, &q, &ev, tile)) return;
+          if (!wait_neighbours<true>(ws, epoch, smem, t, TRC ? &q : nullptr, &ev, tile)) return;
           halo_fetch<CF::KX>(xin, 0, smem, t);
         }
         __syncthreads();
         Bias16 bb;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         // ---------------- conv1
         seg_open(acc);
         run_units<T, S::first(U_CRIT, 1), S::end(U_CRIT, 1), false, false>(acc, ws_, smem, t);
         seg_close(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         lds_bias(smem, 0, t, bb);
         prewait_units<S, S::first(U_BULK, 1)>(ws_);     // bulk_1's first weights, in front of the epilogue's stores
         mfma_drain();
         RowsRaw<T> x1, x2;
-        epilogue<T, 0, 0, 2, true, TR>(acc, q, bs, bb, dblk, 0, 0, nullptr, nullptr, false, t, smem, 0, &x1, 0.f, true, mbase, 0);     // x1 (kept: x still occupies its slots)
+        epilogue<T, 0, 0, 2, true, TR, REG>(acc, q, bs, bb, dblk, 0, 0, nullptr, nullptr, false, t, smem, 0, &x1, 0.f, true, mbase, 0);     // x1 (kept: x still occupies its slots)
         ++epoch;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         seg_open(acc);
         run_units<T, S::first(U_BULK, 1), S::end(U_BULK, 1), true, false, true>(acc, ws_, smem, t, [&](auto IDX, auto PH) __attribute__((always_inline)) { bulk_hook(IDX, PH, std::integral_constant<int, S::first(U_BULK, 1)>{}, std::integral_constant<int, S::end(U_BULK, 1)>{}, 0); });
         seg_close(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         // ---------------- P = conv1x1(x) from the resident x; then x1 may take x's slots
         seg_open(acc);
         run_1x1_res<T>(acc, ws_, smem, t);
@@ -2067,71 +2100,71 @@ if constexpr (DIR == 2) {
         { const int lane = t.lane(); int opx, osw; t.own(lane, opx, osw);
 #pragma unroll
           for (int r = 0; r < R; ++r) lds_put_row(smem, lane >> 5, r, x1.q[r].q, opx, osw); }
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         if (!finish_halo(0, 0)) return;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         // ---------------- conv2
         seg_open(acc);
         run_units<T, S::first(U_CRIT, 2), S::end(U_CRIT, 2), false, false>(acc, ws_, smem, t);
         seg_close(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         lds_bias(smem, 32, t, bb);
         prewait_units<S, S::first(U_BULK, 2)>(ws_);     // bulk_2's first weights, in front of the epilogue's stores
         mfma_drain();
-        epilogue<T, 1, 1, 1, true, TR>(acc, q, bs, bb, dblk, 1, 0, nullptr, nullptr, false, t, smem, 2, nullptr, 0.f, true, mbase, 1);       // x2
+        epilogue<T, 1, 1, 1, true, TR, REG>(acc, q, bs, bb, dblk, 1, 0, nullptr, nullptr, false, t, smem, 2, nullptr, 0.f, true, mbase, 1);       // x2
         ++epoch;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         seg_open(acc);
         run_units<T, S::first(U_BULK, 2), S::end(U_BULK, 2), true, false, true>(acc, ws_, smem, t, [&](auto IDX, auto PH) __attribute__((always_inline)) { bulk_hook(IDX, PH, std::integral_constant<int, S::first(U_BULK, 2)>{}, std::integral_constant<int, S::end(U_BULK, 2)>{}, CF::KD); });
         seg_close(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         if (!finish_halo(CF::KD, 2)) return;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         // ---------------- conv3
         seg_open(acc);
         run_units<T, S::first(U_CRIT, 3), S::end(U_CRIT, 3), false, false>(acc, ws_, smem, t);
         seg_close(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         lds_bias(smem, 64, t, bb);
         prewait_units<S, S::first(U_BULK, 3)>(ws_);     // bulk_3's first weights, in front of the epilogue's stores
         mfma_drain();
-        epilogue<T, 2, 0, 1, true, TR>(acc, q, bs, bb, dblk, 2, 0, nullptr, nullptr, false, t, smem, 0, nullptr, 0.f, true, mbase, 2);       // x3
+        epilogue<T, 2, 0, 1, true, TR, REG>(acc, q, bs, bb, dblk, 2, 0, nullptr, nullptr, false, t, smem, 0, nullptr, 0.f, true, mbase, 2);       // x3
         ++epoch;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         seg_open<3>(acc);
         run_units<T, S::first(U_BULK, 3), S::end(U_BULK, 3), true, false, true>(acc, ws_, smem, t, [&](auto IDX, auto PH) __attribute__((always_inline)) { bulk_hook(IDX, PH, std::integral_constant<int, S::first(U_BULK, 3)>{}, std::integral_constant<int, S::end(U_BULK, 3)>{}, 2 * CF::KD); });
         seg_close<3>(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         if (!finish_halo(2 * CF::KD, 0)) return;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         // ---------------- conv4
         seg_open<3>(acc);
         run_units<T, S::first(U_CRIT, 4), S::end(U_CRIT, 4), false, false>(acc, ws_, smem, t);
         seg_close<3>(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         lds_bias(smem, 96, t, bb);
         lds_get_rows(smem, 2, x2.q, t);   // x2's own pixels still sit in the slots x4 is about to take
         prewait_units<S, S::first(U_BULK, 4)>(ws_);     // bulk_4's first weights, in front of the epilogue's stores
         mfma_drain();
-        epilogue<T, 3, 2, 1, true, TR>(acc, q, bs, bb, dblk, 3, 0, &x2, nullptr, false, t, smem, 2, nullptr, 0.f, true, mbase, 3);           // x4 (+ x2)
+        epilogue<T, 3, 2, 1, true, TR, REG>(acc, q, bs, bb, dblk, 3, 0, &x2, nullptr, false, t, smem, 2, nullptr, 0.f, true, mbase, 3);           // x4 (+ x2)
         RowsRaw<T> tx0, tx1, tr0, tr1;
         ++epoch;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         seg_open<4>(acc);
         run_units<T, S::first(U_BULK, 4), S::end(U_BULK, 4), true, false, true>(acc, ws_, smem, t, [&](auto IDX, auto PH) __attribute__((always_inline)) { bulk_hook(IDX, PH, std::integral_constant<int, S::first(U_BULK, 4)>{}, std::integral_constant<int, S::end(U_BULK, 4)>{}, 3 * CF::KD); });
         seg_close<4>(acc);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         if (!finish_halo(3 * CF::KD, 2)) return;
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         // ---------------- conv5; block tail (+ RRDB tail)
         seg_open<4>(acc);
         run_units<T, S::first(U_CRIT, 5), S::end(U_CRIT, 5)>(acc, ws_, smem, t);
         seg_close<4>(acc);
         // the block tail's residual (every third block).  Requested only now: ahead of conv5 hipcc has no registers for
         // the 16 rows and sends every one through scratch behind its own vmcnt(0)
-        load_rows<T>(res2, 0, q, t, tr0, has_res2); load_rows<T>(res2, 1, q, t, tr1, has_res2);
+        load_rows<T, REG>(res2, 0, q, t, tr0, has_res2); load_rows<T, REG>(res2, 1, q, t, tr1, has_res2);
         if constexpr (!TR) { if (noisy) { load_rows<T>(xin, 0, q, t, tx0); load_rows<T>(xin, 1, q, t, tx1); } }   // rare path: latency exposed
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         mfma_drain();
         Bias16 bb2;
         lds_bias(smem, 128, t, bb);
@@ -2150,13 +2183,13 @@ if constexpr (DIR == 2) {
           epilogue<T, 4, 3, 1, true>(acc, q, bs, bb, xout, 0, 0, &tx0, &tr0, has_res2, t, smem, 0, nullptr, 0.f, full_out);
           epilogue<T, 5, 3, 1, true>(acc, q, bs, bb2, xout, 1, 1, &tx1, &tr1, has_res2, t, smem, 2, nullptr, 0.f, full_out);
         } else {
-          epilogue<T, 4, 3, 1, false>(acc, q, bs, bb, xout, 0, 0, nullptr, &tr0, has_res2, t, smem, 0, nullptr, 5.f, full_out);
-          epilogue<T, 5, 3, 1, false>(acc, q, bs, bb2, xout, 1, 1, nullptr, &tr1, has_res2, t, smem, 2, nullptr, 5.f, full_out);
+          epilogue<T, 4, 3, 1, false, false, REG>(acc, q, bs, bb, xout, 0, 0, nullptr, &tr0, has_res2, t, smem, 0, nullptr, 5.f, full_out);
+          epilogue<T, 5, 3, 1, false, false, REG>(acc, q, bs, bb2, xout, 1, 1, nullptr, &tr1, has_res2, t, smem, 2, nullptr, 5.f, full_out);
         }
         pin_acc45(acc);
-        publish(flags, tile, ++epoch, t, &q, &ev);
+        publish(flags, tile, ++epoch, t, TRC ? &q : nullptr, &ev);
         ws_.ring = (ws_.ring + S::N) & (WR - 1);
-        trace_ev(q, tile, ev);
+        trace_ev<TRC>(q, tile, ev);
         }
       } else {
       // =========================== fp32: every stage by DMA ===========================
@@ -2166,53 +2199,53 @@ if constexpr (DIR == 2) {
       // ---------------- phase 1: x -> conv1..conv5
       issue_w_head<6>(w + CF::phase_off(1), CF::KX, smem, t);
       if (epoch > 0 && !wait_neighbours(ws, epoch, smem, t)) return;
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       run_phase<T, 1>(acc, w + CF::phase_off(1), xin_b, blk.x_in.group_stride, CF::KX, smem, t);
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       mfma_drain();
       epilogue<T, 0, 0>(acc, q, bs, fb[0], dense, 0, 0, nullptr, nullptr, false, t);       // x1
       publish(flags, tile, ++epoch, t);
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       // ---------------- P = conv1x1(x) on own pixels, then phase 2: x1 -> conv2..conv5
       run_1x1<T>(acc, w + CF::phase_off(6), xin_b, blk.x_in.group_stride, smem, t);
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       __syncthreads();                      // every wave done with the 1x1's LDS before phase 2 refills it
       issue_w_head<5>(w + CF::phase_off(2), CF::KD, smem, t);
       if (!wait_neighbours(ws, epoch, smem, t)) return;
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       run_phase<T, 2>(acc, w + CF::phase_off(2), dense_b, d_gs, CF::KD, smem, t);
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       mfma_drain();
       epilogue<T, 1, 1>(acc, q, bs, fb[1], dense, 1, 0, nullptr, nullptr, false, t);     // x2
       publish(flags, tile, ++epoch, t);
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       // ---------------- phase 3: x2 -> conv3..conv5
       issue_w_head<4>(w + CF::phase_off(3), CF::KD, smem, t);
       if (!wait_neighbours(ws, epoch, smem, t)) return;
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       run_phase<T, 3>(acc, w + CF::phase_off(3), dense_b + CF::KD * d_gs, d_gs, CF::KD, smem, t);
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       mfma_drain();
       epilogue<T, 2, 0>(acc, q, bs, fb[2], dense, 2, 0, nullptr, nullptr, false, t);     // x3
       publish(flags, tile, ++epoch, t);
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       // ---------------- phase 4: x3 -> conv4, conv5
       issue_w_head<3>(w + CF::phase_off(4), CF::KD, smem, t);
       if (!wait_neighbours(ws, epoch, smem, t)) return;
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       run_phase<T, 4>(acc, w + CF::phase_off(4), dense_b + 2 * CF::KD * d_gs, d_gs, CF::KD, smem, t);
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       mfma_drain();
       { RowsRaw<T> x2r; load_rows<T>(dense, 1, p, t, x2r);
         epilogue<T, 3, 2>(acc, q, bs, fb[3], dense, 3, 0, &x2r, nullptr, false, t); }     // x4 (+ x2)
       publish(flags, tile, ++epoch, t);
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       // ---------------- phase 5: x4 -> conv5; block tail (+ RRDB tail)
       issue_w_head<2>(w + CF::phase_off(5), CF::KD, smem, t);
       if (!wait_neighbours(ws, epoch, smem, t)) return;
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       run_phase<T, 5>(acc, w + CF::phase_off(5), dense_b + 3 * CF::KD * d_gs, d_gs, CF::KD, smem, t);
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       mfma_drain();
       { RowsRaw<T> tx0, tx1, tr0, tr1;
         load_rows<T>(xin, 0, p, t, tx0); load_rows<T>(xin, 1, p, t, tx1);
@@ -2220,7 +2253,7 @@ if constexpr (DIR == 2) {
         epilogue<T, 4, 3>(acc, q, bs, fb[4], xout, 0, 0, &tx0, &tr0, has_res2, t);
         epilogue<T, 5, 3>(acc, q, bs, fb[5], xout, 1, 1, &tx1, &tr1, has_res2, t); }
       publish(flags, tile, ++epoch, t);
-      trace_ev(p, tile, ev);
+      trace_ev<TRC>(p, tile, ev);
       }
     }
   }

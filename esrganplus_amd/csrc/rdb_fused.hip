@@ -1,6 +1,6 @@
-// rdb_fused.hip — host entry points of the fused dense-block chain + the inference instantiations of its kernel
-// (csrc/rdb_chain_kernel.h; the training-forward and backward instantiations live in rdb_fused_train.hip /
-// rdb_fused_bwd.hip so that the three compile in parallel).
+// rdb_fused.hip — host entry points of the fused dense-block chain + the general inference instantiations of its kernel
+// (csrc/rdb_chain_kernel.h; the regular-geometry, training-forward, backward and traced instantiations live in
+// rdb_fused_reg.hip / rdb_fused_train.hip / rdb_fused_bwd.hip / rdb_traced_*.hip so that they compile in parallel).
 #include "rdb_chain_kernel.h"
 #include <atomic>
 #include <mutex>
@@ -18,6 +18,20 @@ int esr_rdb_launch_bwd_r2(const esr_rdb_chain& p, int grid, int ntiles, int tile
 int esr_rdb_launch_bwd_r1(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
 int esr_rdb_launch_fwd_r2(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
 int esr_rdb_launch_fwd_r1(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
+// the fp16 inference chain for regular geometry (rdb_fused_reg.hip)
+int esr_rdb_launch_fwd_reg(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
+const void* esr_rdb_fwd_reg_fn();
+// the fp16 chains with the trace stamps, for launches with esr_rdb_chain.trace set (rdb_traced_*.hip, rdb_rows{1,2}_traced_*.hip)
+int esr_rdb_launch_fwd_traced(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
+const void* esr_rdb_fwd_traced_fn();
+int esr_rdb_launch_train_traced(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
+int esr_rdb_launch_bwd_traced(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
+int esr_rdb_launch_fwd_r2_traced(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
+int esr_rdb_launch_fwd_r1_traced(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
+int esr_rdb_launch_train_r2_traced(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
+int esr_rdb_launch_train_r1_traced(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
+int esr_rdb_launch_bwd_r2_traced(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
+int esr_rdb_launch_bwd_r1_traced(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st);
 
 // ---- per-device bookkeeping -------------------------------------------------------------------------------------
 // Everything the library keeps about launches in flight is keyed by DEVICE: nn.DataParallel (networks.py:105-107) drives
@@ -100,6 +114,15 @@ bool capturing(hipStream_t st) {
   return c;
 }
 
+// ESR_RDB_GENERAL=1 (read once): regular shapes run the general inference chain as well (A/B, tests)
+std::atomic<int> g_force_general{-1};             // esr_debug_chain_force_general: 0 / 1 override the environment
+bool force_general() {
+  static const bool v = [] { const char* e = getenv("ESR_RDB_GENERAL"); return e && atoi(e) != 0; }();
+  const int o = g_force_general.load(std::memory_order_relaxed);
+  return o >= 0 ? o != 0 : v;
+}
+std::atomic<int> g_last_variant{0};              // esr_debug_chain_last_variant
+
 bool chain_order_on() {                          // ESR_RDB_ORDER=0: measurement only (tools / experiments)
   static const bool v = [] { const char* e = getenv("ESR_RDB_ORDER"); return !e || atoi(e) != 0; }();
   return v;
@@ -145,6 +168,11 @@ void chain_record_launch(hipStream_t st, int grid) {
 
 // Diagnostic (tests/test_gpu_rdb_chain.py): the number of cross-stream event waits the chain ordering has inserted so far.
 extern "C" uint64_t esr_debug_chain_order_waits(void) { return g_order_waits.load(std::memory_order_relaxed); }
+// Diagnostic (tests/test_gpu_chain_variants.py): the kernel variant the last chain launch of this process ran.
+extern "C" int esr_debug_chain_last_variant(void) { return g_last_variant.load(std::memory_order_relaxed); }
+// .. and the in-process form of ESR_RDB_GENERAL (which is read once): 1 / 0 = general chain forced / not forced whatever
+// the environment says, < 0 = back to the environment.  Returns the previous override.
+extern "C" int esr_debug_chain_force_general(int32_t on) { return g_force_general.exchange(on < 0 ? -1 : (on != 0), std::memory_order_relaxed); }
 
 namespace {
 // Diagnostic: a workgroup that takes 120 KB of LDS (so that no chain workgroup fits next to it on the CU) and sleeps
@@ -290,19 +318,29 @@ int chain_launch(const esr_rdb_chain* p, esr_stream_t stream, const char* who, i
       return ESR_ERR_LAUNCH;
     }
   }
+  // fp16 launches run the instantiations without trace stamps unless the launch asks for a trace; the fp16 inference
+  // chain of a shape that is a whole number of 16x32 tiles runs the instantiation without ragged-tile handling
+  const bool traced = p->trace != nullptr && p->dtype == ESR_F16;
+  const bool regular = p->mode == 0 && p->dtype == ESR_F16 && p->band_rows == 0 && p->noise_mode == ESR_NOISE_OFF && rows == 4 &&
+                       !traced && p->H % (4 * rows) == 0 && p->W % TW == 0 && !force_general();
+  g_last_variant.store((regular ? ESR_CHAIN_VARIANT_REGULAR : 0) | (traced ? ESR_CHAIN_VARIANT_TRACED : 0) | (rows << 8), std::memory_order_relaxed);
   auto dispatch = [&]() -> int {
     if (p->band_rows != 0) {
       if (p->dtype != ESR_F16 && p->dtype != ESR_F32) { esr_set_error("%s: bad dtype %d", who, p->dtype); return ESR_ERR_INVALID; }
-      return esr_rdb_launch_band(*p, grid, ntiles, tiles_x, tiles_y, ha, st);
+      return (traced ? esr_rdb_launch_fwd_traced : esr_rdb_launch_band)(*p, grid, ntiles, tiles_x, tiles_y, ha, st);
     }
     if (p->mode == 1)
-      return (rows == 4 ? esr_rdb_launch_train : rows == 2 ? esr_rdb_launch_train_r2 : esr_rdb_launch_train_r1)(*p, grid, ntiles, tiles_x, tiles_y, ha, st);
+      return (traced ? (rows == 4 ? esr_rdb_launch_train_traced : rows == 2 ? esr_rdb_launch_train_r2_traced : esr_rdb_launch_train_r1_traced)
+                     : (rows == 4 ? esr_rdb_launch_train : rows == 2 ? esr_rdb_launch_train_r2 : esr_rdb_launch_train_r1))(*p, grid, ntiles, tiles_x, tiles_y, ha, st);
     if (p->mode == 2)
-      return (rows == 4 ? esr_rdb_launch_bwd : rows == 2 ? esr_rdb_launch_bwd_r2 : esr_rdb_launch_bwd_r1)(*p, grid, ntiles, tiles_x, tiles_y, ha, st);
+      return (traced ? (rows == 4 ? esr_rdb_launch_bwd_traced : rows == 2 ? esr_rdb_launch_bwd_r2_traced : esr_rdb_launch_bwd_r1_traced)
+                     : (rows == 4 ? esr_rdb_launch_bwd : rows == 2 ? esr_rdb_launch_bwd_r2 : esr_rdb_launch_bwd_r1))(*p, grid, ntiles, tiles_x, tiles_y, ha, st);
     if (p->dtype != ESR_F16 && p->dtype != ESR_F32) { esr_set_error("%s: bad dtype %d", who, p->dtype); return ESR_ERR_INVALID; }
     // inference with the fused Philox noise layers (a train-mode module under no_grad): its own instantiations
-    if (p->noise_mode != ESR_NOISE_OFF) return esr_rdb_launch_noisy(*p, grid, ntiles, tiles_x, tiles_y, ha, st);
-    if (rows != 4) return (rows == 2 ? esr_rdb_launch_fwd_r2 : esr_rdb_launch_fwd_r1)(*p, grid, ntiles, tiles_x, tiles_y, ha, st);
+    if (p->noise_mode != ESR_NOISE_OFF) return (traced ? esr_rdb_launch_fwd_traced : esr_rdb_launch_noisy)(*p, grid, ntiles, tiles_x, tiles_y, ha, st);
+    if (rows != 4)
+      return (traced ? (rows == 2 ? esr_rdb_launch_fwd_r2_traced : esr_rdb_launch_fwd_r1_traced)
+                     : (rows == 2 ? esr_rdb_launch_fwd_r2 : esr_rdb_launch_fwd_r1))(*p, grid, ntiles, tiles_x, tiles_y, ha, st);
     if (coop_launch()) {
       // ESR_RDB_COOP=1: the runtime checks the grid against the occupancy query and refuses a grid that cannot be
       // co-resident (a plain launch of the same grid has the same residency, MI355X_MICROARCH.md; the check costs
@@ -311,14 +349,17 @@ int chain_launch(const esr_rdb_chain* p, esr_stream_t stream, const char* who, i
       int a1 = ntiles, a2 = tiles_x, a3 = tiles_y;
       unsigned* a4 = ha;
       void* args[] = {&arg, &a1, &a2, &a3, &a4};
-      const void* fn = p->dtype == ESR_F16 ? (const void*)rdb_chain_kernel<_Float16, 0, false, 0> : (const void*)rdb_chain_kernel<float, 0, false, 0>;
+      const void* fn = p->dtype != ESR_F16 ? (const void*)rdb_chain_kernel<float, 0, false, 0>
+                       : traced ? esr_rdb_fwd_traced_fn() : regular ? esr_rdb_fwd_reg_fn() : (const void*)rdb_chain_kernel<_Float16, 0, false, 0, false>;
       if (hipLaunchCooperativeKernel(fn, dim3(grid), dim3(NT), args, 0, st) != hipSuccess) {
         esr_set_error("%s: cooperative launch refused: %s", who, hipGetErrorString(hipGetLastError()));
         return ESR_ERR_LAUNCH;
       }
       return ESR_OK;
     }
-    if (p->dtype == ESR_F16) hipLaunchKernelGGL((rdb_chain_kernel<_Float16, 0, false, 0>), dim3(grid), dim3(NT), 0, st, *p, ntiles, tiles_x, tiles_y, ha);
+    if (traced) return esr_rdb_launch_fwd_traced(*p, grid, ntiles, tiles_x, tiles_y, ha, st);
+    if (regular) return esr_rdb_launch_fwd_reg(*p, grid, ntiles, tiles_x, tiles_y, ha, st);
+    if (p->dtype == ESR_F16) hipLaunchKernelGGL((rdb_chain_kernel<_Float16, 0, false, 0, false>), dim3(grid), dim3(NT), 0, st, *p, ntiles, tiles_x, tiles_y, ha);
     else hipLaunchKernelGGL((rdb_chain_kernel<float, 0, false, 0>), dim3(grid), dim3(NT), 0, st, *p, ntiles, tiles_x, tiles_y, ha);
     return esr_check_launch("rdb_chain_kernel");
   };

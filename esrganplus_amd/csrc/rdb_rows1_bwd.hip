@@ -4,6 +4,6 @@
 #include "rdb_chain_kernel.h"
 
 int esr_rdb_launch_bwd_r1(const esr_rdb_chain& p, int grid, int ntiles, int tiles_x, int tiles_y, unsigned* host_abort, hipStream_t st) {
-  hipLaunchKernelGGL((rdb_chain_kernel<_Float16, 2>), dim3(grid), dim3(NT), 0, st, p, ntiles, tiles_x, tiles_y, host_abort);
+  hipLaunchKernelGGL((rdb_chain_kernel<_Float16, 2, false, -1, false>), dim3(grid), dim3(NT), 0, st, p, ntiles, tiles_x, tiles_y, host_abort);
   return esr_check_launch("rdb_chain_kernel<backward, 1 rows>");
 }

@@ -880,6 +880,18 @@ int esr_debug_rdb_wgrad_follow(const struct esr_rdb_wgrad* p, const uint32_t* fl
  * real device.  esr_debug_chain_order_waits: cross-stream event waits the chain ordering has inserted so far. */
 int esr_debug_device_alias(int32_t alias);
 uint64_t esr_debug_chain_order_waits(void);
+/* The kernel variant the last chain launch of this process ran (tests): ESR_CHAIN_VARIANT_* | rows per wave << 8.
+ * REGULAR: the fp16 inference chain built for shapes that are a whole number of 16x32 tiles (H % 16 == 0, W % 32 == 0,
+ * no bands, no noise layers; ESR_RDB_GENERAL=1 in the environment keeps the general one).  TRACED: esr_rdb_chain.trace
+ * was set — only then do the fp16 chains run the instantiations that carry the trace stamps.
+ * This query and esr_debug_chain_force_general are for tests only: ONE process-wide word each (not per device like the
+ * rest of the launch bookkeeping), so they mean nothing while several devices or threads launch chains. */
+#define ESR_CHAIN_VARIANT_REGULAR 1
+#define ESR_CHAIN_VARIANT_TRACED 2
+int esr_debug_chain_last_variant(void);
+/* In-process form of ESR_RDB_GENERAL (the environment is read once): on = 1 / 0 forces / does not force the general
+ * chain whatever the environment says, on < 0 goes back to the environment; returns the previous override (-1: none). */
+int esr_debug_chain_force_general(int32_t on);
 size_t esr_rdb_workspace_bytes(int32_t B, int32_t H, int32_t W);
 size_t esr_rdb_weight_stream_bytes(int32_t dtype);
 int esr_rdb_max_tiles_per_image(void);   /* 16x32 tiles of ONE image must not exceed this (= CUs) */
