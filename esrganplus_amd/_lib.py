@@ -25,6 +25,7 @@ OP_TILE = 16
 OP_TILE_X8 = 17
 OP_FOLD3 = 18
 OP_TILE_MANY = 19
+OP_TILE_IMG = 20
 CHAIN_VARIANT_REGULAR, CHAIN_VARIANT_TRACED = 1, 2     # esr_debug_chain_last_variant (| rows per wave << 8)
 BN_STATS, BN_FINALIZE, BN_APPLY, BN_BWD_REDUCE, BN_BWD_FINAL, BN_BWD_APPLY, BN_RESTAT, BN_FIN_APPLY = 0, 1, 2, 3, 4, 5, 6, 7
 NO_LAYER = 0xFFFFFFFF
@@ -112,6 +113,15 @@ class esr_tile_many(C.Structure):
     _fields_ = [('dtype', C.c_int32), ('to_g32', C.c_int32), ('C', C.c_int32), ('tile', C.c_int32), ('pad', C.c_int32),
                 ('scale', C.c_int32), ('th', C.c_int32), ('tw', C.c_int32), ('n_slots', C.c_int32),
                 ('items', C.c_void_p), ('g32', esr_g32), ('slots_nchw', C.c_void_p)]
+
+
+class esr_tile_img_item(C.Structure):
+    """One slot of one pass of esr_tile_img: esr_tile_item's layout, the pointer to a uint8 HWC image."""
+    _fields_ = [('hwc', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32), ('t', C.c_int32), ('live', C.c_int32)]
+
+
+class esr_tile_img(C.Structure):
+    _fields_ = esr_tile_many._fields_ + [('bgr', C.c_int32)]
 
 
 class esr_fold3(C.Structure):
@@ -284,7 +294,8 @@ class _op_union(C.Union):
                 ('pool', esr_pool), ('linear', esr_linear), ('unpermute', esr_unpermute),
                 ('pack_batch', esr_pack_batch), ('rdb_chain', esr_rdb_chain), ('frag_gather', esr_frag_gather),
                 ('rdb_wgrad', esr_rdb_wgrad), ('dihedral', esr_dihedral), ('tile', esr_tile),
-                ('tile_x8', esr_tile_x8), ('fold3', esr_fold3), ('tile_many', esr_tile_many)]
+                ('tile_x8', esr_tile_x8), ('fold3', esr_fold3), ('tile_many', esr_tile_many),
+                ('tile_img', esr_tile_img)]
 
 
 class esr_op(C.Structure):
@@ -302,7 +313,7 @@ EXPORTS = ['esr_packed_weight_bytes', 'esr_g32_dims', 'esr_conv_forward', 'esr_p
            'esr_rdb_mask_bytes', 'esr_rdb_check_abort', 'esr_debug_hold_cus', 'esr_debug_device_alias', 'esr_debug_chain_order_waits', 'esr_debug_chain_last_variant', 'esr_debug_chain_force_general',
            'esr_debug_mfma_probe', 'esr_debug_rdb_wgrad_follow', 'esr_dihedral_op', 'esr_tile_op',
            'esr_tile_x8_op', 'esr_l2_loss_forward', 'esr_fold3_op', 'esr_gan_loss_forward',
-           'esr_batch_assemble', 'esr_tile_many_op']
+           'esr_batch_assemble', 'esr_tile_many_op', 'esr_tile_img_op']
 
 _lib = None
 _lock = threading.Lock()
@@ -367,7 +378,8 @@ def lib():
                          ('esr_rdb_wgrad_run', esr_rdb_wgrad), ('esr_rdb_backward', esr_rdb_chain),
                          ('esr_dihedral_op', esr_dihedral), ('esr_tile_op', esr_tile),
                          ('esr_tile_x8_op', esr_tile_x8), ('esr_fold3_op', esr_fold3),
-                         ('esr_batch_assemble', esr_batch), ('esr_tile_many_op', esr_tile_many)):
+                         ('esr_batch_assemble', esr_batch), ('esr_tile_many_op', esr_tile_many),
+                         ('esr_tile_img_op', esr_tile_img)):
             getattr(L, name).argtypes = [C.POINTER(st), C.c_void_p]
         if L.esr_sizeof_op() != C.sizeof(esr_op):
             raise HipExtensionError('ABI mismatch: sizeof(esr_op) C=%d ctypes=%d'

@@ -10,7 +10,8 @@ import math
 import torch.nn as nn
 
 from . import block as B
-from .functional import run_rrdbnet, run_rrdbnet_tiled, run_rrdbnet_tiled_many, run_rrdbnet_tiled_x8, run_rrdbnet_x8
+from .functional import (run_rrdbnet, run_rrdbnet_images, run_rrdbnet_tiled, run_rrdbnet_tiled_many, run_rrdbnet_tiled_x8,
+                         run_rrdbnet_x8)
 
 
 SUPPORTED_UPSCALE = (1, 2, 3, 4, 8)
@@ -151,10 +152,25 @@ class _RRDBNetBase(B._PlannedModule):
         a list of [out_nc, 4H, 4W] / [1, out_nc, 4H, 4W] float32 results, ranks and order as the inputs, without
         gradient.  One launch plan per (windows per pass, window shape), whatever the images.  Always the eval forward;
         ``self.training`` and ``requires_grad`` are left as they are.  Not covered: the x8 self-ensemble over an image
-        set, scales other than 4, blending.  See ``functional.run_rrdbnet_tiled_many``."""
+        set, scales other than 4, blending.  See ``functional.run_rrdbnet_tiled_many``; for 8-bit images in and out,
+        ``forward_images``."""
         self._x4_only('forward_tiled_many')
         self._join_pending()
         return run_rrdbnet_tiled_many(self, images, tile, pad, windows_per_pass)
+
+    def forward_images(self, images, tile=96, pad=16, windows_per_pass=16, bgr=False):
+        """``forward_tiled_many`` with 8-bit ends: ``images`` is a sequence of ``torch.uint8`` tensors [H, W, 3] (HWC), of
+        any sizes, on one GPU -> a list of fresh uint8 device tensors [4H, 4W, 3], in input order, without gradient.
+        ``bgr=False``: R, G, B in memory on both ends (PIL); ``bgr=True``: B, G, R (cv2, the reference's scripts).  The
+        input is ``float32(v) / 255`` as a true division, the output ``rint(clamp(y, 0, 1) * 255)`` — the reference's
+        inference-script arithmetic — both inside the gather and stitch kernels: 3 bytes up and 48 down per LR pixel, no
+        per-pixel host work.  ``tile`` >= the largest image side runs every image whole.  Always the eval forward;
+        ``self.training`` and ``requires_grad`` are left as they are.  Not covered: the x8 self-ensemble with 8-bit ends,
+        scales other than 4, 16-bit or alpha images, CPU or numpy inputs, blending.  See
+        ``functional.run_rrdbnet_images``."""
+        self._x4_only('forward_images')
+        self._join_pending()
+        return run_rrdbnet_images(self, images, tile, pad, windows_per_pass, bgr)
 
 
 class RRDBNet(_RRDBNetBase):

@@ -2,30 +2,11 @@
 // stitch = the owned rectangle of every window's fp32 NCHW output -> the caller's NCHW image.  Geometry:
 // include/esrgan_hip.h (esr_tile); both kernels derive it from tile, pad and the tile index.  Plain loads and stores.
 // esr_tile_many is the same pair over an image set: a device table names each slot's image and tile.
-#include "common.h"
+#include "tile_geom.h"
 
 namespace {
 
 constexpr int TB_X = 64, TB_Y = 4;   // 64 pixels along x by 4 rows per workgroup
-
-// One axis of tile i: the owned range [o0, o0 + on) and the start w0 of its window of `win` pixels, in an image of n.
-struct TileAxis { int o0, on, w0; };
-
-__host__ __device__ __forceinline__ int tile_window(int n, int tile, int pad) {
-  const int64_t w = (int64_t)tile + 2 * (int64_t)pad;
-  return w < n ? (int)w : n;
-}
-
-__host__ __device__ __forceinline__ int tile_count(int n, int tile) { return (n - 1) / tile + 1; }
-
-__device__ __forceinline__ TileAxis tile_axis(int n, int tile, int pad, int win, int i) {
-  TileAxis a;
-  a.o0 = i * tile;                                  // i < ceil(n / tile), so o0 <= n - 1
-  a.on = n - a.o0 < tile ? n - a.o0 : tile;
-  const int w = a.o0 - pad;
-  a.w0 = w < 0 ? 0 : (w > n - win ? n - win : w);   // shifted inward at the borders
-  return a;
-}
 
 // One thread = one pixel of one window: C strided fp32 reads along x, one finished 32-byte channel group out.
 template <typename T>

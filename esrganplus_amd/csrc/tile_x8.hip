@@ -2,30 +2,11 @@
 // fixed-size windows of an NCHW fp32 image -> their flip / transpose copies as G32 slots, stitch-reduce = the slots' fp32
 // NCHW outputs -> inverse transforms summed in k order -> the owned rectangle of every tile in the caller's NCHW image.
 // Geometry and index maps: include/esrgan_hip.h (esr_tile, esr_dihedral, esr_tile_x8).  Plain loads, stores and VALU.
-#include "common.h"
+#include "tile_geom.h"
 
 namespace {
 
 constexpr int TX_TILE = 32;   // 32 x 32 pixels per workgroup, one pixel per thread
-
-// One axis of tile i: the owned range [o0, o0 + on) and the start w0 of its window of `win` pixels, in an image of n.
-struct TileAxis { int o0, on, w0; };
-
-__host__ __device__ __forceinline__ int tile_window(int n, int tile, int pad) {
-  const int64_t w = (int64_t)tile + 2 * (int64_t)pad;
-  return w < n ? (int)w : n;
-}
-
-__host__ __device__ __forceinline__ int tile_count(int n, int tile) { return (n - 1) / tile + 1; }
-
-__device__ __forceinline__ TileAxis tile_axis(int n, int tile, int pad, int win, int i) {
-  TileAxis a;
-  a.o0 = i * tile;                                  // i < ceil(n / tile), so o0 <= n - 1
-  a.on = n - a.o0 < tile ? n - a.o0 : tile;
-  const int w = a.o0 - pad;
-  a.w0 = w < 0 ? 0 : (w > n - win ? n - win : w);   // shifted inward at the borders
-  return a;
-}
 
 __device__ __forceinline__ int flip(bool on, int n, int i) { return on ? n - 1 - i : i; }
 

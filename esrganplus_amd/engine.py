@@ -155,6 +155,8 @@ def set_nchw(op, ptr):
         op.u.tile_x8.nchw = ptr
     elif op.kind == L.OP_TILE_MANY:
         op.u.tile_many.items = ptr       # the images are named by the pass's slice of the device item table
+    elif op.kind == L.OP_TILE_IMG:
+        op.u.tile_img.items = ptr
     else:
         op.u.layout.nchw = ptr
 
@@ -351,11 +353,12 @@ def tile_x8_op(ops, dt_e, B, C_, th, tw, to_g32, t_count, k_begin, k_count, g=No
     return ops.add(L.OP_TILE_X8, 'tile_x8', d)
 
 
-def tile_many_op(ops, dt_e, C_, th, tw, to_g32, n_slots, g=None, slots=None):
+def tile_many_op(ops, dt_e, C_, th, tw, to_g32, n_slots, g=None, slots=None, img=False):
     """Image-set tiled end (esr_tile_many) appended to `ops`: the gather of n_slots th x tw windows, each of an image of
     its own, into buffer g, or the stitch of n_slots window outputs — the fp32 NCHW tensor `slots` — each into its own
-    image.  tile, pad and the pass's slice of the device item table are set per run (TiledManyPlan.run)."""
-    d = L.esr_tile_many()
+    image.  tile, pad and the pass's slice of the device item table are set per run (TiledManyPlan.run).  img: the end
+    with 8-bit HWC images outside (esr_tile_img: the same fields and bgr, which TiledImgPlan.run sets too)."""
+    d = L.esr_tile_img() if img else L.esr_tile_many()
     d.dtype, d.to_g32, d.scale = dt_e, to_g32, 1 if to_g32 else 4
     d.C, d.th, d.tw, d.n_slots = C_, th, tw, n_slots
     if to_g32:
@@ -363,6 +366,8 @@ def tile_many_op(ops, dt_e, C_, th, tw, to_g32, n_slots, g=None, slots=None):
     else:
         d.slots_nchw = slots.data_ptr()
     d.tile, d.pad = max(th, tw), 0
+    if img:
+        return ops.add(L.OP_TILE_IMG, 'tile_img', d)
     return ops.add(L.OP_TILE_MANY, 'tile_many', d)
 
 
@@ -372,7 +377,7 @@ class Builder:
     image_limit = False           # G32's per-image offset bound (TrainBuilder: the weight-gradient kernels)
 
     def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1, x8=None, tiled=None, tiled_x8=None,
-                 scale=4, tiled_many=None):
+                 scale=4, tiled_many=None, tiled_img=None):
         self.wp = wp
         self.scale = scale            # upscale of the generator: 1, 2, 4, 8 = 0..3 nearest-x2 up-convs, 3 = one folded x3
         self.B, self.H, self.W = B, H, W
@@ -393,6 +398,9 @@ class Builder:
         # window on the NCHW side (H x W here is tw x th for the transposed slots, first k = 4)
         self.tiled_x8 = tiled_x8
         self.tiled_many = tiled_many  # slots: the batch is the windows, H x W each, of any images of a tiled forward
+        if tiled_img is not None:     # slots: tiled_many's plan with 8-bit HWC images at both ends (esr_tile_img)
+            self.tiled_many = tiled_img
+        self.tiled_img = tiled_img is not None
 
     def buf(self, C_, H=None, W=None):
         return new_buf(self.bufs, self.B, C_, H or self.H, W or self.W, self.dtype, self.device, self.image_limit)
@@ -644,7 +652,7 @@ class Builder:
             self.bufs.append(slots)
             c.nchw_out = slots.data_ptr()
             P.ops.add_conv(c)
-            P.out_op = tile_many_op(P.ops, d, out_nc, H, W, 0, B, slots=slots)
+            P.out_op = tile_many_op(P.ops, d, out_nc, H, W, 0, B, slots=slots, img=self.tiled_img)
         elif self.tiled is not None:
             # tiled forward: HR_conv1 leaves the windows' fp32 NCHW outputs in a buffer of the plan, slot-major, and the
             # stitch copies every tile's owned rectangle into the caller's tensor
@@ -679,7 +687,7 @@ class Builder:
             n, wh, ww, k0, kc = self.tiled_x8
             P.in_op = tile_x8_op(P.ops, self.dt_e, n, in_nc, wh, ww, 1, B // (kc * n), k0, kc, g=xin)
         elif self.tiled_many is not None:
-            P.in_op = tile_many_op(P.ops, self.dt_e, in_nc, H, W, 1, B, g=xin)
+            P.in_op = tile_many_op(P.ops, self.dt_e, in_nc, H, W, 1, B, g=xin, img=self.tiled_img)
         elif self.tiled is not None:
             P.in_op = tile_op(P.ops, self.dt_e, self.tiled, in_nc, 1, B // self.tiled, g=xin)
         elif self.x8 is None:
@@ -1014,6 +1022,28 @@ def build_rrdbnet_tiled_many_plan(wp, nb, in_nc, out_nc, S, th, tw, dtype, devic
     between the table-driven gather and stitch."""
     b = Builder(wp, S, th, tw, dtype, device, False, variant, 'net', nb, tiled_many=S)
     return TiledManyPlan(b.rrdbnet(in_nc, out_nc, False), S)
+
+
+class TiledImgPlan(TiledManyPlan):
+    """TiledManyPlan with 8-bit ends: the same inference plan of batch S at th x tw between the gather that reads uint8
+    HWC images and the stitch that writes them (esr_tile_img).  Nothing in it depends on an image or a channel order."""
+
+    def run(self, gather_items, stitch_items, tile, pad, bgr, stream):
+        """One pass: the two uint8 device tensors hold the pass's S esr_tile_img_item entries (LR images / HR results)."""
+        plan = self.plan
+        arr = plan.ops.array()
+        g, s = arr[plan.in_op].u.tile_img, arr[plan.out_op].u.tile_img
+        g.tile = s.tile = tile
+        g.pad = s.pad = pad
+        g.bgr = s.bgr = 1 if bgr else 0
+        plan.run(gather_items, stitch_items, stream)
+
+
+def build_rrdbnet_tiled_img_plan(wp, nb, in_nc, out_nc, S, th, tw, dtype, device, variant):
+    """build_rrdbnet_tiled_many_plan with 8-bit ends (eval mode): the ordinary plan of batch S at the window shape th x tw
+    between esr_tile_img's gather and stitch; HR_conv1 writes the fp32 slots buffer the stitch quantises."""
+    b = Builder(wp, S, th, tw, dtype, device, False, variant, 'net', nb, tiled_img=S)
+    return TiledImgPlan(b.rrdbnet(in_nc, out_nc, False), S)
 
 
 class TiledX8Plan:

@@ -838,8 +838,8 @@ def run_rrdbnet_tiled_many(net, images, tile=96, pad=16, windows_per_pass=16):
     device holds the plan's activations of S windows plus this call's inputs and outputs.  Bit-identical to
     ``tiled_many_reference(net, ...)``; for one image, to ``run_rrdbnet_tiled(x, tile, pad, windows_per_pass)``.  Noise
     is off whatever ``net.training`` is; the module's mode and every ``requires_grad`` are left untouched.
-    Out of scope: the x8 self-ensemble over an image set, scales other than 4, blending."""
-    import numpy as np
+    Out of scope: the x8 self-ensemble over an image set, scales other than 4, blending.  For 8-bit images in and out
+    see ``run_rrdbnet_images``: the same passes with the uint8 conversions fused into the two ends."""
     tile, pad, wpp = _tiled_many_ints(tile, pad, windows_per_pass)
     xs = _tiled_many_images(list(images), net.in_nc)
     if not xs:
@@ -856,11 +856,23 @@ def run_rrdbnet_tiled_many(net, images, tile=96, pad=16, windows_per_pass=16):
         raise ValueError('the images of a tiled forward are on %s: the HIP path needs tensors on an MI355X; there is '
                          'no CPU fallback' % (dev,))
     xin = [v.detach().contiguous().float() for v, _ in xs]
+    outs = _run_tiled_set(net, 'tiled_many', E.build_rrdbnet_tiled_many_plan, groups, xin, sizes, dev,
+                          lambda H, W: torch.empty((1, net.out_nc, 4 * H, 4 * W), dtype=torch.float32, device=dev),
+                          tile, pad)
+    return [o if rank == 4 else o[0] for o, (_, rank) in zip(outs, xs)]
+
+
+def _run_tiled_set(net, kind, build, groups, xin, sizes, dev, new_out, *args):
+    """The passes ``groups`` (``tiled_many_passes``) of a tiled forward over the device images ``xin`` of the LR sizes
+    ``sizes``, on the current stream -> the results, one ``new_out(H, W)`` per image.  One slot table for the call, the
+    gather's entries of every pass of every group, then the stitch's (the 24-byte layout of esr_tile_item), uploaded
+    through the net's pinned ring in one non-blocking copy; one plan per group, keyed (kind, S, th, tw, precision,
+    generation) and built by ``build``; every pass runs it with (its gather slice, its stitch slice, *args, stream)."""
+    import numpy as np
     order = E.StreamOrder.of(net)
     cur = order.enter()
     wp = net._weights(dev)
-    outs = [torch.empty((1, net.out_nc, 4 * H, 4 * W), dtype=torch.float32, device=dev) for H, W in sizes]
-    # one table for the call: the gather's entries of every pass of every group, then the stitch's
+    outs = [new_out(H, W) for H, W in sizes]
     flat = [w for _, _, _, passes in groups for p in passes for w in p]
     n = len(flat)
     idx = np.fromiter((w[0] for w in flat), dtype=np.int64, count=n)
@@ -879,16 +891,89 @@ def run_rrdbnet_tiled_many(net, images, tile=96, pad=16, windows_per_pass=16):
     table = ring.upload(rec, dev)
     isz, stream, at = rec.dtype.itemsize, E.current_stream(), 0
     for th, tw, S, passes in groups:
-        key = ('tiled_many', S, th, tw, net.precision, wp.generation)    # no H, W: whatever images have this window
+        key = (kind, S, th, tw, net.precision, wp.generation)    # no H, W: whatever images have this window
         plan = net._plans.get(key)
         if plan is None:
             if len(net._plans) >= net.max_cached_plans:
                 net._plans.clear()
-            plan = E.build_rrdbnet_tiled_many_plan(wp, net.nb, net.in_nc, net.out_nc, S, th, tw, net.precision, dev,
-                                                   net.variant)
+            plan = build(wp, net.nb, net.in_nc, net.out_nc, S, th, tw, net.precision, dev, net.variant)
             net._plans[key] = plan
         for _ in passes:
-            plan.run(table[at * isz:(at + S) * isz], table[(n + at) * isz:(n + at + S) * isz], tile, pad, stream)
+            plan.run(table[at * isz:(at + S) * isz], table[(n + at) * isz:(n + at + S) * isz], *args, stream)
             at += S
     order.leave(cur)
-    return [o if rank == 4 else o[0] for o, (_, rank) in zip(outs, xs)]
+    return outs
+
+
+def _images_u8(images):
+    """The images of ``run_rrdbnet_images`` / ``images_reference`` as a list: uint8 tensors [H, W, 3] with pixels."""
+    images = list(images)
+    for i, x in enumerate(images):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+            raise ValueError('image %d of forward_images must be a torch.uint8 tensor, got %s'
+                             % (i, x.dtype if isinstance(x, torch.Tensor) else type(x).__name__))
+        if x.dim() != 3:
+            raise ValueError('image %d of forward_images must be [H, W, 3] (HWC), got rank %d: %s' % (i, x.dim(), tuple(x.shape)))
+        if x.shape[2] != 3:
+            raise ValueError('image %d of forward_images must be [H, W, 3] (HWC): its last dimension is %d' % (i, x.shape[2]))
+        if x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError('image %d of a tiled forward has no pixels: shape %s' % (i, tuple(x.shape)))
+    return images
+
+
+def images_reference(fn, images, tile, pad, windows_per_pass=16, bgr=False):
+    """Pure-torch restatement of ``run_rrdbnet_images`` and a x4 forward ``fn``, on any device: every uint8 [H, W, 3]
+    image -> NCHW float32 RGB, ``float32(v) / 255`` as a true division (bit-identical, for all 256 values, to the
+    ``astype(float64) / 255 -> float32`` of the reference's inference script); ``tiled_many_reference(fn, ...)``;
+    ``(y.clamp(0, 1) * 255.0).round()`` -> uint8 [4H, 4W, 3].  ``bgr``: the channel order in memory is B, G, R on both
+    ends, else R, G, B; ``fn`` sees RGB either way.  The 256 quotients are divided once, on the CPU, and looked up: on
+    a GPU torch divides by a Python scalar as a multiplication by its reciprocal, which differs for 126 of them."""
+    images = _images_u8(images)
+    lut = torch.arange(256, dtype=torch.float32) / 255.0
+    xs = [lut.to(x.device)[(x.flip(2) if bgr else x).permute(2, 0, 1).long()] for x in images]
+    ys = tiled_many_reference(fn, xs, tile, pad, windows_per_pass)
+    outs = [(y.clamp(0, 1) * 255.0).round().to(torch.uint8).permute(1, 2, 0) for y in ys]
+    return [(o.flip(2) if bgr else o).contiguous() for o in outs]
+
+
+def run_rrdbnet_images(net, images, tile=96, pad=16, windows_per_pass=16, bgr=False):
+    """``run_rrdbnet_tiled_many`` with 8-bit ends: ``images`` is a sequence of ``torch.uint8`` tensors [H, W, 3] (HWC, as
+    PIL and cv2 hold an image), of any sizes, on one GPU -> a list of fresh uint8 device tensors [4H, 4W, 3], in input
+    order, without gradient; an empty list gives [].  ``bgr=False``: R, G, B in memory on both ends (PIL); ``bgr=True``:
+    B, G, R on both ends (cv2.imread / imwrite, the reference's scripts, ``metrics.device_tensor2img``,
+    ``TrainSet(bgr=True)``).  The reference's inference-script conversions are fused into the two ends
+    (include/esrgan_hip.h: esr_tile_img): the gather reads the bytes and divides, ``float32(v) / 255.0f`` correctly
+    rounded — bit-identical to the script's float64 division rounded to float32, which a multiplication by 1/255 is not —
+    and the stitch writes ``rint(clamp(v, 0, 1) * 255)`` (``tensor2img``'s rounding; non-finite outputs: unspecified).  A
+    folder costs 3 bytes up and 48 bytes down and resident per LR pixel where the float32 ends cost 12 and 192, and
+    nothing is computed per pixel on the host.  Windows, passes, filler, the grouping by window shape, the 65535-slot
+    limit and the cutting of tile / pad down to the largest image are ``run_rrdbnet_tiled_many``'s; so is the plan in
+    between: one per (S, window shape, precision, weight generation), keyed 'tiled_img' — no image size and no ``bgr``
+    in the key; tile, pad and bgr are set on the two ops per run.  ``tile`` >= the largest image side makes every
+    window a whole image: that is the whole-image route.  Non-contiguous images are made contiguous.  Everything runs on
+    the current stream without a device synchronisation.  Bit-identical to ``images_reference(net, ...)`` and to
+    ``device_tensor2img`` of ``run_rrdbnet_tiled_many``'s results.  Noise is off whatever ``net.training`` is; the
+    module's mode and every ``requires_grad`` are left untouched.
+    Out of scope: the x8 self-ensemble with 8-bit ends, scales other than 4, 16-bit or alpha images, CPU or numpy
+    inputs, blending."""
+    tile, pad, wpp = _tiled_many_ints(tile, pad, windows_per_pass)
+    images = _images_u8(images)
+    if net.in_nc != 3 or net.out_nc != 3:
+        raise ValueError('forward_images takes and gives 3-channel 8-bit images: this net has in_nc = %d, out_nc = %d'
+                         % (net.in_nc, net.out_nc))
+    if not images:
+        return []
+    sizes = [(x.shape[0], x.shape[1]) for x in images]
+    m = max(max(s) for s in sizes)
+    tile, pad = min(tile, m), min(pad, m)          # cut down to the largest image: changes no tile and no window
+    groups = tiled_many_passes(sizes, tile, pad, wpp)      # refuses more than 65535 slots per pass
+    dev = images[0].device
+    for i, x in enumerate(images):
+        if x.device != dev:
+            raise ValueError('image %d is on %s, image 0 on %s: a tiled forward runs on one device' % (i, x.device, dev))
+    if dev.type != 'cuda':
+        raise ValueError('the images of a tiled forward are on %s: the HIP path needs tensors on an MI355X; there is '
+                         'no CPU fallback' % (dev,))
+    xin = [x.detach().contiguous() for x in images]
+    return _run_tiled_set(net, 'tiled_img', E.build_rrdbnet_tiled_img_plan, groups, xin, sizes, dev,
+                          lambda H, W: torch.empty((4 * H, 4 * W, 3), dtype=torch.uint8, device=dev), tile, pad, bool(bgr))

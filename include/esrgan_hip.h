@@ -329,6 +329,47 @@ typedef struct esr_tile_many {
   const float* slots_nchw;
 } esr_tile_many;
 
+/* esr_tile_many with 8-bit ends: the gather reads 8-bit HWC images, the stitch writes them; between the two sits the same
+ * plan.  Slots, the device table, its guarantees, th x tw, tile, pad, n_slots and the limits are esr_tile_many's; an item
+ * has esr_tile_item's layout with a byte pointer.  C is 1 or 3, else ESR_ERR_UNSUPPORTED.  With (y, x) a logical pixel of
+ * slot s, (wy, wx) the start of its window, (oy, ox) the start of its owned rectangle, in LR pixels of ITS image of H x W:
+ *   to_g32 = 1, scale = 1  gather: hwc is the LR image uint8 [H][W][C].  Channel c of slot pixel (y, x) is
+ *                 float32(hwc[((wy + y) W + wx + x) C + m(c)]) / 255.0f,   m(c) = 2 - c when bgr and C == 3, else c,
+ *               one correctly rounded float32 division (NOT a multiplication by 1/255, which differs for 126 of the 256
+ *               values from the float64 division the reference's scripts round to float32), then converted to dtype and
+ *               written as esr_tile_many's gather writes: finished 32-byte channel groups, channels >= C zero, the halo
+ *               never touched, filler slots filled like any other.  slot channel 0 is R whatever the order in memory.
+ *   to_g32 = 0, scale = 4  stitch: slots_nchw is fp32 [n_slots][C][4 th][4 tw], 16-byte aligned; hwc is the HR result
+ *               uint8 [4H][4W][C], 4-byte aligned.  For every item with live != 0 and every HR pixel (Y, X) of its owned
+ *               rectangle [4 oy, 4 (oy + on_y)) x [4 ox, 4 (ox + on_x)):
+ *                 hwc[(Y 4W + X) C + m(c)] = uint8(rintf(fminf(fmaxf(v, 0), 1) * 255.0f)),
+ *                 v = slots_nchw[s][c][Y - 4 wy][X - 4 wx]
+ *               (metrics.hip's quant8(v, 0, 1): the reference's tensor2img rounding, half to even; the result for a
+ *               non-finite v is unspecified).  Four HR pixels of a row are written at a time, as C aligned dwords: the byte
+ *               offset (Y 4W + 4 x) C is a multiple of 4.  Nothing outside the owned rectangles is written; slots with
+ *               live == 0 are neither read nor written; g32 and dtype's storage type are unused.
+ * Items live in device memory: this entry cannot check them (pointer alignment included); functional.run_rrdbnet_images
+ * builds them from validated sizes and fresh allocations.                                                              */
+typedef struct esr_tile_img_item {   /* esr_tile_item's layout; lives in DEVICE memory */
+  uint8_t* hwc;                  /* gather: the LR image [H][W][C]; stitch: the HR result [4H][4W][C] */
+  int32_t H, W;                  /* LR size of that image (on both sides) */
+  int32_t t;                     /* tile index in that image's own ny x nx grid */
+  int32_t live;                  /* 0: a filler slot — the gather fills it, the stitch skips it */
+} esr_tile_img_item;
+
+typedef struct esr_tile_img {
+  int32_t dtype, to_g32;
+  int32_t C;                     /* 1 or 3 */
+  int32_t tile, pad;             /* LR pixels */
+  int32_t scale;                 /* 1: gather, 4: stitch */
+  int32_t th, tw;                /* the window shape every item has */
+  int32_t n_slots;               /* batch entries = slots, one image per slot */
+  const esr_tile_img_item* items;    /* n_slots entries, device memory */
+  esr_g32 g32;
+  const float* slots_nchw;
+  int32_t bgr;                   /* C == 3: the channel order in memory is B, G, R on this op's side (else R, G, B) */
+} esr_tile_img;
+
 /* Philox-4x32-7 + Box-Muller N(0,1) fill (csrc/common.h), NCHW fp32 — the exact z the fused noise epilogue uses for
  * (seed, layer); lets tests feed the same z to the oracle (GaussianNoise, block.py:117-122). */
 typedef struct esr_noise_fill {
@@ -761,7 +802,8 @@ enum esr_op_kind { ESR_OP_CONV = 1, ESR_OP_PACK = 2, ESR_OP_LAYOUT = 3, ESR_OP_N
                    ESR_OP_UNPERMUTE = 9, ESR_OP_PACK_BATCH = 10,
                    ESR_OP_RDB_CHAIN = 11, ESR_OP_FRAG_GATHER = 12, ESR_OP_RDB_WGRAD = 13,
                    ESR_OP_RDB_CHAIN_BWD = 14 /* u.rdb_chain with mode 2 */, ESR_OP_DIHEDRAL = 15,
-                   ESR_OP_TILE = 16, ESR_OP_TILE_X8 = 17, ESR_OP_FOLD3 = 18, ESR_OP_TILE_MANY = 19 };
+                   ESR_OP_TILE = 16, ESR_OP_TILE_X8 = 17, ESR_OP_FOLD3 = 18, ESR_OP_TILE_MANY = 19,
+                   ESR_OP_TILE_IMG = 20 };
 
 /* esr_op.flags */
 #define ESR_OPF_SIDE 1   /* on a run of consecutive ESR_OP_WGRAD ops: launch the run on the library's side
@@ -808,6 +850,7 @@ typedef struct esr_op {
     esr_tile_x8 tile_x8;
     esr_fold3 fold3;
     esr_tile_many tile_many;
+    esr_tile_img tile_img;
   } u;
 } esr_op;
 
@@ -824,6 +867,7 @@ int esr_tile_op(const esr_tile* p, esr_stream_t stream);           /* added unde
 int esr_tile_x8_op(const esr_tile_x8* p, esr_stream_t stream);     /* added under ABI 6: a pure addition */
 int esr_fold3_op(const esr_fold3* p, esr_stream_t stream);         /* added under ABI 6: a pure addition */
 int esr_tile_many_op(const esr_tile_many* p, esr_stream_t stream); /* added under ABI 6: a pure addition */
+int esr_tile_img_op(const esr_tile_img* p, esr_stream_t stream);   /* added under ABI 6: a pure addition */
 int esr_conv_wgrad(const esr_wgrad* p, esr_stream_t stream);
 /* n independent weight-gradient problems (disjoint dw/dbias blocks).  fp16 3x3/s1 and 1x1 entries are
  * packed, up to 8 at a time, into ONE launch (at training sizes a single conv's wgrad is ~64
@@ -944,7 +988,7 @@ int esr_graph_destroy(esr_graph_t g);
 int esr_run_ops_timed(const esr_op* ops, int32_t n, esr_stream_t stream, float* ms_out);
 
 const char* esr_last_error(void);
-int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8, esr_fold3 / esr_fold3_op / ESR_OP_FOLD3 with esr_pool modes 4 / 5, esr_batch / esr_batch_item / esr_batch_assemble, and esr_tile_many / esr_tile_item / esr_tile_many_op / ESR_OP_TILE_MANY were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
+int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8, esr_fold3 / esr_fold3_op / ESR_OP_FOLD3 with esr_pool modes 4 / 5, esr_batch / esr_batch_item / esr_batch_assemble, esr_tile_many / esr_tile_item / esr_tile_many_op / ESR_OP_TILE_MANY, and esr_tile_img / esr_tile_img_item / esr_tile_img_op / ESR_OP_TILE_IMG were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
                                 esr_l1_loss, esr_ragan_loss, ESR_OPF_SIDE_FREE) */
 size_t esr_sizeof_op(void);
 

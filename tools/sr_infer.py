@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Inference harness reproducing the reference's ``test_image/test.py`` (lines 9-40) on the HIP path
-with PIL instead of cv2:  python tools/sr_infer.py <model.pth|synthetic> <in_dir> <out_dir> [fp16|fp32] [--scale S] [--x8] [--tile N[,PAD]] [--tile-x8 N[,PAD]] [--tile-many N[,PAD]]
+with PIL instead of cv2:  python tools/sr_infer.py <model.pth|synthetic> <in_dir> <out_dir> [fp16|fp32] [--scale S] [--x8] [--tile N[,PAD]] [--tile-x8 N[,PAD]] [--tile-many N[,PAD]] [--tile-u8 N[,PAD]]
 
 Per image: RGB /255 -> NCHW float32 -> RRDB_Net(3,3,64,23,...) -> clamp(0,1) -> *255 round -> PNG.
 --scale S (also --scale=S; 1, 2, 3, 4 or 8, default 4): the ``upscale`` the network is built with.
@@ -15,6 +15,10 @@ ensemble per window, with the tiled forward's bounded memory and shared plan; no
 odd-sized images run at the cost of full passes.  Images are queued until they hold at least 4 x 16 windows (or the
 folder ends), run in one call and written; the output of each image is that of the call it ran in.  Not combined with
 --x8, --tile or --tile-x8.
+--tile-u8 N[,PAD] (also --tile-u8=N[,PAD]): --tile-many's folder queueing through
+``model.forward_images(images, tile=N, pad=PAD)``: the 8-bit image goes to the device as it is and the 8-bit result comes
+back, the / 255 and the clamp, x 255, round run inside the gather and stitch kernels — the same arithmetic, no per-pixel
+numpy.  N >= the largest image side runs every image whole.  Not combined with --x8, --tile, --tile-x8 or --tile-many.
 The tiled forms are x4-only: with another --scale the script exits with the library's message."""
 import glob
 import os
@@ -31,7 +35,7 @@ from esrganplus_amd import architecture as arch, synth
 def main():
     argv = [a for a in sys.argv[1:] if a != '--x8']
     x8 = '--x8' in sys.argv[1:]
-    tiles = {'--tile': None, '--tile-x8': None, '--tile-many': None}
+    tiles = {'--tile': None, '--tile-x8': None, '--tile-many': None, '--tile-u8': None}
     for flag in tiles:
         for i, a in enumerate(argv):
             if a == flag or a.startswith(flag + '='):
@@ -44,7 +48,7 @@ def main():
                 if len(tiles[flag]) not in (1, 2):
                     sys.exit('sr_infer.py: %s takes N or N,PAD (LR pixels), got %r' % (flag, val))
                 break
-    tiled, tiled_x8, tiled_many = tiles['--tile'], tiles['--tile-x8'], tiles['--tile-many']
+    tiled, tiled_x8, tiled_many, tiled_u8 = tiles['--tile'], tiles['--tile-x8'], tiles['--tile-many'], tiles['--tile-u8']
     scale = 4
     for i, a in enumerate(argv):
         if a == '--scale' or a.startswith('--scale='):
@@ -61,14 +65,18 @@ def main():
     if tiled_many and (x8 or tiled or tiled_x8):
         sys.exit('sr_infer.py: --tile-many is the tiled forward over the folder by itself: it cannot be combined with '
                  '--x8, --tile or --tile-x8')
+    if tiled_u8 and (x8 or tiled or tiled_x8 or tiled_many):
+        sys.exit('sr_infer.py: --tile-u8 is the 8-bit tiled forward over the folder by itself: it cannot be combined with '
+                 '--x8, --tile, --tile-x8 or --tile-many')
     model_path, in_dir, out_dir = argv[0], argv[1], argv[2]
     prec = argv[3] if len(argv) > 3 else 'fp32'
     dev = torch.device('cuda')
     model = arch.RRDB_Net(3, 3, 64, 23, gc=32, upscale=scale, norm_type=None, act_type='leakyrelu',
                           mode='CNA', res_scale=1, upsample_mode='upconv')
-    if tiled or tiled_x8 or tiled_many:
+    if tiled or tiled_x8 or tiled_many or tiled_u8:
         try:
-            model._x4_only('--tile-x8' if tiled_x8 else '--tile-many' if tiled_many else '--tile')      # the library's own refusal, before anything is loaded
+            # the library's own refusal, before anything is loaded
+            model._x4_only('--tile-x8' if tiled_x8 else '--tile-many' if tiled_many else '--tile-u8' if tiled_u8 else '--tile')
         except ValueError as e:
             sys.exit('sr_infer.py: %s' % e)
     sd = synth.rrdbnet_state_dict(23, 0, upscale=scale) if model_path == 'synthetic' else torch.load(model_path, map_location='cpu')
@@ -80,6 +88,8 @@ def main():
     os.makedirs(out_dir, exist_ok=True)
     if tiled_many:
         return run_tile_many(model, dev, in_dir, out_dir, *tiled_many)
+    if tiled_u8:
+        return run_tile_u8(model, dev, in_dir, out_dir, *tiled_u8)
     for idx, path in enumerate(sorted(glob.glob(os.path.join(in_dir, '*'))), 1):
         base = os.path.splitext(os.path.basename(path))[0]
         img = np.array(Image.open(path).convert('RGB')).astype(np.float64) / 255
@@ -113,6 +123,31 @@ def run_tile_many(model, dev, in_dir, out_dir, tile, pad=16):
         img = np.array(Image.open(path).convert('RGB')).astype(np.float64) / 255
         queue.append((idx, base, img.shape[:2], torch.from_numpy(np.transpose(img, (2, 0, 1))).float().unsqueeze(0).to(dev)))
         windows += -(-img.shape[0] // max(tile, 1)) * -(-img.shape[1] // max(tile, 1))
+        if windows >= 4 * 16:
+            flush()
+            windows = 0
+    if queue:
+        flush()
+
+
+def run_tile_u8(model, dev, in_dir, out_dir, tile, pad=16):
+    """--tile-u8: run_tile_many's flushes through ``forward_images``; uint8 HWC up, uint8 HWC down, the same files and
+    lines."""
+    queue, windows = [], 0
+
+    def flush():
+        with torch.no_grad():
+            outs = [y.cpu().numpy() for y in model.forward_images([x for _, _, x in queue], tile, pad)]
+        for (idx, base, x), out in zip(queue, outs):
+            Image.fromarray(out).save(os.path.join(out_dir, '%s_rlt.png' % base))
+            print(idx, base, tuple(x.shape[:2]), '->', out.shape[:2])
+        del queue[:]
+
+    for idx, path in enumerate(sorted(glob.glob(os.path.join(in_dir, '*'))), 1):
+        base = os.path.splitext(os.path.basename(path))[0]
+        x = torch.from_numpy(np.array(Image.open(path).convert('RGB'))).to(dev)
+        queue.append((idx, base, x))
+        windows += -(-x.shape[0] // max(tile, 1)) * -(-x.shape[1] // max(tile, 1))
         if windows >= 4 * 16:
             flush()
             windows = 0
