@@ -283,9 +283,25 @@ __device__ __forceinline__ ImgView img_view(const esr_g32& v, int b, int g0 = 0)
   return o;
 }
 
+// The epilogues carry a lane's 16 values of a row as 8 PAIRS from the accumulator to the packed row: v_pk_add_f32 /
+// v_pk_mul_f32 / v_cvt_pk_f16_f32 take aligned register pairs, and a value flow written element by element leaves the
+// pairing to hipcc's vectoriser — which paired MODE 1's `+ P` at an odd offset and then moved every value twice
+// (v_mov into aligned pairs, v_alignbit / v_pack to re-align the packed halves): VALU instructions that one wave per
+// SIMD issues instead of MFMAs (profiles/chain_valu.md).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+
 // 16 consecutive channels (cout block cb, lane half h) of one pixel <-> float[16], through sc1 accesses
 template <typename T> struct Ch16;
 template <> struct Ch16<_Float16> {
+  // packed row from pairs: one v_cvt_pk_f16_f32 per dword (round to nearest even, as the element-wise conversion)
+  static __device__ __forceinline__ void pack2(const f32x2 (&w)[8], u32x4 (&q)[2]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      q[0][i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(w[i], half2v));
+      q[1][i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(w[4 + i], half2v));
+    }
+  }
   static __device__ __forceinline__ void store(const ImgView& t, int cb, int h, int pixoff, const float v[16]) {
     half8 x, y;
 #pragma unroll
@@ -323,6 +339,22 @@ template <> struct Ch16<_Float16> {
     const int off = pixoff + h * 16;           // (an out-of-range pixoff stays out of range: + 16 at most)
     __builtin_amdgcn_raw_buffer_store_b128(a, t.r, (2 * cb) * t.gs + off, 0, 16);
     __builtin_amdgcn_raw_buffer_store_b128(b, t.r, (2 * cb + 1) * t.gs + off, 0, 16);
+  }
+  // .. with the whole per-lane offset worked out by the caller: off = the lane's 16 bytes in the FIRST group of the cout
+  // block, (2 cb) gs + pixoff + 16 h — or 2^31 for a dropped pixel, which stays past num_records for both stores.
+  // The second group's stride is added in a VGPR, NOT passed as the instruction's scalar offset: hipcc pads "VMEM store
+  // of more than 64 bits -> VALU write of its data registers" only for stores WITHOUT an SGPR offset, and on gfx950 a
+  // 128-bit store with one lost its second dword in lanes 12..15 of every 16 to the v_pk_mul_f32 right behind it
+  // (profiles/chain_valu.md).
+  static __device__ __forceinline__ void store_packed_rows_at(const ImgView& t, int off, const u32x4 (&q)[2]) {
+    u32x4 a = q[0], b = q[1];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const auto r = __builtin_amdgcn_permlane32_swap(a[i], b[i], false, false);
+      a[i] = r[0]; b[i] = r[1];
+    }
+    __builtin_amdgcn_raw_buffer_store_b128(a, t.r, off, 0, 16);
+    __builtin_amdgcn_raw_buffer_store_b128(b, t.r, off + t.gs, 0, 16);
   }
   struct Raw { u32x4 q[2]; };
   static __device__ __forceinline__ void load(const ImgView& t, int cb, int h, int pixoff, Raw& r) {
@@ -502,6 +534,12 @@ __device__ __forceinline__ void lds_put_row(char* smem, int slot, int r, const u
   *(u32x4*)(px + (own_swz ^ 16)) = q[1];
 }
 
+// the LDS copy of a packed row has landed once at most N younger LDS operations are outstanding (they return in order):
+// its registers may be overwritten.  "memory": the compiler's own ds_writes stay on their side of the count.
+template <int N> __device__ __forceinline__ void lds_landed(u32x4 (&q)[2]) {
+  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(q[0]), "+v"(q[1]) : "n"(N) : "memory");
+}
+
 // .. and back (the lane's own pixel as the epilogue stored it)
 template <typename RAW> __device__ __forceinline__ void lds_get_rows(const char* smem, int slot0, RAW (&q)[R], const Tile& t) {
   const int lane = t.lane();
@@ -513,6 +551,76 @@ template <typename RAW> __device__ __forceinline__ void lds_get_rows(const char*
     q[r].q[0] = *(const u32x4*)(px + own_swz);
     q[r].q[1] = *(const u32x4*)(px + (own_swz ^ 16));
   }
+}
+
+// ---- carry into the next block (fp16 path) -----------------------------------------------------------
+// The next block's conv5 accumulators (cout block BLK = 4 / 5) start at scale * x, x = this block's output AS STORED
+// (scale 5: that block's tail `conv5 * 0.2 + x` needs no residual read; 0 when it adds x explicitly).  Nothing of this
+// is needed by the neighbours, so it runs BEHIND publish — in the time the wave otherwise spends waiting for their flags
+// — and reads the packed rows back from the stage slots the tail wrote them to (slot0 + lane half: the lane's own
+// pixels; the zero padding beyond the image carries 0, as it must).  One v_fma_mix_f32 per element takes the fp16 half
+// of the packed dword directly: scale * x + (-0) is the fp32 product bit for bit (it is exact for scale = 5, and -0 keeps
+// the sign of a zero), where a conversion and a multiply were two instructions.
+// Read and wait are ONE statement (an asm ds_read result must not be copied before it has arrived).
+__device__ __forceinline__ float mix_lo(uint32_t q, float s) {
+  float o;
+  asm("v_fma_mix_f32 %0, %1, %2, neg(0) op_sel_hi:[1,0,0]" : "=v"(o) : "v"(q), "s"(s));
+  return o;
+}
+__device__ __forceinline__ float mix_hi(uint32_t q, float s) {
+  float o;
+  asm("v_fma_mix_f32 %0, %1, %2, neg(0) op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(o) : "v"(q), "s"(s));
+  return o;
+}
+// w + (float)half of a packed dword, in one instruction (the epilogue of x4 adds x2 this way)
+__device__ __forceinline__ float mix_add_lo(uint32_t q, float w) {
+  float o;
+  asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(o) : "v"(q), "v"(w));
+  return o;
+}
+__device__ __forceinline__ float mix_add_hi(uint32_t q, float w) {
+  float o;
+  asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(o) : "v"(q), "v"(w));
+  return o;
+}
+template <int BLK> __device__ __forceinline__ void carry_rows(Acc24& acc, char* smem, int slot0, float scale, const Tile& t) {
+  const int lane = t.lane();
+  int own_px, own_swz;
+  t.own(lane, own_px, own_swz);
+  const uint32_t base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem + (uint32_t)((slot0 + (lane >> 5)) * ASLOT + own_px);
+  const uint32_t a0 = base + own_swz, a1 = base + (own_swz ^ 16);     // the two 16-byte halves of the pixel, as lds_put_row wrote them
+  u32x4 q[R][2];
+  constexpr int RP = IW * 32;                                           // one staged row
+  static_assert((R - 1) * RP < 65536, "row offsets are instruction immediates");
+  if constexpr (R == 4)
+    asm volatile("ds_read_b128 %0, %[a0]\n\tds_read_b128 %1, %[a1]\n\t"
+                 "ds_read_b128 %2, %[a0] offset:%[o1]\n\tds_read_b128 %3, %[a1] offset:%[o1]\n\t"
+                 "ds_read_b128 %4, %[a0] offset:%[o2]\n\tds_read_b128 %5, %[a1] offset:%[o2]\n\t"
+                 "ds_read_b128 %6, %[a0] offset:%[o3]\n\tds_read_b128 %7, %[a1] offset:%[o3]\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(q[0][0]), "=&v"(q[0][1]), "=&v"(q[1][0]), "=&v"(q[1][1]), "=&v"(q[R > 2 ? 2 : 0][0]), "=&v"(q[R > 2 ? 2 : 0][1]),
+                   "=&v"(q[R > 3 ? 3 : 0][0]), "=&v"(q[R > 3 ? 3 : 0][1])
+                 : [a0] "v"(a0), [a1] "v"(a1), [o1] "n"(RP), [o2] "n"(2 * RP), [o3] "n"(3 * RP) : "memory");
+  else if constexpr (R == 2)
+    asm volatile("ds_read_b128 %0, %[a0]\n\tds_read_b128 %1, %[a1]\n\t"
+                 "ds_read_b128 %2, %[a0] offset:%[o1]\n\tds_read_b128 %3, %[a1] offset:%[o1]\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(q[0][0]), "=&v"(q[0][1]), "=&v"(q[R > 1 ? 1 : 0][0]), "=&v"(q[R > 1 ? 1 : 0][1])
+                 : [a0] "v"(a0), [a1] "v"(a1), [o1] "n"(RP) : "memory");
+  else
+    asm volatile("ds_read_b128 %0, %[a0]\n\tds_read_b128 %1, %[a1]\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(q[0][0]), "=&v"(q[0][1]) : [a0] "v"(a0), [a1] "v"(a1) : "memory");
+  sfor<R>([&](auto RR) __attribute__((always_inline)) {
+    constexpr int r = decltype(RR)::value;
+    f32x16 nx;
+#pragma unroll
+    for (int e = 0; e < 16; e += 2) {     // element e = half (e & 1) of dword (e >> 1) & 3 of q[e >> 3] (Ch16::get's order)
+      const uint32_t d = q[r][e >> 3][(e >> 1) & 3];
+      nx[e] = mix_lo(d, scale);
+      nx[e + 1] = mix_hi(d, scale);
+    }
+    acc_br<BLK, r>(acc) = nx;
+  });
 }
 
 // ---- the MFMAs of one unit of phase P: cout blocks P-1..5 x 3 kh taps x 4 rows ----------------------
@@ -1406,7 +1514,7 @@ template <typename T, int BLK, int MODE, int LW = 0, bool NOISE = true, bool TRA
 __device__ __forceinline__ void epilogue(Acc24& acc, const PT& p, const BlkS& blk, const Bias16& bias,
                                          const ImgView& out, int out_cb, int ch_cb, const RowsRaw<T>* ex,
                                          const RowsRaw<T>* r2, bool has_res2, const Tile& t, char* smem = nullptr,
-                                         int slot0 = 0, RowsRaw<T>* keep = nullptr, float carry_scale = 0.f,
+                                         int slot0 = 0, RowsRaw<T>* keep = nullptr,
                                          bool full_store = true, char* mask_base = nullptr, int mask_slice = 0) {
   using C16 = Ch16<T>;
   const int lane = t.lane(), tj = lane & 31, th = lane >> 5;
@@ -1425,67 +1533,93 @@ __device__ __forceinline__ void epilogue(Acc24& acc, const PT& p, const BlkS& bl
   uint64_t seed = p.seed;
   if ((n1 || n2) && p.seed_dev) seed = __builtin_nontemporal_load(p.seed_dev);
   uint32_t mbits[4] = {0u, 0u, 0u, 0u};
+  // what the four rows of a lane share is worked out once: the lane's offset inside a row of the output view, and
+  // whether its COLUMN is stored (x1..x4 are only ever read back as HALO pixels by the neighbouring tiles — the tile's
+  // own pixels stay in the LDS / registers — so unless the slice is wanted in memory only the tile's border pixels are
+  // stored: 82 % fewer bytes through the lock-stepped store bursts).  `|`, not `||`: no branches around a compare.
+  const bool store_all = TRAIN || (MODE == 3 && full_store) || p.save_dense;              // wave-uniform
+  const bool col_edge = store_all | (tj == 0) | (tj == TW - 1);
+  const int lane_off = LW != 0 ? 2 * out_cb * out.gs + (ox + 1) * 32 + th * 16 : 0;
+  typename Ch16<_Float16>::Raw qs[R];      // the packed rows (LW != 0: fp16) and the offsets of their deferred stores
+  int offs[R];
   sfor<R>([&](auto RR) __attribute__((always_inline)) {
     constexpr int r = decltype(RR)::value;
     const int oy = oyb + r;
     const f32x16 a = acc_br<BLK, r>(acc);
-    float v[16], tmp[16];
-    // pairs: v_pk_add_f32 / v_pk_mul_f32 do two elements per instruction (same IEEE results as the scalar forms)
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    float tmp[16];
+    // pairs all the way (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32: same IEEE results as the scalar forms); element e
+    // of the row is w[e >> 1][e & 1]
+    f32x2 w[8];
+    auto pairs_of = [&](f32x2 (&o)[8]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = f32x2{tmp[2 * i], tmp[2 * i + 1]};
+    };
 #pragma unroll
     for (int e = 0; e < 16; e += 2) {
       const f32x2 av = {a[e], a[e + 1]}, bv = {bq[e >> 2][e & 3], bq[e >> 2][(e & 3) + 1]};
       const f32x2 x = av + bv;
       if constexpr (MODE != 3) {
         const f32x2 y = x * ESR_LRELU_SLOPE;                                     // LeakyReLU(0.2) = max(x, 0.2 x)
-        v[e] = __builtin_fmaxf(x[0], y[0]);
-        v[e + 1] = __builtin_fmaxf(x[1], y[1]);
+        w[e >> 1] = f32x2{__builtin_fmaxf(x[0], y[0]), __builtin_fmaxf(x[1], y[1])};
         if constexpr (TRAIN) {
           // one v_alignbit per element: shift the sign bit of lrelu(a) (= the sign of a) into the row's mask word
           // (channel e ends up at bit 15 - e; 1 = negative -> slope 0.2)
-          mbits[r] = __builtin_amdgcn_alignbit(mbits[r], __builtin_bit_cast(uint32_t, v[e]), 31);
-          mbits[r] = __builtin_amdgcn_alignbit(mbits[r], __builtin_bit_cast(uint32_t, v[e + 1]), 31);
+          mbits[r] = __builtin_amdgcn_alignbit(mbits[r], __builtin_bit_cast(uint32_t, (float)w[e >> 1][0]), 31);
+          mbits[r] = __builtin_amdgcn_alignbit(mbits[r], __builtin_bit_cast(uint32_t, (float)w[e >> 1][1]), 31);
         }
       } else {
-        v[e] = x[0];
-        v[e + 1] = x[1];
+        w[e >> 1] = x;
       }
     }
     if constexpr (MODE == 1) {
       const f32x16 a1 = acc_br<0, r>(acc);
 #pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] += a1[e];
+      for (int i = 0; i < 8; ++i) w[i] += f32x2{a1[2 * i], a1[2 * i + 1]};
     }
-    if constexpr (MODE == 2) {
-      C16::get(ex->q[r], tmp);
+    if constexpr (MODE == 2 && sizeof(T) == 2) {
+      // + x2 straight from its packed halves: h * 1 + w in one rounding is the sum a conversion and an add give
 #pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] = v[e] * 1.0f + tmp[e];
+      for (int i = 0; i < 8; ++i) {
+        const uint32_t d = ex->q[r].q[i >> 2][i & 3];
+        w[i] = f32x2{mix_add_lo(d, w[i][0]), mix_add_hi(d, w[i][1])};
+      }
+    } else if constexpr (MODE == 2) {
+      f32x2 x2v[8];
+      C16::get(ex->q[r], tmp);
+      pairs_of(x2v);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) w[i] += x2v[i];
     }
     if constexpr (MODE == 3) {
+      f32x2 rv[8];
       if (NOISE && ex) {           // explicit residual (fp32 path, noise): out = conv5*0.2 + x
         C16::get(ex->q[r], tmp);
+        pairs_of(rv);
 #pragma unroll
-        for (int e = 0; e < 16; ++e) v[e] = v[e] * 0.2f + tmp[e];
+        for (int i = 0; i < 8; ++i) w[i] = w[i] * 0.2f + rv[i];
       } else {                     // folded: the accumulators started at 5 x
 #pragma unroll
-        for (int e = 0; e < 16; ++e) v[e] *= 0.2f;
+        for (int i = 0; i < 8; ++i) w[i] *= 0.2f;
       }
       const uint32_t pix = (uint32_t)((t.b * p.H + oy) * p.W + ox);
       if (n1) {
 #pragma unroll
         for (int o = 0; o < 2; ++o) philox_normal8(pix, (uint32_t)(ch_cb * 4 + th * 2 + o), layer1, seed, &tmp[8 * o]);
+        pairs_of(rv);
 #pragma unroll
-        for (int e = 0; e < 16; ++e) v[e] = v[e] + tmp[e] * (p.sigma * v[e]);     // block.py:119-121
+        for (int i = 0; i < 8; ++i) w[i] = w[i] + rv[i] * (p.sigma * w[i]);     // block.py:119-121
       }
       if (has_res2) {
         C16::get(r2->q[r], tmp);
+        pairs_of(rv);
 #pragma unroll
-        for (int e = 0; e < 16; ++e) v[e] = v[e] * 0.2f + tmp[e];
+        for (int i = 0; i < 8; ++i) w[i] = w[i] * 0.2f + rv[i];
         if (n2) {
 #pragma unroll
           for (int o = 0; o < 2; ++o) philox_normal8(pix, (uint32_t)(ch_cb * 4 + th * 2 + o), layer2, seed, &tmp[8 * o]);
+          pairs_of(rv);
 #pragma unroll
-          for (int e = 0; e < 16; ++e) v[e] = v[e] + tmp[e] * (p.sigma * v[e]);
+          for (int i = 0; i < 8; ++i) w[i] = w[i] + rv[i] * (p.sigma * w[i]);
         }
       }
     }
@@ -1501,29 +1635,36 @@ __device__ __forceinline__ void epilogue(Acc24& acc, const PT& p, const BlkS& bl
     }
     const int po = (oy + 1) * wp32 + (ox + 1) * 32;
     if constexpr (LW == 0) {
+      float v[16];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) v[e] = w[e >> 1][e & 1];
       C16::store(out, inside ? out_cb : 0, th, inside ? po : (int)0x80000000u, v);
     } else {
-      typename C16::Raw q;
-      C16::pack(v, q.q);
-      // x1..x4 are only ever read back as HALO pixels by the neighbouring tiles (the tile's own pixels stay
-      // in the LDS / registers): unless the caller wants the dense slices in memory (save_dense), only the
-      // tile's border pixels are stored — 82 % fewer bytes through the lock-stepped store bursts
-      const bool edge = TRAIN || (MODE == 3 && full_store) || p.save_dense || tj == 0 || tj == TW - 1 || (t.wave == 0 && r == 0) ||
-                        (t.wave == NT / 64 - 1 && r == R - 1);
-      C16::store_packed_rows(out, (inside && edge) ? out_cb : 0, th, (inside && edge) ? po : (int)0x80000000u, q.q);
-      // beyond the image: the zero padding (only tiles that stick out of the image have such pixels: one scalar test)
+      typename C16::Raw& q = qs[r];
+      C16::pack2(w, q.q);
+      const bool edge = col_edge | (r == 0 && t.wave == 0) | (r == R - 1 && t.wave == NT / 64 - 1);     // .. or the tile's first / last row
+      const int off = (inside && edge) ? lane_off + (oy + 1) * wp32 : (int)0x80000000u;
+      // beyond the image: the zero padding (only tiles that stick out of the image have such pixels: one scalar test;
+      // the store of such a pixel is dropped — `inside` implies `live` — so it does not matter that it sees the zeros)
       if (ragged && !live) { q.q[0] = u32x4{0, 0, 0, 0}; q.q[1] = u32x4{0, 0, 0, 0}; }
-      if constexpr (LW & 1) lds_put_row(smem, slot0 + th, r, q.q, own_px, own_swz);
+      // v_permlane32_swap exchanges its two registers in place, and the packed row is wanted twice: by the store (behind
+      // the swaps) and by the LDS copy (as packed).  Store first, and hipcc copies all 8 dwords of the row in front of the
+      // swaps.  So the LDS copy goes first and the swaps run in place — once that copy has LANDED, so that they never
+      // overwrite registers a ds_write_b128 may still be reading: the store of row r is issued one row later, behind
+      // `lgkmcnt(2)` (the next row's two ds_writes; LDS operations return in order, ~80 instructions have passed), and
+      // only the last row takes the copies.  (MODE 3's carry into the next block reads the rows back from the LDS:
+      // carry_rows(), behind publish.)
+      constexpr bool defer = (LW & 1) != 0 && r + 1 < R;
+      if constexpr (!defer) C16::store_packed_rows_at(out, off, q.q);
+      else offs[r] = off;
+      if constexpr (LW & 1) {
+        lds_put_row(smem, slot0 + th, r, q.q, own_px, own_swz);
+        asm volatile("" ::: "memory");                     // the rows' ds_writes stay in row order: the count below relies on it
+      }
       if constexpr (LW & 2) keep->q[r] = q;
-      if constexpr (MODE == 3) {
-        // carry into the next block: its conv5 accumulators start at 5 x (x = this output AS STORED), so
-        // that block's tail `conv5*0.2 + x` needs no residual read (zero when it adds x explicitly)
-        float xs[16];
-        C16::get(q, xs);
-        f32x16 nx;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) nx[e] = carry_scale * xs[e];
-        acc_br<BLK, r>(acc) = nx;
+      if constexpr ((LW & 1) != 0 && r >= 1) {
+        lds_landed<2>(qs[r - 1].q);
+        C16::store_packed_rows_at(out, offs[r - 1], qs[r - 1].q);
       }
     }
   });
@@ -2085,7 +2226,7 @@ if constexpr (DIR == 2) {
         prewait_units<S, S::first(U_BULK, 1)>(ws_);     // bulk_1's first weights, in front of the epilogue's stores
         mfma_drain();
         RowsRaw<T> x1, x2;
-        epilogue<T, 0, 0, 2, true, TR, REG>(acc, q, bs, bb, dblk, 0, 0, nullptr, nullptr, false, t, smem, 0, &x1, 0.f, true, mbase, 0);     // x1 (kept: x still occupies its slots)
+        epilogue<T, 0, 0, 2, true, TR, REG>(acc, q, bs, bb, dblk, 0, 0, nullptr, nullptr, false, t, smem, 0, &x1, true, mbase, 0);     // x1 (kept: x still occupies its slots)
         ++epoch;
         trace_ev<TRC>(q, tile, ev);
         seg_open(acc);
@@ -2111,7 +2252,7 @@ if constexpr (DIR == 2) {
         lds_bias(smem, 32, t, bb);
         prewait_units<S, S::first(U_BULK, 2)>(ws_);     // bulk_2's first weights, in front of the epilogue's stores
         mfma_drain();
-        epilogue<T, 1, 1, 1, true, TR, REG>(acc, q, bs, bb, dblk, 1, 0, nullptr, nullptr, false, t, smem, 2, nullptr, 0.f, true, mbase, 1);       // x2
+        epilogue<T, 1, 1, 1, true, TR, REG>(acc, q, bs, bb, dblk, 1, 0, nullptr, nullptr, false, t, smem, 2, nullptr, true, mbase, 1);       // x2
         ++epoch;
         trace_ev<TRC>(q, tile, ev);
         seg_open(acc);
@@ -2128,7 +2269,7 @@ if constexpr (DIR == 2) {
         lds_bias(smem, 64, t, bb);
         prewait_units<S, S::first(U_BULK, 3)>(ws_);     // bulk_3's first weights, in front of the epilogue's stores
         mfma_drain();
-        epilogue<T, 2, 0, 1, true, TR, REG>(acc, q, bs, bb, dblk, 2, 0, nullptr, nullptr, false, t, smem, 0, nullptr, 0.f, true, mbase, 2);       // x3
+        epilogue<T, 2, 0, 1, true, TR, REG>(acc, q, bs, bb, dblk, 2, 0, nullptr, nullptr, false, t, smem, 0, nullptr, true, mbase, 2);       // x3
         ++epoch;
         trace_ev<TRC>(q, tile, ev);
         seg_open<3>(acc);
@@ -2146,7 +2287,7 @@ if constexpr (DIR == 2) {
         lds_get_rows(smem, 2, x2.q, t);   // x2's own pixels still sit in the slots x4 is about to take
         prewait_units<S, S::first(U_BULK, 4)>(ws_);     // bulk_4's first weights, in front of the epilogue's stores
         mfma_drain();
-        epilogue<T, 3, 2, 1, true, TR, REG>(acc, q, bs, bb, dblk, 3, 0, &x2, nullptr, false, t, smem, 2, nullptr, 0.f, true, mbase, 3);           // x4 (+ x2)
+        epilogue<T, 3, 2, 1, true, TR, REG>(acc, q, bs, bb, dblk, 3, 0, &x2, nullptr, false, t, smem, 2, nullptr, true, mbase, 3);           // x4 (+ x2)
         RowsRaw<T> tx0, tx1, tr0, tr1;
         ++epoch;
         trace_ev<TRC>(q, tile, ev);
@@ -2173,21 +2314,26 @@ if constexpr (DIR == 2) {
           // training: the folded form with the noise layers (the carried 5 x makes `conv5 * 0.2 + x` one multiply);
           // every block output is kept for the backward
           if (NZ == 1 || (NZ < 0 && noisy)) {
-            epilogue<T, 4, 3, 1, true, true>(acc, q, bs, bb, xout, 0, 0, nullptr, &tr0, has_res2, t, smem, 0, nullptr, 5.f, true);
-            epilogue<T, 5, 3, 1, true, true>(acc, q, bs, bb2, xout, 1, 1, nullptr, &tr1, has_res2, t, smem, 2, nullptr, 5.f, true);
+            epilogue<T, 4, 3, 1, true, true>(acc, q, bs, bb, xout, 0, 0, nullptr, &tr0, has_res2, t, smem, 0, nullptr, true);
+            epilogue<T, 5, 3, 1, true, true>(acc, q, bs, bb2, xout, 1, 1, nullptr, &tr1, has_res2, t, smem, 2, nullptr, true);
           } else {
-            epilogue<T, 4, 3, 1, false, true>(acc, q, bs, bb, xout, 0, 0, nullptr, &tr0, has_res2, t, smem, 0, nullptr, 5.f, true);
-            epilogue<T, 5, 3, 1, false, true>(acc, q, bs, bb2, xout, 1, 1, nullptr, &tr1, has_res2, t, smem, 2, nullptr, 5.f, true);
+            epilogue<T, 4, 3, 1, false, true>(acc, q, bs, bb, xout, 0, 0, nullptr, &tr0, has_res2, t, smem, 0, nullptr, true);
+            epilogue<T, 5, 3, 1, false, true>(acc, q, bs, bb2, xout, 1, 1, nullptr, &tr1, has_res2, t, smem, 2, nullptr, true);
           }
         } else if (noisy) {
-          epilogue<T, 4, 3, 1, true>(acc, q, bs, bb, xout, 0, 0, &tx0, &tr0, has_res2, t, smem, 0, nullptr, 0.f, full_out);
-          epilogue<T, 5, 3, 1, true>(acc, q, bs, bb2, xout, 1, 1, &tx1, &tr1, has_res2, t, smem, 2, nullptr, 0.f, full_out);
+          epilogue<T, 4, 3, 1, true>(acc, q, bs, bb, xout, 0, 0, &tx0, &tr0, has_res2, t, smem, 0, nullptr, full_out);
+          epilogue<T, 5, 3, 1, true>(acc, q, bs, bb2, xout, 1, 1, &tx1, &tr1, has_res2, t, smem, 2, nullptr, full_out);
         } else {
-          epilogue<T, 4, 3, 1, false, false, REG>(acc, q, bs, bb, xout, 0, 0, nullptr, &tr0, has_res2, t, smem, 0, nullptr, 5.f, full_out);
-          epilogue<T, 5, 3, 1, false, false, REG>(acc, q, bs, bb2, xout, 1, 1, nullptr, &tr1, has_res2, t, smem, 2, nullptr, 5.f, full_out);
+          epilogue<T, 4, 3, 1, false, false, REG>(acc, q, bs, bb, xout, 0, 0, nullptr, &tr0, has_res2, t, smem, 0, nullptr, full_out);
+          epilogue<T, 5, 3, 1, false, false, REG>(acc, q, bs, bb2, xout, 1, 1, nullptr, &tr1, has_res2, t, smem, 2, nullptr, full_out);
         }
-        pin_acc45(acc);
         publish(flags, tile, ++epoch, t, TRC ? &q : nullptr, &ev);
+        // the next block's conv5 accumulators, while the neighbours' flags are on their way (carry_rows): 5 x, or zero
+        // when that block's tail adds x explicitly (inference with noise)
+        { const float cs = (!TR && noisy) ? 0.f : 5.f;
+          carry_rows<4>(acc, smem, 0, cs, t);
+          carry_rows<5>(acc, smem, 2, cs, t); }
+        pin_acc45(acc);
         ws_.ring = (ws_.ring + S::N) & (WR - 1);
         trace_ev<TRC>(q, tile, ev);
         }

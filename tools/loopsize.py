@@ -11,7 +11,12 @@ llvm-objdump.  For every rdb_chain_kernel instantiation in it one JSON object is
                                   every MFMA of the kernel (the tile loop around it holds the tile set-up as well)
     mfma, span_insts, per_mfma    MFMAs in the loop; instructions from the first to the last of them; their ratio
     opcodes                       instructions of the loop by mnemonic
+    valu                          vector-ALU instructions of the loop that are no MFMA (`v_*`): with one wave per SIMD
+                                  each takes an issue slot of its own next to the MFMA stream
+    valu_in_segments              .. of them between two MFMAs that are at most 40 instructions apart
+    valu_tail                     .. of them behind the last MFMA
     kernel_s_memrealtime, kernel_scratch   s_memrealtime / scratch_* instructions in the whole kernel
+    sgpr_spill_count, vgpr_spill_count     from the kernel's metadata in the code object's notes
 
 A size and count report only: nothing is compared or asserted here.
 """
@@ -40,7 +45,24 @@ def disassemble(tu, defines, tmp):
     obj = os.path.join(tmp, os.path.basename(src)[:-4] + '.co')
     subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '--offload-device-only', '--no-gpu-bundle-output'] +
                           ['-D' + d for d in defines] + ['-c', src, '-o', obj], stderr=subprocess.DEVNULL)
-    return subprocess.check_output([os.path.join(LLVM, 'llvm-objdump'), '-d', obj], text=True)
+    notes = subprocess.run([os.path.join(LLVM, 'llvm-readelf'), '--notes', obj], text=True, capture_output=True).stdout
+    return subprocess.check_output([os.path.join(LLVM, 'llvm-objdump'), '-d', obj], text=True), notes
+
+
+def spill_counts(notes):
+    """{kernel symbol: {sgpr_spill_count, vgpr_spill_count}} from the AMDGPU metadata note (YAML, one map per kernel)"""
+    out, cur = {}, {}
+    for line in notes.split('\n'):
+        if line.startswith('  - '):               # a new entry of amdhsa.kernels (its arguments are nested deeper)
+            cur = {}
+        m = re.match(r'^(?:    |  - )\.(symbol|sgpr_spill_count|vgpr_spill_count):\s*(\S+)\s*$', line)
+        if not m:
+            continue
+        if m.group(1) == 'symbol':
+            out[m.group(2)[:-3] if m.group(2).endswith('.kd') else m.group(2)] = cur
+        else:
+            cur[m.group(1)] = int(m.group(2))
+    return out
 
 
 def demangle(names):
@@ -76,7 +98,11 @@ def branch_target(addr, ops):
     return addr + 4 + 4 * off
 
 
-def report(tu, name, pretty, ins):
+def is_valu(op):
+    return op.startswith('v_') and not op.startswith('v_mfma')
+
+
+def report(tu, name, pretty, ins, spills=None):
     r = collections.OrderedDict(tu=tu, kernel=pretty, kernel_bytes=sum(i[1] for i in ins))
     mf = [i[0] for i in ins if i[2].startswith('v_mfma')]
     best = None
@@ -94,10 +120,16 @@ def report(tu, name, pretty, ins):
         r['span_insts'] = len(span)
         r['per_mfma'] = round(len(span) / len(mf), 3)
         r['opcodes'] = dict(collections.Counter(i[2] for i in loop).most_common())
+        r['valu'] = sum(is_valu(i[2]) for i in loop)
+        at = [k for k, i in enumerate(loop) if i[2].startswith('v_mfma')]
+        r['valu_in_segments'] = sum(sum(is_valu(i[2]) for i in loop[a + 1:b]) for a, b in zip(at, at[1:]) if b - a - 1 <= 40)
+        r['valu_tail'] = sum(is_valu(i[2]) for i in loop[at[-1] + 1:])
     else:
         r['loop_bytes'] = None
     r['kernel_s_memrealtime'] = sum(i[2] == 's_memrealtime' for i in ins)
     r['kernel_scratch'] = sum(i[2].startswith('scratch_') for i in ins)
+    for k in ('sgpr_spill_count', 'vgpr_spill_count'):
+        r[k] = (spills or {}).get(k)
     return r
 
 
@@ -115,11 +147,13 @@ def main(argv):
         tus = sorted(f for f in glob.glob(os.path.join(CSRC, '*.hip')) if '#include "rdb_chain_kernel.h"' in open(f).read())
     with tempfile.TemporaryDirectory() as tmp:
         for tu in tus:
-            fns = kernels(disassemble(tu, defines, tmp))
+            text, notes = disassemble(tu, defines, tmp)
+            fns = kernels(text)
+            spills = spill_counts(notes)
             names = [n for n in fns if 'rdb_chain_kernel' in n]
             pretty = demangle(names)
             for n in names:
-                print(json.dumps(report(os.path.basename(tu).replace('.hip', ''), n, pretty.get(n, n), fns[n])), flush=True)
+                print(json.dumps(report(os.path.basename(tu).replace('.hip', ''), n, pretty.get(n, n), fns[n], spills.get(n))), flush=True)
 
 
 if __name__ == '__main__':
