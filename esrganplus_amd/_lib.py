@@ -272,6 +272,21 @@ class esr_img_metrics(C.Structure):
                 ('out', C.c_void_p), ('win', C.c_double * 11)]
 
 
+SET_METRICS_TILE_H, SET_METRICS_TILE_W = 16, 32      # ESR_SET_METRICS_TILE_H / _W: the work unit of esr_image_set_metrics
+
+
+class esr_set_metrics_item(C.Structure):
+    """One image pair of esr_image_set_metrics: a 32-byte entry of the DEVICE table."""
+    _fields_ = [('sr', C.c_void_p), ('hr', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32), ('first', C.c_int32),
+                ('_pad', C.c_int32)]
+
+
+class esr_set_metrics(C.Structure):
+    _fields_ = [('n', C.c_int32), ('crop', C.c_int32), ('bgr', C.c_int32), ('n_units', C.c_int32),
+                ('items', C.c_void_p), ('sizes_host', C.c_void_p), ('out', C.c_void_p), ('scratch', C.c_void_p),
+                ('win', C.c_double * 11)]
+
+
 class esr_frag_gather(C.Structure):
     _fields_ = [('src_off', C.c_void_p), ('src_base', C.c_void_p), ('dst', C.c_void_p), ('n', C.c_int64),
                 ('piece_bytes', C.c_int32), ('_pad', C.c_int32)]
@@ -313,7 +328,7 @@ EXPORTS = ['esr_packed_weight_bytes', 'esr_g32_dims', 'esr_conv_forward', 'esr_p
            'esr_rdb_mask_bytes', 'esr_rdb_check_abort', 'esr_debug_hold_cus', 'esr_debug_device_alias', 'esr_debug_chain_order_waits', 'esr_debug_chain_last_variant', 'esr_debug_chain_force_general',
            'esr_debug_mfma_probe', 'esr_debug_rdb_wgrad_follow', 'esr_dihedral_op', 'esr_tile_op',
            'esr_tile_x8_op', 'esr_l2_loss_forward', 'esr_fold3_op', 'esr_gan_loss_forward',
-           'esr_batch_assemble', 'esr_tile_many_op', 'esr_tile_img_op']
+           'esr_batch_assemble', 'esr_tile_many_op', 'esr_tile_img_op', 'esr_image_set_metrics']
 
 _lib = None
 _lock = threading.Lock()
@@ -379,7 +394,7 @@ def lib():
                          ('esr_dihedral_op', esr_dihedral), ('esr_tile_op', esr_tile),
                          ('esr_tile_x8_op', esr_tile_x8), ('esr_fold3_op', esr_fold3),
                          ('esr_batch_assemble', esr_batch), ('esr_tile_many_op', esr_tile_many),
-                         ('esr_tile_img_op', esr_tile_img)):
+                         ('esr_tile_img_op', esr_tile_img), ('esr_image_set_metrics', esr_set_metrics)):
             getattr(L, name).argtypes = [C.POINTER(st), C.c_void_p]
         if L.esr_sizeof_op() != C.sizeof(esr_op):
             raise HipExtensionError('ABI mismatch: sizeof(esr_op) C=%d ctypes=%d'

@@ -10,8 +10,8 @@ import math
 import torch.nn as nn
 
 from . import block as B
-from .functional import (run_rrdbnet, run_rrdbnet_images, run_rrdbnet_tiled, run_rrdbnet_tiled_many, run_rrdbnet_tiled_x8,
-                         run_rrdbnet_x8)
+from .functional import (run_rrdbnet, run_rrdbnet_evaluate, run_rrdbnet_images, run_rrdbnet_tiled, run_rrdbnet_tiled_many,
+                         run_rrdbnet_tiled_x8, run_rrdbnet_x8)
 
 
 SUPPORTED_UPSCALE = (1, 2, 3, 4, 8)
@@ -171,6 +171,17 @@ class _RRDBNetBase(B._PlannedModule):
         self._x4_only('forward_images')
         self._join_pending()
         return run_rrdbnet_images(self, images, tile, pad, windows_per_pass, bgr)
+
+    def evaluate_images(self, lr_images, hr_images, tile=96, pad=16, windows_per_pass=16, bgr=False, crop=None):
+        """The reference's test script (codes/test.py:49-110) for one image set: ``forward_images(lr_images, ...)``, then
+        PSNR, SSIM, PSNR_Y and SSIM_Y of every result against its ``hr_images`` entry (uint8 [4H, 4W, 3] on the same
+        GPU) in one device pass -> ``(sr_images, result)``; ``result.read()`` is the one read-back, an [n, 4] float64
+        array, ``result.averages()`` the script's four means.  ``crop=None`` cuts ``upscale`` pixels per side as the
+        script does.  Nothing synchronises before ``read()``.  See ``functional.run_rrdbnet_evaluate`` and
+        ``metrics.device_set_metrics``."""
+        self._x4_only('evaluate_images')
+        self._join_pending()
+        return run_rrdbnet_evaluate(self, lr_images, hr_images, tile, pad, windows_per_pass, bgr, crop)
 
 
 class RRDBNet(_RRDBNetBase):

@@ -977,3 +977,26 @@ def run_rrdbnet_images(net, images, tile=96, pad=16, windows_per_pass=16, bgr=Fa
     xin = [x.detach().contiguous() for x in images]
     return _run_tiled_set(net, 'tiled_img', E.build_rrdbnet_tiled_img_plan, groups, xin, sizes, dev,
                           lambda H, W: torch.empty((4 * H, 4 * W, 3), dtype=torch.uint8, device=dev), tile, pad, bool(bgr))
+
+
+def run_rrdbnet_evaluate(net, lr_images, hr_images, tile=96, pad=16, windows_per_pass=16, bgr=False, crop=None):
+    """codes/test.py:49-110 for one image set: ``run_rrdbnet_images`` on ``lr_images``, then
+    ``metrics.device_set_metrics`` on its results against ``hr_images`` (uint8 [4H, 4W, 3] device tensors, one per LR
+    image, channel order as ``bgr`` says) -> ``(sr_images, result)``: the uint8 results of ``run_rrdbnet_images`` and a
+    ``metrics.SetMetricsResult`` whose ``read()`` gives (psnr, ssim, psnr_y, ssim_y) per image.  ``crop=None`` cuts
+    ``net.upscale`` pixels from every side (test.py:75).  Sizes, types and the crop are checked before anything is
+    launched; everything is queued on the current stream and nothing synchronises before ``result.read()``."""
+    from . import metrics as M
+    lr, hr = _images_u8(lr_images), _images_u8(hr_images)
+    if len(lr) != len(hr):
+        raise ValueError('evaluate_images compares equally many images: %d lr, %d hr' % (len(lr), len(hr)))
+    s = net.upscale
+    for i, (a, b) in enumerate(zip(lr, hr)):
+        if (b.shape[0], b.shape[1]) != (s * a.shape[0], s * a.shape[1]):
+            raise ValueError('hr image %d of evaluate_images must be [%d, %d, 3], x%d of its lr image: got %s'
+                             % (i, s * a.shape[0], s * a.shape[1], s, tuple(b.shape)))
+        if b.device != a.device:
+            raise ValueError('hr image %d is on %s, its lr image on %s' % (i, b.device, a.device))
+    crop = M._set_crop([(b.shape[0], b.shape[1]) for b in hr], s if crop is None else crop)
+    sr = run_rrdbnet_images(net, lr, tile, pad, windows_per_pass, bgr)
+    return sr, M.device_set_metrics(sr, hr, crop, bgr)

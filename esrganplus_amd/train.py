@@ -41,6 +41,20 @@ def _buffer_like(buf, ref):
     return buf
 
 
+def _validate(self, lr_images, hr_images, **tiling):
+    """The validation pass of codes/train.py:121-159 on one image set: ``finish()``, then the generator's
+    ``evaluate_images(lr_images, hr_images, **tiling)`` — always the eval forward, the module's mode left as it is — ->
+    the average RGB PSNR as a float (train.py:148-150; cropped by the scale).  The per-image table (psnr, ssim, psnr_y,
+    ssim_y) stays on ``self.val_result``.  Valid between pipelined steps, as ``test()`` is; the read-back of the table is
+    the one synchronisation."""
+    self.finish()
+    if not hasattr(self.netG, 'evaluate_images'):
+        raise ValueError('validate needs a generator with evaluate_images (RRDBNet / RRDB_Net at x4), got %s'
+                         % type(self.netG).__name__)
+    self.val_result = self.netG.evaluate_images(lr_images, hr_images, **tiling)[1]
+    return self.val_result.averages()[0]
+
+
 class ESRGANPlusStep:
     def __init__(self, netG, netD, netF, lr_G=1e-4, lr_D=1e-4, beta1_G=0.9, beta1_D=0.9,
                  pixel_weight=1e-2, feature_weight=1.0, gan_weight=5e-3, loss_scale=1.0, data_parallel=None,
@@ -225,6 +239,8 @@ class ESRGANPlusStep:
         step left in flight."""
         self.finish()
         return {'optimizers': [self.optimizer_G.state_dict(), self.optimizer_D.state_dict()]}
+
+    validate = _validate
 
     def finish(self):
         """Orders what a pipelined step (``step(..., sync_log=False)``) left on the side stream — the end of the D
@@ -740,6 +756,8 @@ class PSNRStep:
         if self._ev_tail is not None:
             torch.cuda.current_stream().wait_event(self._ev_tail)
 
+    validate = _validate
+
     def state_dict(self):
         """The optimizer's state (base_model.py:65-74 `save_training_state`), behind whatever is still in flight."""
         self.finish()
@@ -813,6 +831,7 @@ class SRGANStep:
     comm_reset = ESRGANPlusStep.comm_reset
     comm_report = ESRGANPlusStep.comm_report
     finish = ESRGANPlusStep.finish
+    validate = _validate
 
     @staticmethod
     def g_update_due(iteration, D_update_ratio=1, D_init_iters=0):

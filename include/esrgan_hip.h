@@ -655,6 +655,55 @@ typedef struct esr_img_metrics {
   double win[11];            /* 1-D Gaussian window (cv2.getGaussianKernel(11, 1.5)); the 2-D one is its outer product */
 } esr_img_metrics;
 
+/* The four validation sums of an image SET in one launch set (esr_image_set_metrics; csrc/metrics_set.hip): what
+ * codes/test.py:69-110 logs per image — PSNR, SSIM, PSNR_Y, SSIM_Y — and the validation loop of codes/train.py:121-159
+ * averages, from pairs of 8-bit images on the device (esr_tile_img's stitch results against their ground truth).
+ * Pair i is items[i]: sr and hr are uint8 [H][W][3] (HWC, any byte alignment, rows of 3 W bytes without padding).  With
+ * (ch, cw) = (H - 2 crop, W - 2 crop) the cropped region, k = win, and a(y, x, c), b(y, x, c) the bytes of sr, hr at
+ * cropped position (y, x), out[4 i + 0 .. 3] receives, in fp64:
+ *   0  sum over y, x, c of (a - b)^2                                               (util.py:107-114; exact, an integer)
+ *   1  sum over y, x of (Y_a - Y_b)^2,  Y = (24.966 B + 128.553 G + 65.481 R) / 255 + 16, NOT rounded (test.py:85-89);
+ *      B is byte 0 of a pixel when bgr != 0 (cv2, metrics.hip's images, esr_tile_img with bgr), else byte 2 (PIL)
+ *   2  sum over the three channels and the (ch - 10) x (cw - 10) valid positions of the SSIM map of util.py:117-137:
+ *      window outer(k, k), C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2
+ *   3  the same sum over the Y plane
+ * Sums 2 and 3 are 0 when ch <= 10 or cw <= 10 (no valid position).  The window runs as a row filter and a column filter
+ * (22 taps, not 121): against esr_image_metrics the fp64 summation order differs, nothing else.
+ * Work units: image i is cut into ceil(ch / ESR_SET_METRICS_TILE_H) x ceil(cw / ESR_SET_METRICS_TILE_W) tiles, one
+ * workgroup each; items[i].first is the number of tiles of the images before it (items[0].first = 0) and n_units the
+ * number of all tiles.  Every workgroup writes its four partial sums to scratch[4 unit .. 4 unit + 3] (4 n_units doubles,
+ * need not be initialised), and a second kernel adds an image's partials in an order that depends on its tile count
+ * alone.  No floating-point atomics: two calls on the same bytes give the same bits, and an image's four sums do not
+ * depend on the other images of the call or on its place in the table.
+ * The table lives in DEVICE memory (read by the launch: it must stay valid until the launch has run) and cannot be
+ * checked by this entry.  So the caller repeats the sizes in HOST memory: sizes_host[2 i], sizes_host[2 i + 1] = H, W of
+ * pair i, read during the call only.  From them the entry refuses (ESR_ERR_INVALID) a crop that leaves no pixels of some
+ * image and an n_units that is not the sum of the tile counts, and sizes the launch; whoever fills the table guarantees
+ * that its H, W and first agree with sizes_host and that sr, hr are live images of that size.  (The largest H, W alone
+ * would not do: it is the smallest image that a crop empties.)  A workgroup whose unit lies outside its item's tiles
+ * reads no image and adds zeros.  The kernel reads whole aligned dwords that contain image bytes.                       */
+#define ESR_SET_METRICS_TILE_H 16
+#define ESR_SET_METRICS_TILE_W 32
+typedef struct esr_set_metrics_item {   /* one image pair, 32 bytes; lives in DEVICE memory */
+  const uint8_t* sr;             /* [H][W][3] uint8 */
+  const uint8_t* hr;             /* [H][W][3] uint8 */
+  int32_t H, W;
+  int32_t first;                 /* work units (tiles) of the items before this one */
+  int32_t _pad;
+} esr_set_metrics_item;
+
+typedef struct esr_set_metrics {
+  int32_t n;                     /* image pairs, >= 1 */
+  int32_t crop;                  /* pixels cut from every side, >= 0 */
+  int32_t bgr;                   /* byte 0 of a pixel is B (else R): matters to the luma only */
+  int32_t n_units;               /* tiles of all images */
+  const esr_set_metrics_item* items;   /* n entries, device memory, 8-byte aligned */
+  const int32_t* sizes_host;     /* n x (H, W), HOST memory */
+  double* out;                   /* n x 4 doubles (device) */
+  double* scratch;               /* 4 n_units doubles (device) */
+  double win[11];                /* 1-D Gaussian window, normalised (esr_img_metrics.win) */
+} esr_set_metrics;
+
 /* ---- fused ResidualDenseBlock_5C chain (rdb_fused.hip) -------------------------------------------
  * ONE persistent launch runs n_blocks dense blocks (block.py:260-268) back to back on every 16x32
  * tile, the fp32 accumulators of all 192 output channels of the block in flight held in registers
@@ -944,6 +993,7 @@ int esr_gather_fragments(const esr_frag_gather* g, esr_stream_t stream);
 int esr_rdb_wgrad_run(const esr_rdb_wgrad* p, esr_stream_t stream);
 int64_t esr_rdb_wgrad_workspace_elems(int32_t B, int32_t H, int32_t W, int32_t n_blocks);
 int esr_image_metrics(const esr_img_metrics* p, esr_stream_t stream);   /* replaces util.py:71-158 on the device */
+int esr_image_set_metrics(const esr_set_metrics* p, esr_stream_t stream);   /* added under ABI 6: a pure addition; test.py:69-110 over an image set */
 
 /* The train step's losses with their gradients, one launch each (SRRaGAN_model.py:124-137,150-156).
  * esr_l1_loss_forward: *loss = weight * mean|a - b| (nn.L1Loss, loss.py cri_pix / cri_fea);
@@ -988,7 +1038,7 @@ int esr_graph_destroy(esr_graph_t g);
 int esr_run_ops_timed(const esr_op* ops, int32_t n, esr_stream_t stream, float* ms_out);
 
 const char* esr_last_error(void);
-int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8, esr_fold3 / esr_fold3_op / ESR_OP_FOLD3 with esr_pool modes 4 / 5, esr_batch / esr_batch_item / esr_batch_assemble, esr_tile_many / esr_tile_item / esr_tile_many_op / ESR_OP_TILE_MANY, and esr_tile_img / esr_tile_img_item / esr_tile_img_op / ESR_OP_TILE_IMG were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
+int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8, esr_fold3 / esr_fold3_op / ESR_OP_FOLD3 with esr_pool modes 4 / 5, esr_batch / esr_batch_item / esr_batch_assemble, esr_tile_many / esr_tile_item / esr_tile_many_op / ESR_OP_TILE_MANY, esr_tile_img / esr_tile_img_item / esr_tile_img_op / ESR_OP_TILE_IMG, and esr_set_metrics / esr_set_metrics_item / esr_image_set_metrics were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
                                 esr_l1_loss, esr_ragan_loss, ESR_OPF_SIDE_FREE) */
 size_t esr_sizeof_op(void);
 

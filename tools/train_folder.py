@@ -3,14 +3,17 @@
 decoded uint8 images stay on the device and every batch is one launch):
 
     python tools/train_folder.py HR_DIR [--lr-dir DIR] [--scale S] [--lr-size N] [--batch B] [--iters N] [--nb N]
-                                 [--precision fp16|fp32] [--seed K] [--out DIR]
+                                 [--precision fp16|fp32] [--seed K] [--out DIR] [--val LR_DIR HR_DIR] [--val-freq N]
 
 HR_DIR: the HR images (sizes may differ; each is cut to a multiple of the scale with ``data.modcrop``, as the reference
 does for validation images — without --lr-dir the LR windows are resampled from them on the fly).  --lr-dir: the LR
 images, paired with the HR ones by sorted name (HR = scale x LR).  The generator is an ``RRDBNet`` with synthetic weights
 (as ``sr_infer.py synthetic``), trained by a ``PSNRStep`` (l1) for --iters iterations over ``TrainSet.epoch``.  Prints
 the loss of every iteration and a last line ``iters N, last loss X``.  --out DIR: the generator's state dict is saved
-there as ``G_iters<N>.pth``; nothing else is written, nothing is downloaded."""
+there as ``G_iters<N>.pth``; nothing else is written, nothing is downloaded.  --val LR_DIR HR_DIR: a validation set, paired
+by sorted name (HR = 4 x LR; x4 only), scored every --val-freq iterations (default 100) with ``PSNRStep.validate`` — the
+validation pass of the reference's train loop, one device pass — and printed as the reference logs it:
+``# Validation # PSNR: 2.3456e+01``."""
 import argparse
 import glob
 import os
@@ -44,6 +47,8 @@ def main():
     ap.add_argument('--precision', default='fp16', choices=('fp16', 'fp32'))
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--out')
+    ap.add_argument('--val', nargs=2, metavar=('LR_DIR', 'HR_DIR'))
+    ap.add_argument('--val-freq', type=int, default=100)
     a = ap.parse_args()
     random.seed(a.seed)
     torch.manual_seed(a.seed)
@@ -62,12 +67,22 @@ def main():
     netG = arch.RRDBNet(3, 3, 64, a.nb, upscale=a.scale).to(dev).train().set_precision(a.precision)
     netG.load_state_dict(synth.rrdbnet_state_dict(nb=a.nb, seed=a.seed, upscale=a.scale), strict=True)
     step = train.PSNRStep(netG, loss_scale='dynamic' if a.precision == 'fp16' else 1.0)
+    val = None
+    if a.val:
+        if a.val_freq < 1:
+            sys.exit('train_folder.py: --val-freq takes an int >= 1, got %d' % a.val_freq)
+        val = [[torch.from_numpy(im).to(dev) for im in read_dir(d)] for d in a.val]
     it, loss = 0, float('nan')
     while it < a.iters:
         for var_L, real_H in ts.epoch(a.batch):
             it += 1
             loss = step.step(var_L, real_H)['l_pix']
             print('iter %d  l_pix %.6f' % (it, loss), flush=True)
+            if val and it % a.val_freq == 0:
+                try:
+                    print('# Validation # PSNR: {:.4e}'.format(step.validate(*val)), flush=True)
+                except ValueError as e:
+                    sys.exit('train_folder.py: --val: %s' % e)
             if it == a.iters:
                 break
     step.finish()
