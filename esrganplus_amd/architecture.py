@@ -117,6 +117,7 @@ class _RRDBNetBase(B._PlannedModule):
         eight flip / transpose variants, per image, as one batched launch plan -> [B, out_nc, sH, sW] float32 without
         gradient.  Always the eval forward; ``self.training`` and ``requires_grad`` are left as they are.  See
         ``functional.run_rrdbnet_x8``."""
+        self._ends_fit('forward_x8')
         self._join_pending()
         return run_rrdbnet_x8(self, x, slots_per_pass)
 
@@ -126,12 +127,20 @@ class _RRDBNetBase(B._PlannedModule):
             raise ValueError('%s: the tiled forms are x4-only (this net has upscale=%d); use forward / forward_x8'
                              % (what, self.upscale))
 
+    def _ends_fit(self, what):
+        # the dihedral / gather / stitch kernels (esr_dihedral, esr_tile, esr_tile_x8) move at most 8 image channels:
+        # refused here, before any plan or buffer exists, not by the C entry of the first launch
+        if self.in_nc > 8 or self.out_nc > 8:
+            raise ValueError('%s: expected in_nc <= 8 and out_nc <= 8 (the x8 and tiled forms move at most 8 image '
+                             'channels), got in_nc=%d, out_nc=%d; use forward' % (what, self.in_nc, self.out_nc))
+
     def forward_tiled(self, x, tile=96, pad=16, tiles_per_pass=None):
         """Tiled eval forward: windows of tile + 2 pad LR pixels inside the image, ``tiles_per_pass`` of them per image as
         one batch, every tile's owned rectangle copied into the result -> [B, out_nc, 4H, 4W] float32 without gradient.
         One launch plan serves every image size; exact for pad >= 15 nb + 4, an approximation below.  Always the eval
         forward; ``self.training`` and ``requires_grad`` are left as they are.  See ``functional.run_rrdbnet_tiled``."""
         self._x4_only('forward_tiled')
+        self._ends_fit('forward_tiled')
         self._join_pending()
         return run_rrdbnet_tiled(self, x, tile, pad, tiles_per_pass)
 
@@ -142,6 +151,7 @@ class _RRDBNetBase(B._PlannedModule):
         size; mathematically ``forward_x8(x)`` for pad >= 15 nb + 4, an approximation below.  Always the eval forward;
         ``self.training`` and ``requires_grad`` are left as they are.  See ``functional.run_rrdbnet_tiled_x8``."""
         self._x4_only('forward_tiled_x8')
+        self._ends_fit('forward_tiled_x8')
         self._join_pending()
         return run_rrdbnet_tiled_x8(self, x, tile, pad, tiles_per_pass, slots_per_pass)
 
@@ -155,6 +165,7 @@ class _RRDBNetBase(B._PlannedModule):
         set, scales other than 4, blending.  See ``functional.run_rrdbnet_tiled_many``; for 8-bit images in and out,
         ``forward_images``."""
         self._x4_only('forward_tiled_many')
+        self._ends_fit('forward_tiled_many')
         self._join_pending()
         return run_rrdbnet_tiled_many(self, images, tile, pad, windows_per_pass)
 
@@ -235,6 +246,54 @@ class _SeqNet(B._PlannedModule):
         # by attribute access (`_pspec`), not `parameters()`: that is empty on a nn.DataParallel replica
         return any(t.requires_grad for _, t in self._pspec())
 
+    _input_size = None      # nets with a linear head: the side of the square input that head was sized for
+
+    def _check_input(self, x, what, like=None):
+        """The input contract of every entry point, on the host, before the device is touched or a plan is built: the
+        layout op is built for the first conv's channels and then pointed at the tensor's memory, and the head's first
+        linear reads ``w1`` with the feature count of the plan's last map — a tensor of another shape would be read
+        past its end or with the wrong strides.  ``like``: the shape the other operand of a pair had."""
+        shape = tuple(x.shape)
+        if like is not None and shape != tuple(like):
+            raise ValueError('%s %s: the two operands of a pair must have one shape: expected %s, got %s'
+                             % (type(self).__name__, what, tuple(like), shape))
+        ok = self.__dict__.setdefault('_shapes_ok', set())
+        if shape in ok:
+            return
+        spec = self._spec()
+        cin0, name = spec[0]['cin'], type(self).__name__
+        want = '[B, %d, H, W]' % cin0
+        if len(shape) != 4:
+            raise ValueError('%s %s: expected a 4-D input %s, got %d-D %s' % (name, what, want, len(shape), shape))
+        if shape[1] != cin0:
+            raise ValueError('%s %s: expected %d input channels (%s), got %d in %s'
+                             % (name, what, cin0, want, shape[1], shape))
+        if min(shape[2:]) < 1:
+            raise ValueError('%s %s: expected a non-empty input %s, got %s' % (name, what, want, shape))
+        ch, h, w = cin0, shape[2], shape[3]
+        for s in spec:
+            if 'save' in s:
+                continue
+            if 'shuffle' in s:
+                ch, h, w = ch // s['shuffle'] ** 2, h * s['shuffle'], w * s['shuffle']
+            elif 'pool' in s:
+                h, w = h // 2, w // 2
+            elif s.get('ups'):
+                ch, h, w = s['cout'], 2 * h, 2 * w
+            else:
+                pad = (s['ks'] - 1) // 2
+                ch, h, w = s['cout'], (h + 2 * pad - s['ks']) // s['stride'] + 1, (w + 2 * pad - s['ks']) // s['stride'] + 1
+            if h < 1 or w < 1:
+                raise ValueError('%s %s: expected an input whose map survives every stride-2 conv and pool, got %s: '
+                                 'the map is %d x %d behind %s' % (name, what, shape, h, w, s.get('conv', 'a pool')))
+        head = self._head()
+        if head is not None and ch * h * w != head['w1'].shape[1]:
+            n = self._input_size
+            raise ValueError('%s %s: expected [B, %d, %s, %s] inputs (the head takes %d features), got %s, which '
+                             'flattens to %d x %d x %d = %d features'
+                             % (name, what, cin0, n, n, head['w1'].shape[1], shape, ch, h, w, ch * h * w))
+        ok.add(shape)
+
     def _plan_for(self, wp, dp, shape, dev, *, training, need_bwd, want_w, groups=1, bwd_B=None, dual=None, own=False):
         """A free plan of this configuration's pool, built on first use.  own: the plan gets an input-gradient pack and
         head weights of its own (see _run_forward)."""
@@ -263,6 +322,7 @@ class _SeqNet(B._PlannedModule):
         return plan
 
     def _run_forward(self, x, need_bwd, groups=1, bwd_B=None, dual=None):
+        self._check_input(x, 'forward')
         E.require_cuda(x, 'input')
         xin = x.detach().contiguous().float()
         dev = xin.device
@@ -311,6 +371,7 @@ class _SeqNet(B._PlannedModule):
     # the same plan (same pool key), the same launches on half the batch each, the running-statistics updates in the
     # reference's order (the early half's update is deferred to plan.restat1, which the caller runs after the late half).
     def _pair_begin(self, b):
+        self._check_input(b, '_pair_begin')
         E.require_cuda(b, 'input')
         xb = b.detach().contiguous().float()
         n, C_, H, W = xb.shape
@@ -334,6 +395,8 @@ class _SeqNet(B._PlannedModule):
         return plan, lease
 
     def _pair_finish(self, plan, a):
+        self._check_input(a, '_pair_finish', like=plan.keep_x[0].shape)
+        E.require_cuda(a, 'input')
         xa = a.detach().contiguous().float()
         half = plan.fwd_half[0]
         half.array()[plan.in_op].u.layout.nchw = xa.data_ptr()
@@ -342,6 +405,7 @@ class _SeqNet(B._PlannedModule):
         return plan.out_tensor.clone()
 
     def forward(self, x):
+        self._check_input(x, 'forward')
         self._join_pending()
         need = torch.is_grad_enabled() and (x.requires_grad or self._wants_param_grads())
         if not need:
@@ -355,8 +419,8 @@ class _SeqNet(B._PlannedModule):
         order (esr_bn.groups).  When no parameter requires a gradient and ``b`` does not either (the detached
         ``real`` operand of the G step), the backward runs on ``a``'s half only and ``self(b)`` comes back
         detached."""
-        if a.shape != b.shape:
-            raise ValueError('forward_pair: the two batches must have one shape')
+        self._check_input(a, 'forward_pair')
+        self._check_input(b, 'forward_pair', like=a.shape)
         self._join_pending()
         n = a.shape[0]
         x = torch.cat([a, b])
@@ -387,8 +451,8 @@ class _SeqNet(B._PlannedModule):
         gives the parameter gradients.  Training mode only."""
         if not (self._shared_ok and self.training and torch.is_grad_enabled() and a.requires_grad):
             raise RuntimeError('forward_shared: a training-mode pass whose first operand requires a gradient')
-        if a.shape != b.shape:
-            raise ValueError('forward_shared: the two batches must have one shape')
+        self._check_input(a, 'forward_shared')
+        self._check_input(b, 'forward_shared', like=a.shape)
         self._join_pending()
         holder = []
         y = CN.SharedFirstFn.apply(a, b, self, holder)
@@ -469,17 +533,17 @@ class _DiscriminatorVGG(_SeqNet):
 
 class Discriminator_VGG_128(_DiscriminatorVGG):
     """codes/models/modules/architecture.py:87-129 — 128x128 inputs: 10 convs, Linear(512*4*4, 100)."""
-    _pairs, _final = 5, 4
+    _pairs, _final, _input_size = 5, 4, 128
 
 
 class Discriminator_VGG_96(_DiscriminatorVGG):
     """architecture.py:178-221 — 96x96 inputs: the same 10 convs, Linear(512*3*3, 100)."""
-    _pairs, _final = 5, 3
+    _pairs, _final, _input_size = 5, 3, 96
 
 
 class Discriminator_VGG_192(_DiscriminatorVGG):
     """architecture.py:224-270 — 192x192 inputs: 12 convs (one more 512-channel pair), Linear(512*3*3, 100)."""
-    _pairs, _final = 6, 3
+    _pairs, _final, _input_size = 6, 3, 192
 
 
 class _SNLayer(nn.Module):
@@ -530,6 +594,7 @@ class Discriminator_VGG_128_SN(_SeqNet):
 
     _has_bn = False
     _per_call_weights = True
+    _input_size = 128
 
     def __init__(self):
         super().__init__()
@@ -571,6 +636,7 @@ class Discriminator_VGG_128_SN(_SeqNet):
         return ps
 
     def forward(self, x):
+        self._check_input(x, 'forward')          # before the power iteration: a refused input leaves weight_u alone
         if self.training:
             self._eff = [m.normalised() for m in self._sn_layers()]
             self.invalidate()                   # the buffers the plans pack from were rewritten in place

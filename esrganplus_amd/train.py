@@ -55,10 +55,25 @@ def _validate(self, lr_images, hr_images, **tiling):
     return self.val_result.averages()[0]
 
 
+def _check_channels(what, netG, netD, netF):
+    """The generator's images are what the discriminator and the feature extractor read: their channel counts must
+    agree before a step is built (the networks' plans take the first conv's channels on trust from their caller)."""
+    g = getattr(getattr(netG, 'module', netG), 'out_nc', None)
+    d = getattr(getattr(netD, 'module', netD), 'in_nc', None)
+    if g is None:
+        return
+    if d is not None and g != d:
+        raise ValueError('%s: netD expects %d input channels (in_nc), got a generator with out_nc = %d' % (what, d, g))
+    if netF is not None and g != 3:
+        raise ValueError('%s: the feature term (VGG) expects 3 input channels, got a generator with out_nc = %d; '
+                         'train such a generator without it (SRGANStep with feature_weight = 0, or PSNRStep)' % (what, g))
+
+
 class ESRGANPlusStep:
     def __init__(self, netG, netD, netF, lr_G=1e-4, lr_D=1e-4, beta1_G=0.9, beta1_D=0.9,
                  pixel_weight=1e-2, feature_weight=1.0, gan_weight=5e-3, loss_scale=1.0, data_parallel=None,
                  pixel_criterion='l1', feature_criterion='l1'):
+        _check_channels('ESRGANPlusStep', netG, netD, netF)
         self.netG, self.netD, self.netF = netG, netD, netF
         # 'l1' / 'l2' (SRRaGAN_model.py:31-53): the raw and the autograd form of each criterion's one launch
         self._pix_raw, self._pix_loss = LS.criterion(pixel_criterion)
@@ -800,6 +815,7 @@ class SRGANStep:
         if self.l_fea_w and netF is None:
             raise ValueError('SRGANStep: feature_weight > 0 needs netF')
         self.netF = netF if self.l_fea_w else None
+        _check_channels('SRGANStep', netG, netD, self.netF)
         self.gan_type = str(gan_type).lower()
         LS.gan_kind(self.gan_type)                # refuses 'wgan-gp' and unknown names
         self.D_update_ratio = int(D_update_ratio) if D_update_ratio else 1

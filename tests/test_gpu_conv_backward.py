@@ -8,9 +8,11 @@ so a later change that drops one fails there instead of silently narrowing the t
 reference adjoint used for the up-convs, run without a GPU.
 
 Error bounds are relative to the reference's largest magnitude, a few times the worst error measured on an MI355X.
-Weight gradients are fp32 sums of products of stored values: both precisions at 2e-6 (worst 5.6e-7 fp32, 3.0e-7 fp16).
+Weight gradients are fp32 sums of products of stored values: both precisions at 2e-6 (worst 6.1e-7 fp32 — the bias
+gradient of a cout-1 conv —, 3.0e-7 fp16; cin 1, cin 9 / 17 and cout 1 otherwise at most 5.3e-7 / 1.7e-7).
 Input gradients: fp32 at 4e-6 (worst 8.2e-7); fp16 at 1.5e-3, where rounding the stored fp16 result alone costs up to
-2^-11 of the scale (worst 4.2e-4).  The `exit` cases run the epilogue's third stage as engine.exit_to_conv uses it below
+2^-11 of the scale (worst 4.2e-4); the input gradients of cin-1 and cin-9 / cin-17 convs, into G32 and into fp32 NCHW
+(nchw_out_c = 1), at most 6.8e-7 fp32 and 2.6e-4 fp16.  The `exit` cases run the epilogue's third stage as engine.exit_to_conv uses it below
 an RRDB boundary — res2 with beta != 1, Philox noise on out and on out3 = v * gamma * (1 + sigma z3), the mask next to
 res2 — at the same bounds (worst 3.5e-4 fp16, 1.1e-7 fp32), in fp32 also bit for bit against explicit z2 / z3."""
 import zlib
@@ -141,6 +143,17 @@ WG_CASES = [
     ('fp16', 37, 256, 64, 1, 1, 0, 5, 12),      # 1x1 small maps: four images per workgroup, B not a multiple
     ('fp16', 5, 64, 64, 3, 1, 0, 8, 8),         # packed (cross-check of test_gpu_wgrad_small_maps)
     ('fp16', 6, 64, 64, 4, 2, 0, 3, 6),         # packed stride 2
+    # off-recipe channel counts: cin 1, a second input group of ONE channel (17 fp16, 9 fp32), cout 1; the 4x4/s2 form
+    # with one input and with one output channel
+    ('fp32', 2, 1, 40, 3, 1, 0, 13, 40),
+    ('fp32', 2, 9, 24, 3, 1, 0, 13, 40),
+    ('fp32', 2, 24, 1, 3, 1, 0, 13, 40),
+    ('fp32', 2, 1, 24, 4, 2, 0, 9, 20),
+    ('fp16', 2, 1, 64, 3, 1, 0, 13, 40),
+    ('fp16', 2, 17, 32, 3, 1, 0, 13, 40),
+    ('fp16', 3, 32, 1, 3, 1, 0, 10, 40),
+    ('fp16', 2, 1, 64, 4, 2, 0, 9, 20),
+    ('fp16', 2, 64, 1, 4, 2, 0, 9, 20),
 ]
 
 
@@ -153,6 +166,7 @@ def test_wgrad_cases_reach_every_branch():
     for prec, B, cin, cout, ks, st, ups, H, W in WG_CASES:
         if prec == 'fp32':
             seen.add(('fp32', ks, st, ups))
+            seen |= {('fp32 cin', cin), ('fp32 cout', cout), ('fp32 cin', cin, ks, st)}
             continue
         g = wgrad16_grid(B, H, W, cout, cin, ks, st, ups)
         seen.add(('fp16', ks, st, ups, g['nco'], g['packed']))
@@ -163,11 +177,17 @@ def test_wgrad_cases_reach_every_branch():
         seen.add(('cin', cin))
         seen.add(('cout', cout))
         seen.add(('odd groups', cdiv(cin, 16) % 2 == 1 and cin > 16))
+        seen.add(('one-channel last group', cin > 16 and cin % 16 == 1))
+        seen |= {('cin', cin, ks, st), ('cout', cout, ks, st)}
     for k in [('fp32', 3, 1, 0), ('fp32', 3, 1, 1), ('fp32', 1, 1, 0), ('fp32', 4, 2, 0),
               ('fp16', 3, 1, 0, 1, False), ('fp16', 3, 1, 0, 2, False), ('fp16', 3, 1, 1, 2, False),
               ('fp16', 3, 1, 1, 1, False), ('fp16', 1, 1, 0, 1, False), ('fp16', 1, 1, 0, 2, False),
               ('fp16', 4, 2, 0, 2, False), ('fp16', 3, 1, 0, 2, True), ('fp16', 4, 2, 0, 2, True),
-              ('ipw>1', True), ('ragged W', True), ('ragged H', True), ('cin', 3), ('cout', 3), ('odd groups', True)]:
+              ('ipw>1', True), ('ragged W', True), ('ragged H', True), ('cin', 3), ('cout', 3), ('odd groups', True),
+              # off the recipe: one input / output channel (3x3 and the 4x4/s2 form), a last group of ONE channel
+              ('cin', 1), ('cout', 1), ('one-channel last group', True), ('cin', 1, 3, 1), ('cout', 1, 3, 1),
+              ('cin', 1, 4, 2), ('cout', 1, 4, 2), ('fp32 cin', 1), ('fp32 cin', 9), ('fp32 cout', 1),
+              ('fp32 cin', 1, 4, 2)]:
         assert k in seen, k
 
 
@@ -205,6 +225,15 @@ DG_CASES = [
     ('f16_general_res2', 'fp16', 2, 96, 48, '3x3', 13, 40, 0, 'general2', None, (1, 'plain', 1)),
     ('f32_general_res2', 'fp32', 2, 96, 48, '3x3', 13, 40, 0, 'general2', None, (4, 'plain', 1)),
     ('f16_sum_fold', 'fp16', 2, 64, 48, '3x3', 13, 40, 0, 'plain', (32, 0, 32), (1, 'plain', 1)),
+    # off-recipe channel counts.  nchw_*: fea_conv's input gradient as the training plan's exit issues it (no G32
+    # output, nchw_out_c = the forward cin = 1); cin17 / cin9: the input gradient's second group holds ONE channel
+    ('f16_nchw_cin1', 'fp16', 2, 1, 64, '3x3', 13, 40, 0, 'nchw', None, (1, 'pipe', 1)),
+    ('f32_nchw_cin1', 'fp32', 2, 1, 64, '3x3', 13, 40, 0, 'nchw', None, (4, 'pipe', 1)),
+    ('f16_nchw_cin3', 'fp16', 2, 3, 64, '3x3', 13, 40, 0, 'nchw', None, (1, 'pipe', 1)),
+    ('f16_cin1', 'fp16', 2, 1, 40, '3x3', 13, 40, 0, 'plain', None, (1, 'pipe', 1)),
+    ('f32_cin1', 'fp32', 2, 1, 40, '3x3', 13, 40, 0, 'plain', None, (4, 'pipe', 1)),
+    ('f16_cin17', 'fp16', 2, 17, 40, '3x3', 13, 40, 0, 'plain', None, (1, 'pipe', 1)),
+    ('f32_cin9', 'fp32', 2, 9, 40, '3x3', 13, 40, 0, 'plain', None, (4, 'pipe', 1)),
     ('f16_exit', 'fp16', 2, 96, 48, '3x3', 13, 40, 0, 'exit', None, (1, 'plain', 1)),
     ('f32_exit', 'fp32', 2, 96, 48, '3x3', 13, 40, 0, 'exit', None, (4, 'plain', 1)),
 ]
@@ -245,6 +274,13 @@ def test_dgrad_cases_reach_every_branch():
     assert {'mask_lrelu', 'mask_relu', 'general1', 'general2', 'exit'} <= epis
     assert {c[1] for c in DG_CASES if c[9] == 'exit'} == {'fp16', 'fp32'}
     assert any(c[10] for c in DG_CASES)
+    # off the recipe, per precision: the input gradient of a forward-cin-1 conv into fp32 NCHW (nchw_out_c = 1) and
+    # into G32, and of a conv whose last input group holds ONE channel
+    for p, cpg in (('fp16', 16), ('fp32', 8)):
+        cs = [c for c in DG_CASES if c[1] == p and c[5] == '3x3']
+        assert any(c[3] == 1 and c[9] == 'nchw' for c in cs), p
+        assert any(c[3] == 1 and c[9] == 'plain' for c in cs), p
+        assert any(c[3] == cpg + 1 for c in cs), p
 
 
 # batched weight gradients: one run of OP_WGRAD ops (B, cin, cout, ks, upsample, H, W, tap_major)
@@ -654,9 +690,13 @@ def test_dgrad_matches_fp64(dev, case):
     extra = cdiv(cin, cpg) * cpg + cpg                                       # one whole group past the view
     out = g32(dev, prec, B, extra, H, W, SENT)
     checks = []                                                              # (buffer, channels, reference)
+    nchw = None
     if epi == 'plain':
         c.out = out.view(0, cin)
         checks.append(('out', out, cin, gx))
+    elif epi == 'nchw':
+        nchw = torch.full((B * cin * H * W + 4096,), SENT, device=dev)
+        c.nchw_out_c, c.nchw_out = cin, nchw.data_ptr()
     elif epi.startswith('mask'):
         act = L.ACT_RELU if epi == 'mask_relu' else L.ACT_LRELU
         m = rnd((B, cin, H, W), 'dg.mask', name)
@@ -734,6 +774,12 @@ def test_dgrad_matches_fp64(dev, case):
         worst = max(worst, e)
         assert e <= TOL_DG[prec], '%s %s: err/scale %.3e' % (name, what, e)
         check_buffer(buf, C_, '%s %s' % (name, what))
+    if nchw is not None:
+        n = B * cin * H * W
+        got = nchw.cpu()
+        worst = rel_err(got[:n].reshape(B, cin, H, W)[idx], gx)
+        assert worst <= TOL_DG[prec], '%s nchw: err/scale %.3e' % (name, worst)
+        assert (got[n:] == SENT).all(), '%s: wrote past nchw_out_c channels' % name
     print('dgrad %s: err/scale %.2e' % (name, worst))
     if epi == 'exit' and prec == 'fp32':
         # the same launch on explicit z2 / z3 holding that z: bit for bit the Philox result, in all three outputs

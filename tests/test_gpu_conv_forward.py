@@ -6,7 +6,8 @@ rounded to fp16, the bias in fp32, and for the sub-pixel up-conv the pre-summed 
 The first section restates the dispatch heuristics and the epilogue routing of csrc/conv_mfma.hip in Python and pins
 which case reaches which branch, so a later change that drops one fails there instead of silently narrowing the test.
 Those pins, and the check of the sub-pixel reference against nearest-x2 + 3x3, run without a GPU.  The GPU sections
-run every branch (ragged maps, a short last tile, cin 3, cout 3, a ragged third cout block, a 1x1-pixel image), every
+run every branch (ragged maps, a short last tile, cin 3, cout 3, a ragged third cout block, a 1x1-pixel image; off
+the recipe: cin 1 and 2, a second input group of one channel, cout 1 and 20, nchw_out_c = 1), every
 epilogue stage alone and combined in the order esrgan_hip.h documents, in-place and in-slice stores, partial views,
 Philox noise against its explicit form, and the refusals.  Every G32 output is pre-filled with a sentinel: the zero
 ring, the rows and columns past the map, the groups past the view and the padding lanes must hold what they held.
@@ -14,7 +15,8 @@ ring, the rows and columns past the map, the groups past the view and the paddin
 Error bounds are relative to the reference's largest magnitude.  fp32: 4e-6, the backward file's gate.  fp16: every
 stage runs in fp32 on exact fp16 operands (an fp16 conv storing fp32 NCHW is within 3e-7), so the error is the
 round-to-nearest of the stored result, at most 2^-11 = 4.9e-4 of the scale, plus fp32 round-off: 6e-4, tighter
-than the backward file's 1.5e-3.  Worst measured on an MI355X: fp32 9.7e-7, fp16 4.5e-4."""
+than the backward file's 1.5e-3.  Worst measured on an MI355X: fp32 9.7e-7, fp16 4.5e-4; on the off-recipe channel
+counts alone fp32 6.0e-7 (cout 20), fp16 3.9e-4 (cout 1)."""
 import numpy as np
 import pytest
 import torch
@@ -106,6 +108,19 @@ BR_CASES = [
     ('f32_ncw2', 'fp32', 16, 32, 256, '3x3', 17, 33, 0, 'lrelu', (4, 'plain', 2)),
     ('f32_cin3', 'fp32', 2, 3, 64, '3x3', 34, 36, 0, 'lrelu', (4, 'plain', 1)),
     ('f32_1px', 'fp32', 3, 32, 40, '3x3', 1, 1, 0, 'lrelu', (4, 'plain', 1)),
+    # off-recipe channel counts: one and two channels in a group, a second group of ONE channel (17 fp16, 9 fp32),
+    # one output channel, 20 output channels (a ragged second fp16 group / third fp32 group)
+    ('f16_cin1', 'fp16', 2, 1, 64, '3x3', 13, 40, 0, 'lrelu', (1, 'plain', 1)),
+    ('f16_cin2', 'fp16', 2, 2, 24, '3x3', 13, 40, 0, 'lrelu', (1, 'pipe', 1)),
+    ('f16_cin17', 'fp16', 2, 17, 40, '3x3', 13, 40, 0, 'lrelu', (1, 'plain', 1)),
+    ('f16_cout1', 'fp16', 2, 32, 1, '3x3', 13, 40, 0, 'lrelu', (1, 'pipe', 1)),
+    ('f16_cout20', 'fp16', 2, 40, 20, '3x3', 13, 40, 0, 'none', (1, 'pipe', 1)),
+    ('f16_cin1_r4', 'fp16', 2, 1, 64, '3x3', 13, 40, 256, 'lrelu', (4, 'plain', 1)),
+    ('f32_cin1', 'fp32', 2, 1, 64, '3x3', 13, 40, 0, 'lrelu', (4, 'plain', 1)),
+    ('f32_cin2', 'fp32', 2, 2, 24, '3x3', 13, 40, 0, 'lrelu', (4, 'pipe', 1)),
+    ('f32_cin9', 'fp32', 2, 9, 40, '3x3', 13, 40, 0, 'lrelu', (4, 'plain', 1)),
+    ('f32_cout1', 'fp32', 2, 32, 1, '3x3', 13, 40, 0, 'lrelu', (4, 'pipe', 1)),
+    ('f32_cout20', 'fp32', 2, 40, 20, '3x3', 13, 40, 0, 'none', (4, 'pipe', 1)),
     ('f16_ups_one', 'fp16', 3, 24, 32, 'ups', 26, 40, 0, 'lrelu', 'one'),
     ('f16_ups_two', 'fp16', 2, 32, 72, 'ups', 18, 70, 0, 'lrelu', 'two'),
     ('f16_ups_1px', 'fp16', 2, 32, 40, 'ups', 2, 2, 0, 'lrelu', 'two'),
@@ -166,6 +181,11 @@ EPI_CASES = [
     ('f16_nchw_out', 'fp16', 2, 32, 40, 13, 40, 0, dict(act='lrelu', nchw=35), 'general'),
     ('f32_nchw_res', 'fp32', 2, 32, 72, 13, 40, 0, dict(act='lrelu', res1=(1.0, None), nchw=20), 'general'),
     ('f16_nchw3_res', 'fp16', 2, 32, 3, 13, 40, 0, dict(act='none', res1=(1.0, None), nchw=3), 'general'),
+    # nchw_out_c = 1 (a single-channel generator's last conv), alone and next to a G32 output
+    ('f16_nchw1', 'fp16', 2, 32, 1, 13, 40, 0, dict(act='lrelu', out=False, nchw=1), 'fast_nchw'),
+    ('f32_nchw1', 'fp32', 2, 32, 1, 13, 40, 0, dict(act='none', out=False, nchw=1), 'fast_nchw'),
+    ('f16_nchw1_out', 'fp16', 2, 32, 1, 13, 40, 0, dict(act='none', nchw=1), 'general'),
+    ('f32_nchw1_out', 'fp32', 2, 32, 1, 13, 40, 0, dict(act='lrelu', nchw=1), 'general'),
 ]
 
 
@@ -215,6 +235,12 @@ def test_forward_cases_reach_every_branch():
         cs = [c for c in BR_CASES if c[1] == p]
         assert any(c[6] % 16 and c[7] % 32 and c[6] > 16 and c[7] > 32 for c in cs), p
         assert any(c[3] == 3 for c in cs) and any(c[4] == 3 for c in cs), p
+        # off the recipe: cin 1 and 2, cout 1 and 20, and a last input group that holds ONE channel, on 3x3 convs
+        cpg = 16 if p == 'fp16' else 8
+        for cin in (1, 2, cpg + 1):
+            assert any(c[3] == cin and c[5] == '3x3' for c in cs), (p, 'cin', cin)
+        for cout in (1, 20):
+            assert any(c[4] == cout and c[5] == '3x3' for c in cs), (p, 'cout', cout)
         assert any(cdiv(c[4], 32) == 3 and c[4] % 32 for c in cs), p
         assert any(c[6] == 1 and c[7] == 1 for c in cs), p
 
@@ -237,6 +263,10 @@ def test_epilogue_cases_route_as_pinned():
     assert any(c[9] == 'general' and c[8].get('nchw') == 3 == c[4] for c in EPI_CASES)
     assert any(c[9] == 'general' and 0 < c[8].get('nchw', 0) < c[4] for c in EPI_CASES)
     assert any(c[9] == 'fast_nchw' and 0 < c[8].get('nchw', 0) < c[4] for c in EPI_CASES)
+    # nchw_out_c = cout = 1 on both paths, in both precisions
+    for p in ('fp16', 'fp32'):
+        for route in ('fast_nchw', 'general'):
+            assert any(c[1] == p and c[9] == route and c[8].get('nchw') == 1 == c[4] for c in EPI_CASES), (p, route)
     # activations with the residual stages
     assert {c[8]['act'] for c in EPI_CASES if 'res1' in c[8] or 'res2' in c[8]} == {'relu', 'lrelu', 'none'}
 

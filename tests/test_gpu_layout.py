@@ -15,7 +15,8 @@ pytestmark = pytest.mark.gpu
 
 U = R.U
 SENTINEL = -77.25               # exact in fp16 and fp32
-SHAPES = [(2, 3, 5, 63), (1, 4, 3, 64), (2, 5, 2, 65), (1, 40, 4, 130)]
+# C = 1 (one lane of a group), 9 and 17 (a second group of ONE channel in fp32 / fp16) next to the recipe's 3
+SHAPES = [(2, 3, 5, 63), (1, 4, 3, 64), (2, 5, 2, 65), (1, 40, 4, 130), (2, 1, 3, 33), (1, 9, 2, 66), (2, 17, 3, 34)]
 MEAN = [float(np.float32(v)) for v in (0.485, 0.456, 0.406, 0.25)]
 INV_STD = [float(np.float32(v)) for v in (1 / 0.229, 1 / 0.224, 1 / 0.225, 3.0)]
 GUARD = 96
