@@ -217,6 +217,8 @@ class RRDB_Net(_RRDBNetBase):
 # =================================================================================================
 # Discriminator_VGG_128 and VGGFeatureExtractor (the rest of the ESRGAN+ train step)
 # =================================================================================================
+import contextlib  # noqa: E402
+
 import torch  # noqa: E402
 
 from . import _lib as L  # noqa: E402
@@ -326,43 +328,41 @@ class _SeqNet(B._PlannedModule):
         E.require_cuda(x, 'input')
         xin = x.detach().contiguous().float()
         dev = xin.device
-        order = E.StreamOrder.of(self) if not need_bwd else None      # inference calls: one at a time per module
-        cur = order.enter() if order else None
-        st = E.current_stream()
-        wp = self._weights(dev)
-        dp = None
-        want_w = dual is not None or self._wants_param_grads()
-        # _per_call_weights (Discriminator_VGG_128_SN): the weights a backward needs are those of ITS forward, and a later
-        # forward rewrites the module's weight buffers (a new power iteration) before that backward runs — such plans own
-        # their input-gradient operands and head weights, snapshotted at forward time
-        own = need_bwd and getattr(self, '_per_call_weights', False)
-        if need_bwd and not own:
-            dp = self._dgrad_weights(dev)
-            dp.ensure(st, force=(bool(self.training) or want_w) and not self.__dict__.get('_weights_clean', False)
-                      and not self._dgrad_fresh())
-        training = bool(self.training) and self._has_bn
-        groups = groups if training else 1
-        plan = self._plan_for(wp, dp, tuple(xin.shape), dev, training=training, need_bwd=need_bwd, want_w=want_w,
-                              groups=groups, bwd_B=bwd_B, dual=dual, own=own)
-        lease = CN._Lease(plan) if need_bwd else None
-        if own:
-            plan.own_dp.ensure(st, force=True)
-            if plan.own_head is not None:
-                with torch.no_grad():
-                    for k, v in self._head().items():
-                        plan.own_head[k].copy_(v)
-        if training:
-            plan.sums_f.zero_()
-        if plan.graph:
-            plan.x_static.copy_(xin)
-            plan.fwd.graph_launch(st)
-        else:
-            plan.fwd.array()[plan.in_op].u.layout.nchw = xin.data_ptr()
-            plan.fwd.run(st)
-        plan.keep_x = xin       # (num_batches_tracked is advanced by the BN finalize launches)
-        y = plan.out_tensor.clone()
-        if order:
-            order.leave(cur)
+        # inference calls: one at a time per module
+        with E.StreamOrder.of(self).call() if not need_bwd else contextlib.nullcontext():
+            st = E.current_stream()
+            wp = self._weights(dev)
+            dp = None
+            want_w = dual is not None or self._wants_param_grads()
+            # _per_call_weights (Discriminator_VGG_128_SN): the weights a backward needs are those of ITS forward, and a
+            # later forward rewrites the module's weight buffers (a new power iteration) before that backward runs — such
+            # plans own their input-gradient operands and head weights, snapshotted at forward time
+            own = need_bwd and getattr(self, '_per_call_weights', False)
+            if need_bwd and not own:
+                dp = self._dgrad_weights(dev)
+                dp.ensure(st, force=(bool(self.training) or want_w) and not self.__dict__.get('_weights_clean', False)
+                          and not self._dgrad_fresh())
+            training = bool(self.training) and self._has_bn
+            groups = groups if training else 1
+            plan = self._plan_for(wp, dp, tuple(xin.shape), dev, training=training, need_bwd=need_bwd, want_w=want_w,
+                                  groups=groups, bwd_B=bwd_B, dual=dual, own=own)
+            lease = CN._Lease(plan) if need_bwd else None
+            if own:
+                plan.own_dp.ensure(st, force=True)
+                if plan.own_head is not None:
+                    with torch.no_grad():
+                        for k, v in self._head().items():
+                            plan.own_head[k].copy_(v)
+            if training:
+                plan.sums_f.zero_()
+            if plan.graph:
+                plan.x_static.copy_(xin)
+                plan.fwd.graph_launch(st)
+            else:
+                plan.fwd.array()[plan.in_op].u.layout.nchw = xin.data_ptr()
+                plan.fwd.run(st)
+            plan.keep_x = xin       # (num_batches_tracked is advanced by the BN finalize launches)
+            y = plan.out_tensor.clone()
         return y, lease
 
     # ---- the dual pair forward in two stages (train step, round 5): ``_pair_begin(b)`` runs the SECOND operand's half

@@ -8,6 +8,7 @@ block.py:260-268 / 287-291) into a recorded list of fused-conv launches over G32
 torch is used here for device memory (buffers are torch tensors) and the stream handle only.
 """
 import collections
+import contextlib
 import ctypes as C
 import os
 
@@ -143,24 +144,6 @@ def _conv(dtype_e, B, H, W, src, src_ch, dst, cw, act=L.ACT_NONE, ks=None, strid
     return c
 
 
-def set_nchw(op, ptr):
-    """Bind the caller's NCHW tensor to an op that reads or writes one: a conv with an NCHW epilogue or a layout op."""
-    if op.kind == L.OP_CONV:
-        op.u.conv.nchw_out = ptr
-    elif op.kind == L.OP_DIHEDRAL:
-        op.u.dihedral.nchw = ptr
-    elif op.kind == L.OP_TILE:
-        op.u.tile.nchw = ptr
-    elif op.kind == L.OP_TILE_X8:
-        op.u.tile_x8.nchw = ptr
-    elif op.kind == L.OP_TILE_MANY:
-        op.u.tile_many.items = ptr       # the images are named by the pass's slice of the device item table
-    elif op.kind == L.OP_TILE_IMG:
-        op.u.tile_img.items = ptr
-    else:
-        op.u.layout.nchw = ptr
-
-
 def upload_table(table, device):
     """A ctypes array as a device tensor (the caller keeps it alive as long as an op points at it)."""
     return torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(device)
@@ -236,6 +219,7 @@ class Plan:
         self.in_op = None        # index of the NCHW->G32 layout op of the input
         self.out_op = None       # index of the op producing the NCHW output
         self.out_shape = None
+        self.ends = None         # the Ends behind in_op / out_op of an RRDBNet plan (bind)
         self.noise_ops = []      # (op index, which) of convs carrying a noise epilogue
         self.chain_ops = []      # indices of OP_RDB_CHAIN ops (noise mode / seed set per run)
         self.chain_ws = None     # workspace of the chain ops (word 1: a bounded spin of the chain kernel timed out)
@@ -244,6 +228,10 @@ class Plan:
         self.wgen = None
         self.chain_noise = False
         self.graph_bound = False   # TrainPlan.enable_graph: the chain ops read their seed from the device
+
+    def bind(self, **values):
+        """Per-run values of the two end ops, by the names of the plan's Ends.per_run."""
+        self.ends.bind(self, **values)
 
     def run(self, x, out, stream, seed=0, zs=None):
         arr = self.ops.array()
@@ -302,73 +290,179 @@ def layout_op(ops, dt_e, B, g, C_, to_g32, nchw=None, affine=None):
     return ops.add(L.OP_LAYOUT, 'layout', lo)
 
 
-def dihedral_op(ops, dt_e, B, C_, H, W, to_g32, k_count, g=None, slots=None):
-    """Self-ensemble end (esr_dihedral) appended to `ops`: the import of k_count transformed copies of B NCHW images of
-    H x W into buffer g, or the reduce of k_count x B outputs — from g or from the fp32 NCHW tensor `slots` — into B
-    NCHW images of H x W.  The range's first k, accumulate and scale are set per pass (X8Plan.run)."""
-    d = L.esr_dihedral()
-    d.dtype, d.to_g32 = dt_e, to_g32
-    d.B, d.C, d.H, d.W = B, C_, H, W
-    if g is not None:
-        d.g32 = g.view(0, C_)
-    if slots is not None:
-        d.slots_nchw = slots.data_ptr()
-    d.k_begin, d.k_count, d.accumulate, d.scale = 0, k_count, 0, 1.0
-    return ops.add(L.OP_DIHEDRAL, 'dihedral', d)
+def _both(*names):
+    return {n: (n, n) for n in names}
 
 
-def tile_op(ops, dt_e, B, C_, to_g32, t_count, g=None, slots=None):
-    """Tiled-inference end (esr_tile) appended to `ops`: the gather of t_count windows of each of B NCHW images into
-    buffer g (its H x W is the window shape), or the stitch of t_count x B window outputs — the fp32 NCHW tensor `slots`
-    — into B NCHW images.  Everything image-sized (H, W, tile, pad, the pass's first tile) is set per run
-    (TiledPlan.run): the op is recorded for the smallest image that has this window."""
-    d = L.esr_tile()
-    d.dtype, d.to_g32, d.scale = dt_e, to_g32, 1 if to_g32 else 4
-    d.B, d.C = B, C_
-    if to_g32:
-        d.g32 = g.view(0, C_)
-        d.H, d.W = g.H, g.W
+class Ends:
+    """The two ends of an RRDBNet inference plan: how the caller's pixels get into the first G32 buffer and how HR_conv1's
+    result reaches the caller.  Everything between them is the same recorded middle (Builder.rrdbnet, Builder.tail), so an
+    inference form is one Ends class, one per kind of op, plus its entry function in functional.py.
+    kind, field: the op kind of the two ends and its member of the esr_op union; ptr: the field that takes the caller's
+    pointer (set_nchw); per_run: the values bind() writes per run, each with the field it goes to on the input op and
+    on the output op (None: not there).
+    This base class is the plain pair: the NCHW -> G32 layout import, and HR_conv1 itself — through its NCHW epilogue —
+    as the output op."""
+
+    kind, field, ptr = L.OP_LAYOUT, 'layout', 'nchw'
+    per_run = {}
+
+    def input_op(self, b, xin, in_nc):
+        """Records the op that fills the in_nc channels of buffer xin of Builder b; returns its index."""
+        return b.import_nchw(xin, in_nc)
+
+    def output(self, b, hr1, out_nc):
+        """Records HR_conv1 (the esr_conv hr1, its output still unset) and what follows it; returns the index of the op
+        that writes the caller's tensor."""
+        return b.plan.ops.add_conv(hr1)
+
+    def end_ops(self, plan):
+        """The structs of the plan's input op and output op, in the array the next run launches."""
+        arr = plan.ops.array()
+        return getattr(arr[plan.in_op].u, self.field), getattr(arr[plan.out_op].u, self.field)
+
+    def bind(self, plan, **values):
+        """Writes the per-run values (names of per_run) into the two end ops of the plan."""
+        g, s = self.end_ops(plan)
+        for name, v in values.items():
+            gf, sf = self.per_run[name]
+            if gf is not None:
+                setattr(g, gf, v)
+            if sf is not None:
+                setattr(s, sf, v)
+
+
+class SlotEnds(Ends):
+    """Ends with an op on either side (fill(): the struct of the input op, to_g32 = 1 into buffer g, or of the output op,
+    to_g32 = 0).  HR_conv1 leaves its fp32 NCHW result (unrounded in either precision, as the ordinary plan's) in a
+    buffer of the plan, slot-major, and the output op moves it from there into the caller's tensor."""
+
+    def input_op(self, b, xin, in_nc):
+        return b.plan.ops.add(self.kind, self.field, self.fill(b, in_nc, 1, g=xin))
+
+    def output(self, b, hr1, out_nc):
+        P = b.plan
+        slots = torch.empty(P.out_shape, dtype=torch.float32, device=b.device)
+        b.bufs.append(slots)
+        hr1.nchw_out = slots.data_ptr()
+        P.ops.add_conv(hr1)
+        return P.ops.add(self.kind, self.field, self.fill(b, out_nc, 0, slots=slots))
+
+    def ends_of(self, d, C_, to_g32, g, slots):
+        """The fields every such struct has: the direction, the channels, and the G32 buffer or the slots tensor."""
+        d.to_g32, d.C = to_g32, C_
+        if to_g32:
+            d.g32 = g.view(0, C_)
+        else:
+            d.slots_nchw = slots.data_ptr()
+        return d
+
+
+class DihedralEnds(SlotEnds):
+    """Self-ensemble ends (esr_dihedral) of a batch of slots x n images: the import of the transformed copies of n NCHW
+    images of H x W, and the reduce that undoes the transforms of the slots x n outputs into n NCHW images of sH x sW.
+    The range's first k, accumulate and scale are set per pass (x8_passes)."""
+
+    kind, field = L.OP_DIHEDRAL, 'dihedral'
+    per_run = dict(_both('k_begin'), accumulate=(None, 'accumulate'), scale=(None, 'scale'))
+
+    def __init__(self, n, H, W):
+        self.n, self.H, self.W = n, H, W
+
+    def fill(self, b, C_, to_g32, g=None, slots=None):
+        d = self.ends_of(L.esr_dihedral(), C_, to_g32, g, slots)
+        s = 1 if to_g32 else b.scale
+        d.dtype, d.B, d.H, d.W = b.dt_e, self.n, s * self.H, s * self.W
+        d.k_begin, d.k_count, d.accumulate, d.scale = 0, b.B // self.n, 0, 1.0
+        return d
+
+    def output(self, b, hr1, out_nc):
+        i = super().output(b, hr1, out_nc)
+        b.plan.out_shape = (self.n, out_nc, b.scale * self.H, b.scale * self.W)
+        return i
+
+
+class TileEnds(SlotEnds):
+    """Tiled-inference ends (esr_tile) of a batch of windows x n images, the builder's H x W the window: the gather of
+    t_count windows of each of n NCHW images, and the stitch that copies every tile's owned rectangle out of the
+    t_count x n window outputs into n NCHW images.  Everything image-sized (H, W, tile, pad) and the pass's first tile
+    are set per run (bind_image, tile_passes): the ops are recorded for the smallest image that has this window."""
+
+    kind, field, struct = L.OP_TILE, 'tile', L.esr_tile
+    per_run = dict(_both('tile', 'pad', 't_begin'), H=('H', None), W=('W', None), HR_H=(None, 'H'), HR_W=(None, 'W'))
+
+    def __init__(self, n):
+        self.n = n
+
+    def window(self, b):
+        """(th, tw, windows per image) of the batch."""
+        return b.H, b.W, b.B // self.n
+
+    def fill(self, b, C_, to_g32, g=None, slots=None):
+        d = self.ends_of(self.struct(), C_, to_g32, g, slots)
+        th, tw, t_count = self.window(b)
+        d.dtype, d.B, d.scale = b.dt_e, self.n, 1 if to_g32 else 4
+        d.H, d.W = th * d.scale, tw * d.scale
+        d.tile, d.pad, d.t_begin, d.t_count = max(th, tw), 0, 0, t_count
+        return d
+
+
+class TileX8Ends(TileEnds):
+    """Tiled self-ensemble ends (esr_tile_x8) of a batch of slots x windows x n images: the gather-import of the
+    transforms [k0, k0 + slots) of the th x tw windows (th x tw on the NCHW side: the builder's H x W is tw x th for the
+    transposed slots, k0 = 4), and the stitch-reduce that undoes the transforms, sums and copies every tile's owned
+    rectangle into the caller's tensor.  TileEnds' per-run values and the pass's k range, accumulate and mean scale."""
+
+    kind, field, struct = L.OP_TILE_X8, 'tile_x8', L.esr_tile_x8
+    per_run = dict(TileEnds.per_run, **_both('k_begin'), accumulate=(None, 'accumulate'), scale=(None, 'mean_scale'))
+
+    def __init__(self, n, th, tw, k0, slots):
+        self.n, self.th, self.tw, self.k0, self.slots = n, th, tw, k0, slots
+
+    def window(self, b):
+        return self.th, self.tw, b.B // (self.slots * self.n)
+
+    def fill(self, b, C_, to_g32, g=None, slots=None):
+        d = super().fill(b, C_, to_g32, g, slots)
+        d.k_begin, d.k_count, d.accumulate, d.mean_scale = self.k0, self.slots, 0, 1.0
+        return d
+
+
+class TileManyEnds(SlotEnds):
+    """Image-set tiled ends (esr_tile_many) of a batch of windows, the builder's H x W each: the gather of every slot's
+    window from an image of its own, and the stitch of every slot's owned rectangle into the image its table entry
+    names.  The images are named by the pass's slice of the device item table (ptr = items); tile and pad are set per
+    run."""
+
+    kind, field, ptr, struct = L.OP_TILE_MANY, 'tile_many', 'items', L.esr_tile_many
+    per_run = _both('tile', 'pad')
+
+    def fill(self, b, C_, to_g32, g=None, slots=None):
+        d = self.ends_of(self.struct(), C_, to_g32, g, slots)
+        d.dtype, d.scale = b.dt_e, 1 if to_g32 else 4
+        d.th, d.tw, d.n_slots = b.H, b.W, b.B
+        d.tile, d.pad = max(b.H, b.W), 0
+        return d
+
+
+class TileImgEnds(TileManyEnds):
+    """TileManyEnds with 8-bit HWC images outside (esr_tile_img: the same fields and bgr, set per run too); the stitch
+    quantises the fp32 slots buffer."""
+
+    kind, field, struct = L.OP_TILE_IMG, 'tile_img', L.esr_tile_img
+    per_run = _both('tile', 'pad', 'bgr')
+
+
+ENDS_OF_KIND = {e.kind: e for e in (Ends, DihedralEnds, TileEnds, TileX8Ends, TileManyEnds, TileImgEnds)}
+
+
+def set_nchw(op, ptr):
+    """Bind the caller's tensor to an op that reads or writes one: a conv with an NCHW epilogue, or one of the end ops."""
+    if op.kind == L.OP_CONV:
+        op.u.conv.nchw_out = ptr
     else:
-        d.slots_nchw = slots.data_ptr()
-        d.H, d.W = slots.shape[2], slots.shape[3]
-    d.tile, d.pad, d.t_begin, d.t_count = max(d.H, d.W) // d.scale, 0, 0, t_count
-    return ops.add(L.OP_TILE, 'tile', d)
-
-
-def tile_x8_op(ops, dt_e, B, C_, th, tw, to_g32, t_count, k_begin, k_count, g=None, slots=None):
-    """Tiled self-ensemble end (esr_tile_x8) appended to `ops`: the gather-import of k_count transformed copies of t_count
-    th x tw windows of each of B NCHW images into buffer g, or the stitch-reduce of k_count x t_count x B window outputs
-    — the fp32 NCHW tensor `slots` — into B NCHW images.  Everything image-sized (H, W, tile, pad, the pass's first tile)
-    and the pass's k range, accumulate and mean_scale are set per run (TiledX8Plan.run): the op is recorded for the
-    smallest image that has this window."""
-    d = L.esr_tile_x8()
-    d.dtype, d.to_g32, d.scale = dt_e, to_g32, 1 if to_g32 else 4
-    d.B, d.C, d.H, d.W = B, C_, th * d.scale, tw * d.scale
-    if to_g32:
-        d.g32 = g.view(0, C_)
-    else:
-        d.slots_nchw = slots.data_ptr()
-    d.tile, d.pad, d.t_begin, d.t_count = max(th, tw), 0, 0, t_count
-    d.k_begin, d.k_count, d.accumulate, d.mean_scale = k_begin, k_count, 0, 1.0
-    return ops.add(L.OP_TILE_X8, 'tile_x8', d)
-
-
-def tile_many_op(ops, dt_e, C_, th, tw, to_g32, n_slots, g=None, slots=None, img=False):
-    """Image-set tiled end (esr_tile_many) appended to `ops`: the gather of n_slots th x tw windows, each of an image of
-    its own, into buffer g, or the stitch of n_slots window outputs — the fp32 NCHW tensor `slots` — each into its own
-    image.  tile, pad and the pass's slice of the device item table are set per run (TiledManyPlan.run).  img: the end
-    with 8-bit HWC images outside (esr_tile_img: the same fields and bgr, which TiledImgPlan.run sets too)."""
-    d = L.esr_tile_img() if img else L.esr_tile_many()
-    d.dtype, d.to_g32, d.scale = dt_e, to_g32, 1 if to_g32 else 4
-    d.C, d.th, d.tw, d.n_slots = C_, th, tw, n_slots
-    if to_g32:
-        d.g32 = g.view(0, C_)
-    else:
-        d.slots_nchw = slots.data_ptr()
-    d.tile, d.pad = max(th, tw), 0
-    if img:
-        return ops.add(L.OP_TILE_IMG, 'tile_img', d)
-    return ops.add(L.OP_TILE_MANY, 'tile_many', d)
+        e = ENDS_OF_KIND[op.kind]
+        setattr(getattr(op.u, e.field), e.ptr, ptr)
 
 
 class Builder:
@@ -376,8 +470,7 @@ class Builder:
 
     image_limit = False           # G32's per-image offset bound (TrainBuilder: the weight-gradient kernels)
 
-    def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1, x8=None, tiled=None, tiled_x8=None,
-                 scale=4, tiled_many=None, tiled_img=None):
+    def __init__(self, wp, B, H, W, dtype, device, noise, variant, kind='net', nb=1, scale=4, ends=None):
         self.wp = wp
         self.scale = scale            # upscale of the generator: 1, 2, 4, 8 = 0..3 nearest-x2 up-convs, 3 = one folded x3
         self.B, self.H, self.W = B, H, W
@@ -392,15 +485,7 @@ class Builder:
         self.plan = Plan()
         self.bufs = self.plan.bufs    # everything the ops point at stays alive with the plan
         self.zbufs = []
-        self.x8 = x8                  # (images, H, W of the NCHW input): the batch is slots x images of a self-ensemble
-        self.tiled = tiled            # images: the batch is windows x images of a tiled forward, H x W the window
-        # (images, th, tw, first k, slots): the batch is slots x windows x images of a tiled self-ensemble, th x tw the
-        # window on the NCHW side (H x W here is tw x th for the transposed slots, first k = 4)
-        self.tiled_x8 = tiled_x8
-        self.tiled_many = tiled_many  # slots: the batch is the windows, H x W each, of any images of a tiled forward
-        if tiled_img is not None:     # slots: tiled_many's plan with 8-bit HWC images at both ends (esr_tile_img)
-            self.tiled_many = tiled_img
-        self.tiled_img = tiled_img is not None
+        self.ends = ends or Ends()    # the two ends of rrdbnet(); B x H x W is the batch between them
 
     def buf(self, C_, H=None, W=None):
         return new_buf(self.bufs, self.B, C_, H or self.H, W or self.W, self.dtype, self.device, self.image_limit)
@@ -636,43 +721,7 @@ class Builder:
         c = _conv(d, B, h, w, u3.view(0), 64, None, e[hr1])
         c.nchw_out_c = out_nc
         P.out_shape = (B, out_nc, s * H, s * W)
-        if self.tiled_x8 is not None:
-            # tiled self-ensemble: HR_conv1 leaves the transformed windows' fp32 NCHW outputs in a buffer of the plan, and
-            # the stitch-reduce undoes the transforms, sums and copies every tile's owned rectangle into the caller's tensor
-            n, wh, ww, k0, kc = self.tiled_x8
-            slots = torch.empty(P.out_shape, dtype=torch.float32, device=self.device)
-            self.bufs.append(slots)
-            c.nchw_out = slots.data_ptr()
-            P.ops.add_conv(c)
-            P.out_op = tile_x8_op(P.ops, d, n, out_nc, wh, ww, 0, B // (kc * n), k0, kc, slots=slots)
-        elif self.tiled_many is not None:
-            # tiled forward over an image set: as the tiled forward below, but every slot's owned rectangle goes into the
-            # image its table entry names
-            slots = torch.empty(P.out_shape, dtype=torch.float32, device=self.device)
-            self.bufs.append(slots)
-            c.nchw_out = slots.data_ptr()
-            P.ops.add_conv(c)
-            P.out_op = tile_many_op(P.ops, d, out_nc, H, W, 0, B, slots=slots, img=self.tiled_img)
-        elif self.tiled is not None:
-            # tiled forward: HR_conv1 leaves the windows' fp32 NCHW outputs in a buffer of the plan, slot-major, and the
-            # stitch copies every tile's owned rectangle into the caller's tensor
-            slots = torch.empty(P.out_shape, dtype=torch.float32, device=self.device)
-            self.bufs.append(slots)
-            c.nchw_out = slots.data_ptr()
-            P.ops.add_conv(c)
-            P.out_op = tile_op(P.ops, d, self.tiled, out_nc, 0, B // self.tiled, slots=slots)
-        elif self.x8 is None:
-            P.out_op = P.ops.add_conv(c)
-        else:
-            # self-ensemble: HR_conv1 leaves its fp32 NCHW result (unrounded in either precision, as the ordinary plan's)
-            # in a buffer of the plan, slot-major, and the reduce undoes the transforms into the caller's tensor
-            n, xh, xw = self.x8
-            slots = torch.empty(P.out_shape, dtype=torch.float32, device=self.device)
-            self.bufs.append(slots)
-            c.nchw_out = slots.data_ptr()
-            P.ops.add_conv(c)
-            P.out_op = dihedral_op(P.ops, d, n, out_nc, s * xh, s * xw, 0, B // n, slots=slots)
-            P.out_shape = (n, out_nc, s * xh, s * xw)
+        P.out_op = self.ends.output(self, c, out_nc)
         return t, us, u3
 
     def rrdbnet(self, in_nc, out_nc, explicit_z):
@@ -683,18 +732,8 @@ class Builder:
         self.alloc_z(explicit_z)
         xin = self.buf(in_nc)
         fea = self.buf(64)
-        if self.tiled_x8 is not None:
-            n, wh, ww, k0, kc = self.tiled_x8
-            P.in_op = tile_x8_op(P.ops, self.dt_e, n, in_nc, wh, ww, 1, B // (kc * n), k0, kc, g=xin)
-        elif self.tiled_many is not None:
-            P.in_op = tile_many_op(P.ops, self.dt_e, in_nc, H, W, 1, B, g=xin, img=self.tiled_img)
-        elif self.tiled is not None:
-            P.in_op = tile_op(P.ops, self.dt_e, self.tiled, in_nc, 1, B // self.tiled, g=xin)
-        elif self.x8 is None:
-            P.in_op = self.import_nchw(xin, in_nc)
-        else:
-            n, xh, xw = self.x8
-            P.in_op = dihedral_op(P.ops, self.dt_e, n, in_nc, xh, xw, 1, B // n, g=xin)
+        P.ends = self.ends
+        P.in_op = self.ends.input_op(self, xin, in_nc)
         if nb and rdb_chain_ok(B, H, W, self.noise, explicit_z):
             # fused trunk: two 64-channel slots + the chain's 128-channel dense scratch
             xa, xb = self.buf(64), self.buf(64)
@@ -826,9 +865,10 @@ def concurrent_streams(device, n):
 class StreamOrder:
     """A module's launch plans own their activation buffers, packed weights and chain workspaces, so two inference
     calls of ONE module from two streams must not overlap (torch modules are stateless in that respect; a second
-    stream is how users overlap independent work).  enter() makes the calling stream wait — on the device — for the
-    module's previous call when that ran on another stream; leave() marks the end of this call.  Skipped under
-    graph capture (the graph's order applies)."""
+    stream is how users overlap independent work).  ``with StreamOrder.of(mod).call():`` makes the calling stream wait —
+    on the device — for the module's previous call when that ran on another stream, and marks the end of this call on
+    the way out, also when the call raises: part of its launches may be queued by then.  Skipped under graph capture
+    (the graph's order applies)."""
 
     def __init__(self):
         self.last = None
@@ -841,21 +881,19 @@ class StreamOrder:
             so = mod.__dict__['_stream_order'] = StreamOrder()
         return so
 
-    def enter(self):
+    @contextlib.contextmanager
+    def call(self):
         cur = torch.cuda.current_stream()
-        if torch.cuda.is_current_stream_capturing():
-            return cur
-        if self.last is not None and self.last != cur.cuda_stream:
+        if not torch.cuda.is_current_stream_capturing() and self.last is not None and self.last != cur.cuda_stream:
             cur.wait_event(self.event)
-        return cur
-
-    def leave(self, cur):
-        if torch.cuda.is_current_stream_capturing():
-            return
-        if self.event is None:
-            self.event = torch.cuda.Event()
-        self.event.record(cur)
-        self.last = cur.cuda_stream
+        try:
+            yield cur
+        finally:
+            if not torch.cuda.is_current_stream_capturing():
+                if self.event is None:
+                    self.event = torch.cuda.Event()
+                self.event.record(cur)
+                self.last = cur.cuda_stream
 
 
 def env_int(name, default, lo, hi):
@@ -910,8 +948,12 @@ def build_block_plan(kind, wp, B, H, W, dtype, device, noise, variant, explicit_
     return Builder(wp, B, H, W, dtype, device, noise, variant, kind).block_plan(explicit_z)
 
 
-def build_rrdbnet_plan(wp, nb, in_nc, out_nc, B, H, W, dtype, device, noise, variant, explicit_z, scale=4):
-    return Builder(wp, B, H, W, dtype, device, noise, variant, 'net', nb, scale=scale).rrdbnet(in_nc, out_nc, explicit_z)
+def build_rrdbnet_plan(wp, nb, in_nc, out_nc, B, H, W, dtype, device, noise, variant, explicit_z, scale=4, ends=None):
+    """The plan of RRDBNet over a batch of B x H x W between `ends` (default: the plain NCHW pair).  Every other form
+    below is this plan in eval mode, at the batch its ends make of the caller's images: the ops between the two ends
+    are those of the ordinary plan of that batch shape."""
+    b = Builder(wp, B, H, W, dtype, device, noise, variant, 'net', nb, scale=scale, ends=ends)
+    return b.rrdbnet(in_nc, out_nc, explicit_z)
 
 
 X8_SLOTS = (8, 4, 2, 1)
@@ -926,35 +968,44 @@ def x8_slots(H, W, slots_per_pass=None):
     return min(n, 4) if H != W else n
 
 
+def x8_passes(slots):
+    """The 8 / slots passes of a self-ensemble, [(first k, index of the plan, accumulate, scale)]: the first plan runs
+    k 0..3 and the last one k 4..7 (the transposed shape where there are two), the passes are chained through the
+    output op's accumulate from the second on, and the last applies the 1/8."""
+    return [(k0, -1 if k0 >= 4 else 0, int(k0 > 0), 0.125 if k0 + slots == 8 else 1.0) for k0 in range(0, 8, slots)]
+
+
+def tile_passes(n_tiles, P):
+    """First tiles of the passes of P tiles over an image of n_tiles.  A tail pass is as large as the others: the gather
+    repeats the last tile, the stitch skips it."""
+    return range(0, n_tiles, P)
+
+
+def bind_image(plans, x, tile, pad, P):
+    """What a tiled run of the images x sets once per call on the two ends of its plans — H, W on the gather, 4H, 4W on
+    the stitch, tile and pad on both — -> its tile_passes."""
+    H, W = x.shape[2], x.shape[3]
+    for plan in plans:
+        plan.bind(H=H, W=W, HR_H=4 * H, HR_W=4 * W, tile=tile, pad=pad)
+    return tile_passes(-(-H // tile) * -(-W // tile), P)
+
+
 class X8Plan:
-    """The x8 self-ensemble of one (batch, shape, precision): 8 / slots passes over one inference plan of batch
-    slots x B (two plans for non-square input: H x W for k 0..3, W x H for k 4..7), chained through the reduce op's
-    `accumulate`; the last pass applies the 1/8."""
+    """The x8 self-ensemble of one (batch, shape, precision): x8_passes over one inference plan of batch slots x B (two
+    plans for non-square input: H x W for k 0..3, W x H for k 4..7) between DihedralEnds."""
 
     def __init__(self, plans, slots, out_shape):
         self.plans, self.slots, self.out_shape = plans, slots, out_shape
 
-    def bind_pass(self, k0):
-        """The plan of the pass that starts at slot k0, its two dihedral ops set to that range."""
-        plan = self.plans[-1 if k0 >= 4 else 0]
-        arr = plan.ops.array()
-        arr[plan.in_op].u.dihedral.k_begin = k0
-        r = arr[plan.out_op].u.dihedral
-        r.k_begin, r.accumulate, r.scale = k0, int(k0 > 0), 0.125 if k0 + self.slots == 8 else 1.0
-        return plan
-
     def run(self, x, out, stream):
-        for k0 in range(0, 8, self.slots):
-            self.bind_pass(k0).run(x, out, stream)
+        for k0, i, accumulate, scale in x8_passes(self.slots):
+            self.plans[i].bind(k_begin=k0, accumulate=accumulate, scale=scale)
+            self.plans[i].run(x, out, stream)
 
 
 def build_rrdbnet_x8_plan(wp, nb, in_nc, out_nc, B, H, W, dtype, device, variant, slots, scale=4):
-    """Self-ensemble form of build_rrdbnet_plan (eval mode): the dihedral import in place of the NCHW import, the
-    dihedral reduce behind HR_conv1, and between them the ops of the ordinary plan of batch slots x B."""
-    plans = []
-    for sh, sw in ([(H, W)] if H == W else [(H, W), (W, H)]):
-        b = Builder(wp, slots * B, sh, sw, dtype, device, False, variant, 'net', nb, x8=(B, H, W), scale=scale)
-        plans.append(b.rrdbnet(in_nc, out_nc, False))
+    plans = [build_rrdbnet_plan(wp, nb, in_nc, out_nc, slots * B, sh, sw, dtype, device, False, variant, False, scale,
+                                DihedralEnds(B, H, W)) for sh, sw in ([(H, W)] if H == W else [(H, W), (W, H)])]
     return X8Plan(plans, slots, (B, out_nc, scale * H, scale * W))
 
 
@@ -974,115 +1025,64 @@ def tiled_geometry(H, W, tile, pad):
 
 class TiledPlan:
     """The tiled forward of every image whose windows are th x tw, in passes of P windows per image: one inference plan
-    of batch P x B at th x tw between a gather and a stitch (esr_tile).  Nothing in it depends on the image size."""
+    of batch P x B at th x tw between TileEnds.  Nothing in it depends on the image size."""
 
     def __init__(self, plan, P):
         self.plan, self.P = plan, P
 
     def run(self, x, out, tile, pad, stream):
-        H, W = x.shape[2], x.shape[3]
-        ny, nx = -(-H // tile), -(-W // tile)
-        plan = self.plan
-        arr = plan.ops.array()
-        g, s = arr[plan.in_op].u.tile, arr[plan.out_op].u.tile
-        g.H, g.W, s.H, s.W = H, W, 4 * H, 4 * W
-        g.tile = s.tile = tile
-        g.pad = s.pad = pad
-        for t0 in range(0, ny * nx, self.P):
-            g.t_begin = s.t_begin = t0           # a tail pass: the gather repeats the last tile, the stitch skips it
-            plan.run(x, out, stream)
+        for t0 in bind_image([self.plan], x, tile, pad, self.P):
+            self.plan.bind(t_begin=t0)
+            self.plan.run(x, out, stream)
 
 
 def build_rrdbnet_tiled_plan(wp, nb, in_nc, out_nc, B, th, tw, dtype, device, variant, P):
-    """Tiled form of build_rrdbnet_plan (eval mode): the gather in place of the NCHW import, the stitch behind HR_conv1,
-    and between them the ops of the ordinary plan of batch P x B at the window shape th x tw."""
-    b = Builder(wp, P * B, th, tw, dtype, device, False, variant, 'net', nb, tiled=B)
-    return TiledPlan(b.rrdbnet(in_nc, out_nc, False), P)
+    return TiledPlan(build_rrdbnet_plan(wp, nb, in_nc, out_nc, P * B, th, tw, dtype, device, False, variant, False,
+                                        ends=TileEnds(B)), P)
 
 
 class TiledManyPlan:
     """The tiled forward of S windows of th x tw per pass, whichever images they belong to: one inference plan of batch S
-    at th x tw between a table-driven gather and stitch (esr_tile_many).  Nothing in it depends on an image."""
+    at th x tw between TileManyEnds — or TileImgEnds, the same plan with 8-bit images outside and one more bound value,
+    bgr.  Nothing in it depends on an image or a channel order."""
 
     def __init__(self, plan, S):
         self.plan, self.S = plan, S
 
-    def run(self, gather_items, stitch_items, tile, pad, stream):
-        """One pass: the two uint8 device tensors hold the pass's S esr_tile_item entries (LR images / HR results)."""
-        plan = self.plan
-        arr = plan.ops.array()
-        g, s = arr[plan.in_op].u.tile_many, arr[plan.out_op].u.tile_many
-        g.tile = s.tile = tile
-        g.pad = s.pad = pad
-        plan.run(gather_items, stitch_items, stream)
+    def bind(self, **bound):
+        """tile and pad (and bgr) of the passes that follow."""
+        self.plan.bind(**bound)
+
+    def run(self, gather_items, stitch_items, stream):
+        """One pass: the two uint8 device tensors hold the pass's S item entries (esr_tile_item / esr_tile_img_item: LR
+        images / HR results)."""
+        self.plan.run(gather_items, stitch_items, stream)
 
 
-def build_rrdbnet_tiled_many_plan(wp, nb, in_nc, out_nc, S, th, tw, dtype, device, variant):
-    """Image-set form of build_rrdbnet_tiled_plan (eval mode): the ordinary plan of batch S at the window shape th x tw
-    between the table-driven gather and stitch."""
-    b = Builder(wp, S, th, tw, dtype, device, False, variant, 'net', nb, tiled_many=S)
-    return TiledManyPlan(b.rrdbnet(in_nc, out_nc, False), S)
-
-
-class TiledImgPlan(TiledManyPlan):
-    """TiledManyPlan with 8-bit ends: the same inference plan of batch S at th x tw between the gather that reads uint8
-    HWC images and the stitch that writes them (esr_tile_img).  Nothing in it depends on an image or a channel order."""
-
-    def run(self, gather_items, stitch_items, tile, pad, bgr, stream):
-        """One pass: the two uint8 device tensors hold the pass's S esr_tile_img_item entries (LR images / HR results)."""
-        plan = self.plan
-        arr = plan.ops.array()
-        g, s = arr[plan.in_op].u.tile_img, arr[plan.out_op].u.tile_img
-        g.tile = s.tile = tile
-        g.pad = s.pad = pad
-        g.bgr = s.bgr = 1 if bgr else 0
-        plan.run(gather_items, stitch_items, stream)
-
-
-def build_rrdbnet_tiled_img_plan(wp, nb, in_nc, out_nc, S, th, tw, dtype, device, variant):
-    """build_rrdbnet_tiled_many_plan with 8-bit ends (eval mode): the ordinary plan of batch S at the window shape th x tw
-    between esr_tile_img's gather and stitch; HR_conv1 writes the fp32 slots buffer the stitch quantises."""
-    b = Builder(wp, S, th, tw, dtype, device, False, variant, 'net', nb, tiled_img=S)
-    return TiledImgPlan(b.rrdbnet(in_nc, out_nc, False), S)
+def build_rrdbnet_tiled_many_plan(wp, nb, in_nc, out_nc, S, th, tw, dtype, device, variant, ends=TileManyEnds):
+    return TiledManyPlan(build_rrdbnet_plan(wp, nb, in_nc, out_nc, S, th, tw, dtype, device, False, variant, False,
+                                            ends=ends()), S)
 
 
 class TiledX8Plan:
-    """The tiled x8 self-ensemble of every image whose windows are th x tw: per pass of P windows per image, 8 / slots
-    runs of one inference plan of batch slots x P x B (two plans for non-square windows: th x tw for k 0..3, tw x th for
-    k 4..7) between a gather-import and a stitch-reduce (esr_tile_x8), chained through `accumulate` into the caller's
-    tensor; the last run of a pass applies the 1/8.  Nothing in it depends on the image size."""
+    """The tiled x8 self-ensemble of every image whose windows are th x tw: per pass of P windows per image, the
+    x8_passes of one inference plan of batch slots x P x B (two plans for non-square windows: th x tw for k 0..3, tw x th
+    for k 4..7) between TileX8Ends, chained into the caller's tensor.  Nothing in it depends on the image size."""
 
     def __init__(self, plans, slots, P):
         self.plans, self.slots, self.P = plans, slots, P
 
     def run(self, x, out, tile, pad, stream):
-        H, W = x.shape[2], x.shape[3]
-        ny, nx = -(-H // tile), -(-W // tile)
-        for plan in self.plans:
-            arr = plan.ops.array()
-            g, s = arr[plan.in_op].u.tile_x8, arr[plan.out_op].u.tile_x8
-            g.H, g.W, s.H, s.W = H, W, 4 * H, 4 * W
-            g.tile = s.tile = tile
-            g.pad = s.pad = pad
-        for t0 in range(0, ny * nx, self.P):
-            for k0 in range(0, 8, self.slots):
-                plan = self.plans[-1 if k0 >= 4 else 0]
-                arr = plan.ops.array()
-                g, s = arr[plan.in_op].u.tile_x8, arr[plan.out_op].u.tile_x8
-                g.t_begin = s.t_begin = t0       # a tail pass: the gather repeats the last tile, the stitch skips it
-                g.k_begin = s.k_begin = k0
-                s.accumulate, s.mean_scale = int(k0 > 0), 0.125 if k0 + self.slots == 8 else 1.0
-                plan.run(x, out, stream)
+        for t0 in bind_image(self.plans, x, tile, pad, self.P):
+            for k0, i, accumulate, scale in x8_passes(self.slots):
+                self.plans[i].bind(t_begin=t0, k_begin=k0, accumulate=accumulate, scale=scale)
+                self.plans[i].run(x, out, stream)
 
 
 def build_rrdbnet_tiled_x8_plan(wp, nb, in_nc, out_nc, B, th, tw, dtype, device, variant, P, slots):
-    """Tiled self-ensemble form of build_rrdbnet_plan (eval mode): the gather-import in place of the NCHW import, the
-    stitch-reduce behind HR_conv1, and between them the ops of the ordinary plan of batch slots x P x B at the window
-    shape (and, for non-square windows, a second one at the transposed shape)."""
-    plans = []
-    for k0, sh, sw in ([(0, th, tw)] if th == tw else [(0, th, tw), (4, tw, th)]):
-        b = Builder(wp, slots * P * B, sh, sw, dtype, device, False, variant, 'net', nb, tiled_x8=(B, th, tw, k0, slots))
-        plans.append(b.rrdbnet(in_nc, out_nc, False))
+    plans = [build_rrdbnet_plan(wp, nb, in_nc, out_nc, slots * P * B, sh, sw, dtype, device, False, variant, False,
+                                ends=TileX8Ends(B, th, tw, k0, slots))
+             for k0, sh, sw in ([(0, th, tw)] if th == tw else [(0, th, tw), (4, tw, th)])]
     return TiledX8Plan(plans, slots, P)
 
 

@@ -71,22 +71,20 @@ def run_block(mod, kind, x, z=None):
     B, C_, H, W = xin.shape
     if C_ != 64:
         raise ValueError('expected 64 input channels, got %d' % C_)
-    order = E.StreamOrder.of(mod)
-    cur = order.enter()
-    wp = mod._weights(xin.device)
-    has_noise = getattr(mod, 'noise', None) is not None if kind == 'rdb' else True
-    noise = bool(mod.training and has_noise)
-    n_noise = E.NoiseLayers(mod.variant, kind, 1, noise).total
-    zs = _zs_list(z, n_noise, (B, 64, H, W), xin.device) if noise else None
-    key = (kind, B, H, W, mod.precision, noise, zs is not None, wp.generation)
-    plan = mod._plans.get(key)
-    if plan is None:
-        plan = E.build_block_plan(kind, wp, B, H, W, mod.precision, xin.device, noise,
-                                  mod.variant, zs is not None)
-        mod._plans = {key: plan}
-    out = torch.empty(plan.out_shape, dtype=torch.float32, device=xin.device)
-    plan.run(xin, out, E.current_stream(), _draw_seed() if (noise and zs is None) else 0, zs)
-    order.leave(cur)
+    with E.StreamOrder.of(mod).call():
+        wp = mod._weights(xin.device)
+        has_noise = getattr(mod, 'noise', None) is not None if kind == 'rdb' else True
+        noise = bool(mod.training and has_noise)
+        n_noise = E.NoiseLayers(mod.variant, kind, 1, noise).total
+        zs = _zs_list(z, n_noise, (B, 64, H, W), xin.device) if noise else None
+        key = (kind, B, H, W, mod.precision, noise, zs is not None, wp.generation)
+        plan = mod._plans.get(key)
+        if plan is None:
+            plan = E.build_block_plan(kind, wp, B, H, W, mod.precision, xin.device, noise,
+                                      mod.variant, zs is not None)
+            mod._plans = {key: plan}
+        out = torch.empty(plan.out_shape, dtype=torch.float32, device=xin.device)
+        plan.run(xin, out, E.current_stream(), _draw_seed() if (noise and zs is None) else 0, zs)
     return out
 
 
@@ -430,12 +428,32 @@ def _flat_grad_route(net, params):
     return bool(net.flat_param_grads) and all(p.requires_grad and p.is_leaf for p in params)
 
 
+def _cached_plan(mod, key, build):
+    """``mod._plans[key]``, built by ``build()`` on first use.  A full cache is emptied before the build, so that the old
+    plans' buffers are free when the new one allocates its own."""
+    plan = mod._plans.get(key)
+    if plan is None:
+        if len(mod._plans) >= mod.max_cached_plans:
+            mod._plans.clear()
+        plan = mod._plans[key] = build()
+    return plan
+
+
+def _eval_front(net, x, s):
+    """The front of an eval entry of RRDBNet at upscale s -> (xin, None), the checked fp32 NCHW input, or (None, the
+    result of an empty batch: torch returns an empty result)."""
+    if x.dim() == 4 and x.shape[0] == 0:
+        E.require_cuda(x, 'input')
+        return None, x.new_zeros((0, net.out_nc, s * x.shape[2], s * x.shape[3]), dtype=torch.float32)
+    xin = _prep_input(x, 'input')
+    if xin.shape[1] != net.in_nc:
+        raise ValueError('expected %d input channels, got %d' % (net.in_nc, xin.shape[1]))
+    return xin, None
+
+
 def run_rrdbnet(net, x, z=None):
     """RRDBNet.forward (architecture.py:76-78) on the HIP path."""
-    if x.dim() == 4 and x.shape[0] == 0:          # empty batch: torch returns an empty result
-        E.require_cuda(x, 'input')
-        return x.new_zeros((0, net.out_nc, net.upscale * x.shape[2], net.upscale * x.shape[3]), dtype=torch.float32)
-    if _needs_grad(net, x):
+    if not (x.dim() == 4 and x.shape[0] == 0) and _needs_grad(net, x):
         E.require_cuda(x, 'input')
         B, C_, H, W = x.shape
         if C_ != net.in_nc:
@@ -452,26 +470,20 @@ def run_rrdbnet(net, x, z=None):
             return _RRDBNetFn.apply(x, net, zs, proxy)
         net._flush_stale_grads()
         return _RRDBNetFn.apply(x, net, zs, None, *params)
-    xin = _prep_input(x, 'input')
-    B, C_, H, W = xin.shape
-    if C_ != net.in_nc:
-        raise ValueError('expected %d input channels, got %d' % (net.in_nc, C_))
-    order = E.StreamOrder.of(net)
-    cur = order.enter()
-    wp = net._weights(xin.device)
-    noise = bool(net.training)
-    zs = _zs_list(z, E.NoiseLayers(net.variant, 'net', net.nb).total, (B, 64, H, W), xin.device) if noise else None
-    key = (B, H, W, net.precision, noise, zs is not None, wp.generation)
-    plan = net._plans.get(key)
-    if plan is None:
-        if len(net._plans) >= net.max_cached_plans:
-            net._plans.clear()
-        plan = E.build_rrdbnet_plan(wp, net.nb, net.in_nc, net.out_nc, B, H, W, net.precision,
-                                    xin.device, noise, net.variant, zs is not None, scale=net.upscale)
-        net._plans[key] = plan
-    out = torch.empty(plan.out_shape, dtype=torch.float32, device=xin.device)
-    plan.run(xin, out, E.current_stream(), _draw_seed() if (noise and zs is None) else 0, zs)
-    order.leave(cur)
+    xin, empty = _eval_front(net, x, net.upscale)
+    if xin is None:
+        return empty
+    B, _, H, W = xin.shape
+    dev = xin.device
+    with E.StreamOrder.of(net).call():
+        wp = net._weights(dev)
+        noise = bool(net.training)
+        zs = _zs_list(z, E.NoiseLayers(net.variant, 'net', net.nb).total, (B, 64, H, W), dev) if noise else None
+        plan = _cached_plan(net, (B, H, W, net.precision, noise, zs is not None, wp.generation),
+                            lambda: E.build_rrdbnet_plan(wp, net.nb, net.in_nc, net.out_nc, B, H, W, net.precision, dev,
+                                                         noise, net.variant, zs is not None, scale=net.upscale))
+        out = torch.empty(plan.out_shape, dtype=torch.float32, device=dev)
+        plan.run(xin, out, E.current_stream(), _draw_seed() if (noise and zs is None) else 0, zs)
     return out
 
 
@@ -526,40 +538,30 @@ def run_rrdbnet_x8(net, x, slots_per_pass=None):
     images and is only meaningful at B = 1).  slots_per_pass (8, 4, 2 or 1; default ESR_X8_SLOTS, else 8 for square and 4
     for non-square input) bounds the memory of large images: each pass runs slots x B copies.  Every pass still holds
     whole-image plans; ``run_rrdbnet_tiled_x8`` is the ensemble per window, with the memory of a tiled forward."""
-    if x.dim() == 4 and x.shape[0] == 0:
-        E.require_cuda(x, 'input')
-        return x.new_zeros((0, net.out_nc, net.upscale * x.shape[2], net.upscale * x.shape[3]), dtype=torch.float32)
-    xin = _prep_input(x, 'input')
-    B, C_, H, W = xin.shape
-    if C_ != net.in_nc:
-        raise ValueError('expected %d input channels, got %d' % (net.in_nc, C_))
+    xin, empty = _eval_front(net, x, net.upscale)
+    if xin is None:
+        return empty
+    B, _, H, W = xin.shape
     slots = E.x8_slots(H, W, slots_per_pass)
-    order = E.StreamOrder.of(net)
-    cur = order.enter()
-    wp = net._weights(xin.device)
-    key = ('x8', slots, B, H, W, net.precision, False, False, wp.generation)
-    plan = net._plans.get(key)
-    if plan is None:
-        if len(net._plans) >= net.max_cached_plans:
-            net._plans.clear()
-        plan = E.build_rrdbnet_x8_plan(wp, net.nb, net.in_nc, net.out_nc, B, H, W, net.precision, xin.device,
-                                       net.variant, slots, scale=net.upscale)
-        net._plans[key] = plan
-    out = torch.empty(plan.out_shape, dtype=torch.float32, device=xin.device)
-    plan.run(xin, out, E.current_stream())
-    order.leave(cur)
+    with E.StreamOrder.of(net).call():
+        wp = net._weights(xin.device)
+        plan = _cached_plan(net, ('x8', slots, B, H, W, net.precision, False, False, wp.generation),
+                            lambda: E.build_rrdbnet_x8_plan(wp, net.nb, net.in_nc, net.out_nc, B, H, W, net.precision,
+                                                            xin.device, net.variant, slots, scale=net.upscale))
+        out = torch.empty(plan.out_shape, dtype=torch.float32, device=xin.device)
+        plan.run(xin, out, E.current_stream())
     return out
 
 
 tiled_geometry = E.tiled_geometry
 
 
-def _tiled_args(B, H, W, tile, pad, tiles_per_pass):
-    """Validated (tile, pad, P) of a tiled forward: P windows per image and pass.  Values beyond the image are cut down to
-    it, which changes no tile and no window."""
+def _tiled_ints(tile, pad, per_pass, per_pass_name):
+    """Validated ints (tile >= 1, pad >= 0, per_pass >= 1) of a tiled forward; per_pass_name: 'tiles_per_pass' or
+    'windows_per_pass', as the caller's argument is called."""
     import operator
     vals = []
-    for name, v, lo in (('tile', tile, 1), ('pad', pad, 0), ('tiles_per_pass', max(1, 16 // B) if tiles_per_pass is None else tiles_per_pass, 1)):
+    for name, v, lo in (('tile', tile, 1), ('pad', pad, 0), (per_pass_name, per_pass, 1)):
         try:
             if isinstance(v, bool):
                 raise TypeError
@@ -569,7 +571,14 @@ def _tiled_args(B, H, W, tile, pad, tiles_per_pass):
         if v < lo:
             raise ValueError('%s of a tiled forward must be an int >= %d, got %r' % (name, lo, v))
         vals.append(v)
-    tile, pad, P = min(vals[0], max(H, W)), min(vals[1], max(H, W)), vals[2]
+    return tuple(vals)
+
+
+def _tiled_args(B, H, W, tile, pad, tiles_per_pass):
+    """Validated (tile, pad, P) of a tiled forward: P windows per image and pass.  Values beyond the image are cut down to
+    it, which changes no tile and no window."""
+    tile, pad, P = _tiled_ints(tile, pad, max(1, 16 // B) if tiles_per_pass is None else tiles_per_pass, 'tiles_per_pass')
+    tile, pad = min(tile, max(H, W)), min(pad, max(H, W))
     P = min(P, -(-H // tile) * -(-W // tile))
     if P * B > 65535:
         raise ValueError('tiles_per_pass x batch = %d x %d windows are more than one launch takes (65535)' % (P, B))
@@ -656,29 +665,20 @@ def run_rrdbnet_tiled_x8(net, x, tile=96, pad=16, tiles_per_pass=None, slots_per
     every ``requires_grad`` are left untouched; the result [B, out_nc, 4H, 4W] fp32 carries no gradient; B > 1 is
     ensembled per image.  The default pass — tiles_per_pass = max(1, 16 // (slots B)) windows of 128 x 128 — is the
     16 x 128 x 128 batch that bench.py measures; other pass sizes are unmeasured (profiles/tiled_x8.md)."""
-    if x.dim() == 4 and x.shape[0] == 0:
-        E.require_cuda(x, 'input')
-        return x.new_zeros((0, net.out_nc, 4 * x.shape[2], 4 * x.shape[3]), dtype=torch.float32)
-    xin = _prep_input(x, 'input')
-    B, C_, H, W = xin.shape
-    if C_ != net.in_nc:
-        raise ValueError('expected %d input channels, got %d' % (net.in_nc, C_))
+    xin, empty = _eval_front(net, x, 4)
+    if xin is None:
+        return empty
+    B, _, H, W = xin.shape
     tile, pad, P, slots = _tiled_x8_args(B, H, W, tile, pad, tiles_per_pass, slots_per_pass)
     th, tw = min(tile + 2 * pad, H), min(tile + 2 * pad, W)
-    order = E.StreamOrder.of(net)
-    cur = order.enter()
-    wp = net._weights(xin.device)
-    key = ('tiled_x8', slots, P, B, th, tw, net.precision, wp.generation)   # no H, W: every image with this window shares it
-    plan = net._plans.get(key)
-    if plan is None:
-        if len(net._plans) >= net.max_cached_plans:
-            net._plans.clear()
-        plan = E.build_rrdbnet_tiled_x8_plan(wp, net.nb, net.in_nc, net.out_nc, B, th, tw, net.precision, xin.device,
-                                             net.variant, P, slots)
-        net._plans[key] = plan
-    out = torch.empty((B, net.out_nc, 4 * H, 4 * W), dtype=torch.float32, device=xin.device)
-    plan.run(xin, out, tile, pad, E.current_stream())
-    order.leave(cur)
+    with E.StreamOrder.of(net).call():
+        wp = net._weights(xin.device)
+        # no H, W in the key: every image with this window shares the plan
+        plan = _cached_plan(net, ('tiled_x8', slots, P, B, th, tw, net.precision, wp.generation),
+                            lambda: E.build_rrdbnet_tiled_x8_plan(wp, net.nb, net.in_nc, net.out_nc, B, th, tw,
+                                                                  net.precision, xin.device, net.variant, P, slots))
+        out = torch.empty((B, net.out_nc, 4 * H, 4 * W), dtype=torch.float32, device=xin.device)
+        plan.run(xin, out, tile, pad, E.current_stream())
     return out
 
 
@@ -696,47 +696,26 @@ def run_rrdbnet_tiled(net, x, tile=96, pad=16, tiles_per_pass=None):
     A pass costs what that batch costs, so an image the whole-image forward can take is faster through ``net(x)``
     (339 x 510: 2 passes, 17.3 against 8.5 ms in fp16): tiling bounds memory and shares the plan, it is not a speed-up.
     The x8 self-ensemble over the same windows is ``run_rrdbnet_tiled_x8``."""
-    if x.dim() == 4 and x.shape[0] == 0:
-        E.require_cuda(x, 'input')
-        return x.new_zeros((0, net.out_nc, 4 * x.shape[2], 4 * x.shape[3]), dtype=torch.float32)
-    xin = _prep_input(x, 'input')
-    B, C_, H, W = xin.shape
-    if C_ != net.in_nc:
-        raise ValueError('expected %d input channels, got %d' % (net.in_nc, C_))
+    xin, empty = _eval_front(net, x, 4)
+    if xin is None:
+        return empty
+    B, _, H, W = xin.shape
     tile, pad, P = _tiled_args(B, H, W, tile, pad, tiles_per_pass)
     th, tw = min(tile + 2 * pad, H), min(tile + 2 * pad, W)
-    order = E.StreamOrder.of(net)
-    cur = order.enter()
-    wp = net._weights(xin.device)
-    key = ('tiled', P, B, th, tw, net.precision, wp.generation)      # no H, W: every image with this window shares it
-    plan = net._plans.get(key)
-    if plan is None:
-        if len(net._plans) >= net.max_cached_plans:
-            net._plans.clear()
-        plan = E.build_rrdbnet_tiled_plan(wp, net.nb, net.in_nc, net.out_nc, B, th, tw, net.precision, xin.device,
-                                          net.variant, P)
-        net._plans[key] = plan
-    out = torch.empty((B, net.out_nc, 4 * H, 4 * W), dtype=torch.float32, device=xin.device)
-    plan.run(xin, out, tile, pad, E.current_stream())
-    order.leave(cur)
+    with E.StreamOrder.of(net).call():
+        wp = net._weights(xin.device)
+        # no H, W in the key: every image with this window shares the plan
+        plan = _cached_plan(net, ('tiled', P, B, th, tw, net.precision, wp.generation),
+                            lambda: E.build_rrdbnet_tiled_plan(wp, net.nb, net.in_nc, net.out_nc, B, th, tw, net.precision,
+                                                               xin.device, net.variant, P))
+        out = torch.empty((B, net.out_nc, 4 * H, 4 * W), dtype=torch.float32, device=xin.device)
+        plan.run(xin, out, tile, pad, E.current_stream())
     return out
 
 
 def _tiled_many_ints(tile, pad, windows_per_pass):
-    """Validated ints (tile, pad, windows_per_pass) of a tiled forward over an image set: _tiled_args' rules and wording."""
-    import operator
-    vals = []
-    for name, v, lo in (('tile', tile, 1), ('pad', pad, 0), ('windows_per_pass', windows_per_pass, 1)):
-        try:
-            if isinstance(v, bool):
-                raise TypeError
-            v = operator.index(v)
-        except TypeError:
-            raise ValueError('%s of a tiled forward must be an int >= %d, got %r' % (name, lo, v))
-        if v < lo:
-            raise ValueError('%s of a tiled forward must be an int >= %d, got %r' % (name, lo, v))
-        vals.append(v)
-    return tuple(vals)
+    """Validated ints (tile, pad, windows_per_pass) of a tiled forward over an image set."""
+    return _tiled_ints(tile, pad, windows_per_pass, 'windows_per_pass')
 
 
 def _tiled_many_groups(sizes, tile, pad, windows_per_pass):
@@ -845,63 +824,69 @@ def run_rrdbnet_tiled_many(net, images, tile=96, pad=16, windows_per_pass=16):
     if not xs:
         return []
     sizes = [(v.shape[2], v.shape[3]) for v, _ in xs]
-    m = max(max(s) for s in sizes)
-    tile, pad = min(tile, m), min(pad, m)          # cut down to the largest image: changes no tile and no window
-    groups = tiled_many_passes(sizes, tile, pad, wpp)      # refuses more than 65535 slots per pass
-    dev = xs[0][0].device
-    for i, (v, _) in enumerate(xs):
-        if v.device != dev:
-            raise ValueError('image %d is on %s, image 0 on %s: a tiled forward runs on one device' % (i, v.device, dev))
-    if dev.type != 'cuda':
-        raise ValueError('the images of a tiled forward are on %s: the HIP path needs tensors on an MI355X; there is '
-                         'no CPU fallback' % (dev,))
+    tile, pad, groups, dev = _tiled_set_passes(sizes, [v.device for v, _ in xs], tile, pad, wpp)
     xin = [v.detach().contiguous().float() for v, _ in xs]
-    outs = _run_tiled_set(net, 'tiled_many', E.build_rrdbnet_tiled_many_plan, groups, xin, sizes, dev,
+    outs = _run_tiled_set(net, 'tiled_many', E.TileManyEnds, groups, xin, sizes, dev,
                           lambda H, W: torch.empty((1, net.out_nc, 4 * H, 4 * W), dtype=torch.float32, device=dev),
-                          tile, pad)
+                          tile=tile, pad=pad)
     return [o if rank == 4 else o[0] for o, (_, rank) in zip(outs, xs)]
 
 
-def _run_tiled_set(net, kind, build, groups, xin, sizes, dev, new_out, *args):
+def _tiled_set_passes(sizes, devices, tile, pad, wpp):
+    """What a tiled forward over an image set settles before it touches the device, from the images' LR sizes and
+    devices and the validated ints -> (tile, pad, groups, device): tile and pad cut down to the largest image, which
+    changes no tile and no window; the passes (``tiled_many_passes``, which refuses more than 65535 slots per pass); and
+    the one GPU all images are on."""
+    m = max(max(s) for s in sizes)
+    tile, pad = min(tile, m), min(pad, m)
+    groups = tiled_many_passes(sizes, tile, pad, wpp)
+    dev = devices[0]
+    for i, d in enumerate(devices):
+        if d != dev:
+            raise ValueError('image %d is on %s, image 0 on %s: a tiled forward runs on one device' % (i, d, dev))
+    if dev.type != 'cuda':
+        raise ValueError('the images of a tiled forward are on %s: the HIP path needs tensors on an MI355X; there is '
+                         'no CPU fallback' % (dev,))
+    return tile, pad, groups, dev
+
+
+def _run_tiled_set(net, kind, ends, groups, xin, sizes, dev, new_out, **bound):
     """The passes ``groups`` (``tiled_many_passes``) of a tiled forward over the device images ``xin`` of the LR sizes
     ``sizes``, on the current stream -> the results, one ``new_out(H, W)`` per image.  One slot table for the call, the
     gather's entries of every pass of every group, then the stitch's (the 24-byte layout of esr_tile_item), uploaded
-    through the net's pinned ring in one non-blocking copy; one plan per group, keyed (kind, S, th, tw, precision,
-    generation) and built by ``build``; every pass runs it with (its gather slice, its stitch slice, *args, stream)."""
+    through the net's pinned ring in one non-blocking copy; one plan per group between the engine's ``ends``, keyed
+    (kind, S, th, tw, precision, generation) and bound to ``bound`` (tile, pad, ...); every pass runs it on its gather
+    slice and its stitch slice."""
     import numpy as np
-    order = E.StreamOrder.of(net)
-    cur = order.enter()
-    wp = net._weights(dev)
-    outs = [new_out(H, W) for H, W in sizes]
-    flat = [w for _, _, _, passes in groups for p in passes for w in p]
-    n = len(flat)
-    idx = np.fromiter((w[0] for w in flat), dtype=np.int64, count=n)
-    rec = np.zeros(2 * n, dtype=_tile_item_dtype())
-    rec['nchw'][:n] = np.array([x.data_ptr() for x in xin], dtype=np.uint64)[idx]
-    rec['nchw'][n:] = np.array([o.data_ptr() for o in outs], dtype=np.uint64)[idx]
-    hw = np.array(sizes, dtype=np.int32)[idx]
-    rec['H'][:n] = rec['H'][n:] = hw[:, 0]
-    rec['W'][:n] = rec['W'][n:] = hw[:, 1]
-    rec['t'][:n] = rec['t'][n:] = np.fromiter((w[1] for w in flat), dtype=np.int32, count=n)
-    rec['live'][:n] = rec['live'][n:] = np.fromiter((w[2] for w in flat), dtype=np.int32, count=n)
-    rings = net.__dict__.setdefault('_table_rings', {})
-    ring = rings.get(dev.index)
-    if ring is None:
-        ring = rings[dev.index] = E.PinnedRing()
-    table = ring.upload(rec, dev)
-    isz, stream, at = rec.dtype.itemsize, E.current_stream(), 0
-    for th, tw, S, passes in groups:
-        key = (kind, S, th, tw, net.precision, wp.generation)    # no H, W: whatever images have this window
-        plan = net._plans.get(key)
-        if plan is None:
-            if len(net._plans) >= net.max_cached_plans:
-                net._plans.clear()
-            plan = build(wp, net.nb, net.in_nc, net.out_nc, S, th, tw, net.precision, dev, net.variant)
-            net._plans[key] = plan
-        for _ in passes:
-            plan.run(table[at * isz:(at + S) * isz], table[(n + at) * isz:(n + at + S) * isz], *args, stream)
-            at += S
-    order.leave(cur)
+    with E.StreamOrder.of(net).call():
+        wp = net._weights(dev)
+        outs = [new_out(H, W) for H, W in sizes]
+        flat = [w for _, _, _, passes in groups for p in passes for w in p]
+        n = len(flat)
+        idx = np.fromiter((w[0] for w in flat), dtype=np.int64, count=n)
+        rec = np.zeros(2 * n, dtype=_tile_item_dtype())
+        rec['nchw'][:n] = np.array([x.data_ptr() for x in xin], dtype=np.uint64)[idx]
+        rec['nchw'][n:] = np.array([o.data_ptr() for o in outs], dtype=np.uint64)[idx]
+        hw = np.array(sizes, dtype=np.int32)[idx]
+        rec['H'][:n] = rec['H'][n:] = hw[:, 0]
+        rec['W'][:n] = rec['W'][n:] = hw[:, 1]
+        rec['t'][:n] = rec['t'][n:] = np.fromiter((w[1] for w in flat), dtype=np.int32, count=n)
+        rec['live'][:n] = rec['live'][n:] = np.fromiter((w[2] for w in flat), dtype=np.int32, count=n)
+        rings = net.__dict__.setdefault('_table_rings', {})
+        ring = rings.get(dev.index)
+        if ring is None:
+            ring = rings[dev.index] = E.PinnedRing()
+        table = ring.upload(rec, dev)
+        isz, stream, at = rec.dtype.itemsize, E.current_stream(), 0
+        for th, tw, S, passes in groups:
+            # no H, W in the key: whatever images have this window
+            plan = _cached_plan(net, (kind, S, th, tw, net.precision, wp.generation),
+                                lambda: E.build_rrdbnet_tiled_many_plan(wp, net.nb, net.in_nc, net.out_nc, S, th, tw,
+                                                                        net.precision, dev, net.variant, ends))
+            plan.bind(**bound)
+            for _ in passes:
+                plan.run(table[at * isz:(at + S) * isz], table[(n + at) * isz:(n + at + S) * isz], stream)
+                at += S
     return outs
 
 
@@ -964,19 +949,11 @@ def run_rrdbnet_images(net, images, tile=96, pad=16, windows_per_pass=16, bgr=Fa
     if not images:
         return []
     sizes = [(x.shape[0], x.shape[1]) for x in images]
-    m = max(max(s) for s in sizes)
-    tile, pad = min(tile, m), min(pad, m)          # cut down to the largest image: changes no tile and no window
-    groups = tiled_many_passes(sizes, tile, pad, wpp)      # refuses more than 65535 slots per pass
-    dev = images[0].device
-    for i, x in enumerate(images):
-        if x.device != dev:
-            raise ValueError('image %d is on %s, image 0 on %s: a tiled forward runs on one device' % (i, x.device, dev))
-    if dev.type != 'cuda':
-        raise ValueError('the images of a tiled forward are on %s: the HIP path needs tensors on an MI355X; there is '
-                         'no CPU fallback' % (dev,))
+    tile, pad, groups, dev = _tiled_set_passes(sizes, [x.device for x in images], tile, pad, wpp)
     xin = [x.detach().contiguous() for x in images]
-    return _run_tiled_set(net, 'tiled_img', E.build_rrdbnet_tiled_img_plan, groups, xin, sizes, dev,
-                          lambda H, W: torch.empty((4 * H, 4 * W, 3), dtype=torch.uint8, device=dev), tile, pad, bool(bgr))
+    return _run_tiled_set(net, 'tiled_img', E.TileImgEnds, groups, xin, sizes, dev,
+                          lambda H, W: torch.empty((4 * H, 4 * W, 3), dtype=torch.uint8, device=dev),
+                          tile=tile, pad=pad, bgr=1 if bgr else 0)
 
 
 def run_rrdbnet_evaluate(net, lr_images, hr_images, tile=96, pad=16, windows_per_pass=16, bgr=False, crop=None):

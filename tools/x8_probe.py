@@ -84,8 +84,9 @@ def main():
             out = torch.zeros(xp.out_shape, dtype=torch.float32, device=dev)
             for _ in range(a.reps):
                 tot, imp, red = 0.0, 0.0, 0.0
-                for k0 in range(0, 8, xp.slots):          # every pass with its own range, as X8Plan.run sets it
-                    plan = xp.bind_pass(k0)
+                for k0, i, accumulate, scale in E.x8_passes(xp.slots):    # every pass with its own range, as X8Plan.run
+                    plan = xp.plans[i]
+                    plan.bind(k_begin=k0, accumulate=accumulate, scale=scale)
                     arr = plan.ops.array()
                     E.set_nchw(arr[plan.in_op], x.data_ptr())     # (the ops keep the pointers of their last run)
                     E.set_nchw(arr[plan.out_op], out.data_ptr())
