@@ -26,6 +26,7 @@ OP_TILE_X8 = 17
 OP_FOLD3 = 18
 OP_TILE_MANY = 19
 OP_TILE_IMG = 20
+OP_TILE_SET_X8 = 21
 CHAIN_VARIANT_REGULAR, CHAIN_VARIANT_TRACED = 1, 2     # esr_debug_chain_last_variant (| rows per wave << 8)
 BN_STATS, BN_FINALIZE, BN_APPLY, BN_BWD_REDUCE, BN_BWD_FINAL, BN_BWD_APPLY, BN_RESTAT, BN_FIN_APPLY = 0, 1, 2, 3, 4, 5, 6, 7
 NO_LAYER = 0xFFFFFFFF
@@ -122,6 +123,14 @@ class esr_tile_img_item(C.Structure):
 
 class esr_tile_img(C.Structure):
     _fields_ = esr_tile_many._fields_ + [('bgr', C.c_int32)]
+
+
+class esr_tile_set_x8(C.Structure):
+    """esr_tile_many's pass-level fields with n_windows (one table entry per WINDOW) in the place of n_slots, esr_tile_x8's
+    k range, and the outside format: img, bgr, and acc, the partial sums of the 8-bit form."""
+    _fields_ = [(('n_windows' if n == 'n_slots' else n), t) for n, t in esr_tile_many._fields_] + [
+        ('k_begin', C.c_int32), ('k_count', C.c_int32), ('accumulate', C.c_int32), ('mean_scale', C.c_float),
+        ('img', C.c_int32), ('bgr', C.c_int32), ('acc', C.c_void_p)]
 
 
 class esr_fold3(C.Structure):
@@ -310,7 +319,7 @@ class _op_union(C.Union):
                 ('pack_batch', esr_pack_batch), ('rdb_chain', esr_rdb_chain), ('frag_gather', esr_frag_gather),
                 ('rdb_wgrad', esr_rdb_wgrad), ('dihedral', esr_dihedral), ('tile', esr_tile),
                 ('tile_x8', esr_tile_x8), ('fold3', esr_fold3), ('tile_many', esr_tile_many),
-                ('tile_img', esr_tile_img)]
+                ('tile_img', esr_tile_img), ('tile_set_x8', esr_tile_set_x8)]
 
 
 class esr_op(C.Structure):
@@ -328,7 +337,8 @@ EXPORTS = ['esr_packed_weight_bytes', 'esr_g32_dims', 'esr_conv_forward', 'esr_p
            'esr_rdb_mask_bytes', 'esr_rdb_check_abort', 'esr_debug_hold_cus', 'esr_debug_device_alias', 'esr_debug_chain_order_waits', 'esr_debug_chain_last_variant', 'esr_debug_chain_force_general',
            'esr_debug_mfma_probe', 'esr_debug_rdb_wgrad_follow', 'esr_dihedral_op', 'esr_tile_op',
            'esr_tile_x8_op', 'esr_l2_loss_forward', 'esr_fold3_op', 'esr_gan_loss_forward',
-           'esr_batch_assemble', 'esr_tile_many_op', 'esr_tile_img_op', 'esr_image_set_metrics']
+           'esr_batch_assemble', 'esr_tile_many_op', 'esr_tile_img_op', 'esr_image_set_metrics',
+           'esr_tile_set_x8_op']
 
 _lib = None
 _lock = threading.Lock()
@@ -394,7 +404,8 @@ def lib():
                          ('esr_dihedral_op', esr_dihedral), ('esr_tile_op', esr_tile),
                          ('esr_tile_x8_op', esr_tile_x8), ('esr_fold3_op', esr_fold3),
                          ('esr_batch_assemble', esr_batch), ('esr_tile_many_op', esr_tile_many),
-                         ('esr_tile_img_op', esr_tile_img), ('esr_image_set_metrics', esr_set_metrics)):
+                         ('esr_tile_img_op', esr_tile_img), ('esr_image_set_metrics', esr_set_metrics),
+                         ('esr_tile_set_x8_op', esr_tile_set_x8)):
             getattr(L, name).argtypes = [C.POINTER(st), C.c_void_p]
         if L.esr_sizeof_op() != C.sizeof(esr_op):
             raise HipExtensionError('ABI mismatch: sizeof(esr_op) C=%d ctypes=%d'

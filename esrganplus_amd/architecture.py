@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from . import block as B
 from .functional import (run_rrdbnet, run_rrdbnet_evaluate, run_rrdbnet_images, run_rrdbnet_tiled, run_rrdbnet_tiled_many,
-                         run_rrdbnet_tiled_x8, run_rrdbnet_x8)
+                         run_rrdbnet_tiled_many_x8, run_rrdbnet_tiled_x8, run_rrdbnet_x8)
 
 
 SUPPORTED_UPSCALE = (1, 2, 3, 4, 8)
@@ -161,38 +161,54 @@ class _RRDBNetBase(B._PlannedModule):
         grouped by window shape, filler only in a group's last pass — so a folder runs at the cost of full passes ->
         a list of [out_nc, 4H, 4W] / [1, out_nc, 4H, 4W] float32 results, ranks and order as the inputs, without
         gradient.  One launch plan per (windows per pass, window shape), whatever the images.  Always the eval forward;
-        ``self.training`` and ``requires_grad`` are left as they are.  Not covered: the x8 self-ensemble over an image
-        set, scales other than 4, blending.  See ``functional.run_rrdbnet_tiled_many``; for 8-bit images in and out,
-        ``forward_images``."""
+        ``self.training`` and ``requires_grad`` are left as they are.  Not covered: scales other than 4, blending.  See
+        ``functional.run_rrdbnet_tiled_many``; for 8-bit images in and out, ``forward_images``; for the x8
+        self-ensemble, ``forward_tiled_many_x8``."""
         self._x4_only('forward_tiled_many')
         self._ends_fit('forward_tiled_many')
         self._join_pending()
         return run_rrdbnet_tiled_many(self, images, tile, pad, windows_per_pass)
 
-    def forward_images(self, images, tile=96, pad=16, windows_per_pass=16, bgr=False):
+    def forward_tiled_many_x8(self, images, tile=96, pad=16, windows_per_pass=16, slots_per_pass=None):
+        """The x8 self-ensemble over an image set: ``forward_tiled_x8``'s ensemble per window with
+        ``forward_tiled_many``'s packing — the windows of every image in ``images``, grouped by window shape,
+        ``windows_per_pass`` batch entries to a pass: ``windows_per_pass // slots`` windows, each in ``slots`` (8 for
+        square windows, 4 otherwise, or ``slots_per_pass``) of its eight transforms at a time -> a list of
+        [out_nc, 4H, 4W] / [1, out_nc, 4H, 4W] float32 results, ranks and order as the inputs, without gradient.  One
+        launch plan (two for non-square windows) per (slots, windows per pass, window shape), whatever the images.
+        Always the eval forward; ``self.training`` and ``requires_grad`` are left as they are.  See
+        ``functional.run_rrdbnet_tiled_many_x8``; with 8-bit ends, ``forward_images(x8=True)``."""
+        self._x4_only('forward_tiled_many_x8')
+        self._ends_fit('forward_tiled_many_x8')
+        self._join_pending()
+        return run_rrdbnet_tiled_many_x8(self, images, tile, pad, windows_per_pass, slots_per_pass)
+
+    def forward_images(self, images, tile=96, pad=16, windows_per_pass=16, bgr=False, x8=False, slots_per_pass=None):
         """``forward_tiled_many`` with 8-bit ends: ``images`` is a sequence of ``torch.uint8`` tensors [H, W, 3] (HWC), of
         any sizes, on one GPU -> a list of fresh uint8 device tensors [4H, 4W, 3], in input order, without gradient.
         ``bgr=False``: R, G, B in memory on both ends (PIL); ``bgr=True``: B, G, R (cv2, the reference's scripts).  The
         input is ``float32(v) / 255`` as a true division, the output ``rint(clamp(y, 0, 1) * 255)`` — the reference's
         inference-script arithmetic — both inside the gather and stitch kernels: 3 bytes up and 48 down per LR pixel, no
         per-pixel host work.  ``tile`` >= the largest image side runs every image whole.  Always the eval forward;
-        ``self.training`` and ``requires_grad`` are left as they are.  Not covered: the x8 self-ensemble with 8-bit ends,
-        scales other than 4, 16-bit or alpha images, CPU or numpy inputs, blending.  See
-        ``functional.run_rrdbnet_images``."""
+        ``self.training`` and ``requires_grad`` are left as they are.  ``x8=True``: the self-ensemble per window
+        (``forward_tiled_many_x8``'s passes, ``slots_per_pass`` its slots) with the same 8-bit ends; the mean is
+        quantised once, by the last k range.  Not covered: scales other than 4, 16-bit or alpha images, CPU or numpy
+        inputs, blending.  See ``functional.run_rrdbnet_images``."""
         self._x4_only('forward_images')
         self._join_pending()
-        return run_rrdbnet_images(self, images, tile, pad, windows_per_pass, bgr)
+        return run_rrdbnet_images(self, images, tile, pad, windows_per_pass, bgr, x8, slots_per_pass)
 
-    def evaluate_images(self, lr_images, hr_images, tile=96, pad=16, windows_per_pass=16, bgr=False, crop=None):
+    def evaluate_images(self, lr_images, hr_images, tile=96, pad=16, windows_per_pass=16, bgr=False, crop=None,
+                        x8=False, slots_per_pass=None):
         """The reference's test script (codes/test.py:49-110) for one image set: ``forward_images(lr_images, ...)``, then
         PSNR, SSIM, PSNR_Y and SSIM_Y of every result against its ``hr_images`` entry (uint8 [4H, 4W, 3] on the same
         GPU) in one device pass -> ``(sr_images, result)``; ``result.read()`` is the one read-back, an [n, 4] float64
         array, ``result.averages()`` the script's four means.  ``crop=None`` cuts ``upscale`` pixels per side as the
-        script does.  Nothing synchronises before ``read()``.  See ``functional.run_rrdbnet_evaluate`` and
-        ``metrics.device_set_metrics``."""
+        script does.  ``x8=True`` scores ``forward_images(x8=True)``, the self-ensemble.  Nothing synchronises before
+        ``read()``.  See ``functional.run_rrdbnet_evaluate`` and ``metrics.device_set_metrics``."""
         self._x4_only('evaluate_images')
         self._join_pending()
-        return run_rrdbnet_evaluate(self, lr_images, hr_images, tile, pad, windows_per_pass, bgr, crop)
+        return run_rrdbnet_evaluate(self, lr_images, hr_images, tile, pad, windows_per_pass, bgr, crop, x8, slots_per_pass)
 
 
 class RRDBNet(_RRDBNetBase):

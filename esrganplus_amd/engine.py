@@ -453,7 +453,35 @@ class TileImgEnds(TileManyEnds):
     per_run = _both('tile', 'pad', 'bgr')
 
 
-ENDS_OF_KIND = {e.kind: e for e in (Ends, DihedralEnds, TileEnds, TileX8Ends, TileManyEnds, TileImgEnds)}
+class TileSetX8Ends(TileManyEnds):
+    """Image-set self-ensemble ends (esr_tile_set_x8) of a batch of slots x P windows: the gather-import of the transforms
+    [k0, k0 + slots) of the P upright th x tw windows the pass's table names (the builder's H x W is tw x th for the
+    transposed slots, k0 = 4), and the stitch-reduce that undoes the transforms, sums and copies every live window's
+    owned rectangle into ITS image's result.  img: 8-bit HWC images outside instead of fp32 NCHW; acc: the fp32 tensor
+    [P, C, 4 th, 4 tw] that carries the 8-bit form's partial sums between the passes (the two plans of a non-square
+    window share it; None: the float form, or all eight slots in one pass).  tile, pad, bgr and the pass's k range,
+    accumulate and mean scale are set per run."""
+
+    kind, field, struct = L.OP_TILE_SET_X8, 'tile_set_x8', L.esr_tile_set_x8
+    per_run = dict(_both('tile', 'pad', 'bgr', 'k_begin'), accumulate=(None, 'accumulate'), scale=(None, 'mean_scale'))
+
+    def __init__(self, th, tw, k0, slots, img=False, acc=None):
+        self.th, self.tw, self.k0, self.slots, self.img, self.acc = th, tw, k0, slots, img, acc
+
+    def fill(self, b, C_, to_g32, g=None, slots=None):
+        d = self.ends_of(self.struct(), C_, to_g32, g, slots)
+        d.dtype, d.scale = b.dt_e, 1 if to_g32 else 4
+        d.th, d.tw, d.n_windows = self.th, self.tw, b.B // self.slots
+        d.tile, d.pad = max(self.th, self.tw), 0
+        d.k_begin, d.k_count, d.accumulate, d.mean_scale = self.k0, self.slots, 0, 1.0
+        d.img, d.bgr = int(self.img), 0
+        if self.acc is not None and not to_g32:
+            b.bufs.append(self.acc)
+            d.acc = self.acc.data_ptr()
+        return d
+
+
+ENDS_OF_KIND = {e.kind: e for e in (Ends, DihedralEnds, TileEnds, TileX8Ends, TileManyEnds, TileImgEnds, TileSetX8Ends)}
 
 
 def set_nchw(op, ptr):
@@ -1084,6 +1112,35 @@ def build_rrdbnet_tiled_x8_plan(wp, nb, in_nc, out_nc, B, th, tw, dtype, device,
                                 ends=TileX8Ends(B, th, tw, k0, slots))
              for k0, sh, sw in ([(0, th, tw)] if th == tw else [(0, th, tw), (4, tw, th)])]
     return TiledX8Plan(plans, slots, P)
+
+
+class TiledSetX8Plan:
+    """The x8 self-ensemble of P windows of th x tw per pass, whichever images they belong to: the x8_passes of one
+    inference plan of batch slots x P (two plans for non-square windows: th x tw for k 0..3, tw x th for k 4..7) between
+    TileSetX8Ends, chained through the results themselves (fp32 ends) or through `acc` (8-bit ends).  Nothing in it
+    depends on an image or a channel order."""
+
+    def __init__(self, plans, slots, P, acc):
+        self.plans, self.slots, self.P, self.acc = plans, slots, P, acc
+
+    def bind(self, **bound):
+        """tile and pad (and bgr) of the passes that follow."""
+        for plan in self.plans:
+            plan.bind(**bound)
+
+    def run(self, gather_items, stitch_items, stream):
+        """One pass of P windows: the two uint8 device tensors hold its P item entries (LR images / HR results)."""
+        for k0, i, accumulate, scale in x8_passes(self.slots):
+            self.plans[i].bind(k_begin=k0, accumulate=accumulate, scale=scale)
+            self.plans[i].run(gather_items, stitch_items, stream)
+
+
+def build_rrdbnet_tiled_set_x8_plan(wp, nb, in_nc, out_nc, P, th, tw, dtype, device, variant, slots, img=False):
+    acc = (torch.empty((P, out_nc, 4 * th, 4 * tw), dtype=torch.float32, device=device) if img and slots < 8 else None)
+    plans = [build_rrdbnet_plan(wp, nb, in_nc, out_nc, slots * P, sh, sw, dtype, device, False, variant, False,
+                                ends=TileSetX8Ends(th, tw, k0, slots, img, acc))
+             for k0, sh, sw in ([(0, th, tw)] if th == tw else [(0, th, tw), (4, tw, th)])]
+    return TiledSetX8Plan(plans, slots, P, acc)
 
 
 # =================================================================================================

@@ -797,6 +797,118 @@ def tiled_many_reference(fn, images, tile, pad, windows_per_pass=16):
     return [o if rank == 4 else o[0] for o, (_, rank) in zip(outs, xs)]
 
 
+def _x8_slots_arg(slots_per_pass, x8=True):
+    """slots_per_pass of an image-set entry, checked before anything else is: one of E.X8_SLOTS or None, and only with
+    the self-ensemble."""
+    if slots_per_pass is None:
+        return None
+    if not x8:
+        raise ValueError('slots_per_pass = %r belongs to the x8 self-ensemble: pass x8=True' % (slots_per_pass,))
+    if isinstance(slots_per_pass, bool) or slots_per_pass not in E.X8_SLOTS:
+        raise ValueError('slots per pass of the x8 self-ensemble must be one of %s, got %r' % (E.X8_SLOTS, slots_per_pass))
+    return int(slots_per_pass)
+
+
+def tiled_many_x8_passes(sizes, tile, pad, windows_per_pass=16, slots_per_pass=None):
+    """The passes of the x8 self-ensemble over images of the LR sizes ``sizes`` [(H, W)]: host code only.  Groups, their
+    order and the order of the windows inside a group are ``tiled_many_passes``'.  ``windows_per_pass`` counts batch
+    entries of the launch plan, and a window takes ``slots = E.x8_slots(th, tw, slots_per_pass)`` of them at a time
+    (8, 4, 2 or 1; 8 for square windows and 4 otherwise by default), so a pass holds
+    P = min(max(1, windows_per_pass // slots), windows of the group) windows and runs 8 / slots times, once per k range
+    (``E.x8_passes``); the default pass is the 16 x 128 x 128 batch that bench.py measures.  Only a group's last pass may
+    hold filler, which repeats the group's last window with live = 0 (gathered for every k, never reduced).
+    -> [(th, tw, slots, P, passes)] per group, passes a list of P-tuples (image, tile, live)."""
+    slots_per_pass = _x8_slots_arg(slots_per_pass)
+    tile, pad, wpp = _tiled_many_ints(tile, pad, windows_per_pass)
+    out = []
+    for th, tw, _, members in _tiled_many_groups([(int(h), int(w)) for h, w in sizes], tile, pad, 1):
+        slots = E.x8_slots(th, tw, slots_per_pass)
+        wins = [(i, t, 1) for i, n in members for t in range(n)]
+        P = min(max(1, wpp // slots), len(wins))
+        if slots * P > 65535:
+            raise ValueError('slots x windows = %d x %d batch entries of %d x %d windows are more than one launch takes '
+                             '(65535)' % (slots, P, th, tw))
+        passes = []
+        for k in range(0, len(wins), P):
+            p = wins[k:k + P]
+            passes.append(tuple(p + [(wins[-1][0], wins[-1][1], 0)] * (P - len(p))))
+        out.append((th, tw, slots, P, passes))
+    return out
+
+
+def tiled_many_x8_reference(fn, images, tile, pad, windows_per_pass=16, slots_per_pass=None):
+    """Pure-torch restatement of the x8 self-ensemble over an image set and a x4 forward ``fn``: the passes of
+    ``tiled_many_x8_passes``; per pass its P windows — filler included — transformed the eight ways of ``x8_transform``
+    in runs of ``slots`` transforms, so ``fn`` sees batches of slots P windows, entry (k - k0) P + p, th x tw for k < 4
+    and tw x th for k >= 4; the outputs inverse-transformed and summed as seven fp32 adds in k order, times 0.125
+    (``tiled_x8_reference``'s arithmetic); and the owned rectangle of every live window's mean copied into its image's
+    result.  Nothing is blended.  -> a list of fp32 results, [C', 4H, 4W] or [1, C', 4H, 4W] as the inputs' ranks."""
+    xs = _tiled_many_images(list(images), None)
+    groups = tiled_many_x8_passes([(v.shape[2], v.shape[3]) for v, _ in xs], tile, pad, windows_per_pass, slots_per_pass)
+    tile, pad, _ = _tiled_many_ints(tile, pad, windows_per_pass)
+    geo = [tiled_geometry(v.shape[2], v.shape[3], tile, pad) for v, _ in xs]
+    outs = [None] * len(xs)
+    for th, tw, slots, P, passes in groups:
+        for p in passes:
+            wins = torch.cat([xs[i][0][:, :, geo[i][4][t][4]:geo[i][4][t][4] + th, geo[i][4][t][5]:geo[i][4][t][5] + tw]
+                              for i, t, _ in p], 0)
+            acc = None
+            for k0 in range(0, 8, slots):
+                ys = fn(torch.cat([x8_transform(wins, k) for k in range(k0, k0 + slots)], 0)).float().split(P, 0)
+                for k, y in zip(range(k0, k0 + slots), ys):
+                    acc = x8_inverse(y, k) if acc is None else acc + x8_inverse(y, k)
+            mean = acc * 0.125
+            for s, (i, t, live) in enumerate(p):
+                if not live:
+                    continue
+                if outs[i] is None:
+                    outs[i] = mean.new_empty((1, mean.shape[1], 4 * xs[i][0].shape[2], 4 * xs[i][0].shape[3]))
+                y0, y1, x0, x1, wy, wx = geo[i][4][t]
+                outs[i][:, :, 4 * y0:4 * y1, 4 * x0:4 * x1] = mean[s:s + 1, :, 4 * (y0 - wy):4 * (y1 - wy), 4 * (x0 - wx):4 * (x1 - wx)]
+    return [o if rank == 4 else o[0] for o, (_, rank) in zip(outs, xs)]
+
+
+def _tiled_set_x8_passes(sizes, devices, tile, pad, wpp, slots_per_pass):
+    """``_tiled_set_passes`` for the self-ensemble: the groups are ``tiled_many_x8_passes``'."""
+    m = max(max(s) for s in sizes)
+    tile, pad = min(tile, m), min(pad, m)
+    groups = tiled_many_x8_passes(sizes, tile, pad, wpp, slots_per_pass)
+    return tile, pad, groups, _one_gpu(devices)
+
+
+def run_rrdbnet_tiled_many_x8(net, images, tile=96, pad=16, windows_per_pass=16, slots_per_pass=None):
+    """The x8 self-ensemble of RRDBNet over an image set: ``run_rrdbnet_tiled_x8``'s ensemble per window — pad included,
+    eight transforms, inverse transforms summed in k order, times 0.125, the owned rectangle of the mean copied out —
+    with ``run_rrdbnet_tiled_many``'s packing: the windows of ALL images share the passes (``tiled_many_x8_passes``),
+    grouped by window shape, P = min(max(1, windows_per_pass // slots), windows of the group) windows per pass, each
+    pass run 8 / slots times as one batch of slots x P entries of the ordinary inference plan (two plans for non-square
+    windows) and chained into the results; only a group's last pass holds filler.  ``windows_per_pass`` counts batch
+    entries, so the default pass is the 16 x 128 x 128 batch bench.py measures, where a loop of ``run_rrdbnet_tiled_x8``
+    over small images runs slots x P of one image each.  ``images``, the results (fresh fp32 tensors, ranks and order as
+    the inputs, no gradient), the pinned slot table (one 24-byte entry per window and side, one non-blocking copy), the
+    stream order and the cutting of tile / pad down to the largest image are ``run_rrdbnet_tiled_many``'s.  One launch
+    plan per (slots, P, window shape, precision, weight generation), keyed 'tiled_set_x8' — no image size in the key —
+    between the table-driven gather-import and stitch-reduce of include/esrgan_hip.h: esr_tile_set_x8.  Bit-identical
+    to ``tiled_many_x8_reference(net, ...)``; for one image, to ``run_rrdbnet_tiled_x8(x[None], tile, pad, P, slots)``
+    at windows_per_pass = slots x P.  Noise is off whatever ``net.training`` is; the module's mode and every
+    ``requires_grad`` are left untouched.  Measured (profiles/set_x8.md, nb = 23, fp16): the device time is that of the
+    plan runs — packing two single-window 128 x 128 images into a pass gives 0.977 of the per-image loop, not 0.5, since
+    a batch of 8 costs half of 16 — the gain is the host time, the resident bytes and the caller's loop.  Out of scope:
+    scales other than 4, blending."""
+    slots_per_pass = _x8_slots_arg(slots_per_pass)
+    tile, pad, wpp = _tiled_many_ints(tile, pad, windows_per_pass)
+    xs = _tiled_many_images(list(images), net.in_nc)
+    if not xs:
+        return []
+    sizes = [(v.shape[2], v.shape[3]) for v, _ in xs]
+    tile, pad, groups, dev = _tiled_set_x8_passes(sizes, [v.device for v, _ in xs], tile, pad, wpp, slots_per_pass)
+    xin = [v.detach().contiguous().float() for v, _ in xs]
+    outs = _run_tiled_set(net, 'tiled_set_x8', E.TileSetX8Ends, groups, xin, sizes, dev,
+                          lambda H, W: torch.empty((1, net.out_nc, 4 * H, 4 * W), dtype=torch.float32, device=dev),
+                          tile=tile, pad=pad, bgr=0)
+    return [o if rank == 4 else o[0] for o, (_, rank) in zip(outs, xs)]
+
+
 def _tile_item_dtype():
     import numpy as np
     return np.dtype([('nchw', '<u8'), ('H', '<i4'), ('W', '<i4'), ('t', '<i4'), ('live', '<i4')])   # esr_tile_item
@@ -817,8 +929,8 @@ def run_rrdbnet_tiled_many(net, images, tile=96, pad=16, windows_per_pass=16):
     device holds the plan's activations of S windows plus this call's inputs and outputs.  Bit-identical to
     ``tiled_many_reference(net, ...)``; for one image, to ``run_rrdbnet_tiled(x, tile, pad, windows_per_pass)``.  Noise
     is off whatever ``net.training`` is; the module's mode and every ``requires_grad`` are left untouched.
-    Out of scope: the x8 self-ensemble over an image set, scales other than 4, blending.  For 8-bit images in and out
-    see ``run_rrdbnet_images``: the same passes with the uint8 conversions fused into the two ends."""
+    Out of scope: scales other than 4, blending.  For 8-bit images in and out see ``run_rrdbnet_images``: the same passes
+    with the uint8 conversions fused into the two ends; for the x8 self-ensemble, ``run_rrdbnet_tiled_many_x8``."""
     tile, pad, wpp = _tiled_many_ints(tile, pad, windows_per_pass)
     xs = _tiled_many_images(list(images), net.in_nc)
     if not xs:
@@ -840,6 +952,11 @@ def _tiled_set_passes(sizes, devices, tile, pad, wpp):
     m = max(max(s) for s in sizes)
     tile, pad = min(tile, m), min(pad, m)
     groups = tiled_many_passes(sizes, tile, pad, wpp)
+    return tile, pad, groups, _one_gpu(devices)
+
+
+def _one_gpu(devices):
+    """The one GPU all images of a tiled forward are on."""
     dev = devices[0]
     for i, d in enumerate(devices):
         if d != dev:
@@ -847,21 +964,23 @@ def _tiled_set_passes(sizes, devices, tile, pad, wpp):
     if dev.type != 'cuda':
         raise ValueError('the images of a tiled forward are on %s: the HIP path needs tensors on an MI355X; there is '
                          'no CPU fallback' % (dev,))
-    return tile, pad, groups, dev
+    return dev
 
 
-def _run_tiled_set(net, kind, ends, groups, xin, sizes, dev, new_out, **bound):
+def _run_tiled_set(net, kind, ends, groups, xin, sizes, dev, new_out, img=False, **bound):
     """The passes ``groups`` (``tiled_many_passes``) of a tiled forward over the device images ``xin`` of the LR sizes
     ``sizes``, on the current stream -> the results, one ``new_out(H, W)`` per image.  One slot table for the call, the
     gather's entries of every pass of every group, then the stitch's (the 24-byte layout of esr_tile_item), uploaded
     through the net's pinned ring in one non-blocking copy; one plan per group between the engine's ``ends``, keyed
     (kind, S, th, tw, precision, generation) and bound to ``bound`` (tile, pad, ...); every pass runs it on its gather
-    slice and its stitch slice."""
+    slice and its stitch slice.  Groups of ``tiled_many_x8_passes`` (th, tw, slots, P, passes) run the self-ensemble
+    instead: the table holds one entry per WINDOW, the plan is keyed (kind, slots, P, th, tw, precision, generation) and
+    runs its ``x8_passes`` on every pass's slices between ``E.TileSetX8Ends``; ``img``: the images outside are 8-bit."""
     import numpy as np
     with E.StreamOrder.of(net).call():
         wp = net._weights(dev)
         outs = [new_out(H, W) for H, W in sizes]
-        flat = [w for _, _, _, passes in groups for p in passes for w in p]
+        flat = [w for g in groups for p in g[-1] for w in p]
         n = len(flat)
         idx = np.fromiter((w[0] for w in flat), dtype=np.int64, count=n)
         rec = np.zeros(2 * n, dtype=_tile_item_dtype())
@@ -878,11 +997,18 @@ def _run_tiled_set(net, kind, ends, groups, xin, sizes, dev, new_out, **bound):
             ring = rings[dev.index] = E.PinnedRing()
         table = ring.upload(rec, dev)
         isz, stream, at = rec.dtype.itemsize, E.current_stream(), 0
-        for th, tw, S, passes in groups:
+        for th, tw, *per_pass, passes in groups:
             # no H, W in the key: whatever images have this window
-            plan = _cached_plan(net, (kind, S, th, tw, net.precision, wp.generation),
-                                lambda: E.build_rrdbnet_tiled_many_plan(wp, net.nb, net.in_nc, net.out_nc, S, th, tw,
-                                                                        net.precision, dev, net.variant, ends))
+            if len(per_pass) == 1:
+                S, = per_pass
+                plan = _cached_plan(net, (kind, S, th, tw, net.precision, wp.generation),
+                                    lambda: E.build_rrdbnet_tiled_many_plan(wp, net.nb, net.in_nc, net.out_nc, S, th, tw,
+                                                                            net.precision, dev, net.variant, ends))
+            else:
+                slots, S = per_pass
+                plan = _cached_plan(net, (kind, slots, S, th, tw, net.precision, wp.generation),
+                                    lambda: E.build_rrdbnet_tiled_set_x8_plan(wp, net.nb, net.in_nc, net.out_nc, S, th, tw,
+                                                                              net.precision, dev, net.variant, slots, img))
             plan.bind(**bound)
             for _ in passes:
                 plan.run(table[at * isz:(at + S) * isz], table[(n + at) * isz:(n + at + S) * isz], stream)
@@ -921,7 +1047,19 @@ def images_reference(fn, images, tile, pad, windows_per_pass=16, bgr=False):
     return [(o.flip(2) if bgr else o).contiguous() for o in outs]
 
 
-def run_rrdbnet_images(net, images, tile=96, pad=16, windows_per_pass=16, bgr=False):
+def images_x8_reference(fn, images, tile, pad, windows_per_pass=16, slots_per_pass=None, bgr=False):
+    """``images_reference`` with ``tiled_many_x8_reference`` in the middle: the same look-up-table division on the way
+    in, the self-ensemble's fp32 mean per window, the same ``(y.clamp(0, 1) * 255.0).round()`` on the way out — the
+    quantisation of ``tiled_many_x8_reference``'s floats."""
+    images = _images_u8(images)
+    lut = torch.arange(256, dtype=torch.float32) / 255.0
+    xs = [lut.to(x.device)[(x.flip(2) if bgr else x).permute(2, 0, 1).long()] for x in images]
+    ys = tiled_many_x8_reference(fn, xs, tile, pad, windows_per_pass, slots_per_pass)
+    outs = [(y.clamp(0, 1) * 255.0).round().to(torch.uint8).permute(1, 2, 0) for y in ys]
+    return [(o.flip(2) if bgr else o).contiguous() for o in outs]
+
+
+def run_rrdbnet_images(net, images, tile=96, pad=16, windows_per_pass=16, bgr=False, x8=False, slots_per_pass=None):
     """``run_rrdbnet_tiled_many`` with 8-bit ends: ``images`` is a sequence of ``torch.uint8`` tensors [H, W, 3] (HWC, as
     PIL and cv2 hold an image), of any sizes, on one GPU -> a list of fresh uint8 device tensors [4H, 4W, 3], in input
     order, without gradient; an empty list gives [].  ``bgr=False``: R, G, B in memory on both ends (PIL); ``bgr=True``:
@@ -939,8 +1077,13 @@ def run_rrdbnet_images(net, images, tile=96, pad=16, windows_per_pass=16, bgr=Fa
     the current stream without a device synchronisation.  Bit-identical to ``images_reference(net, ...)`` and to
     ``device_tensor2img`` of ``run_rrdbnet_tiled_many``'s results.  Noise is off whatever ``net.training`` is; the
     module's mode and every ``requires_grad`` are left untouched.
-    Out of scope: the x8 self-ensemble with 8-bit ends, scales other than 4, 16-bit or alpha images, CPU or numpy
-    inputs, blending."""
+    ``x8=True`` is the self-ensemble per window with the same 8-bit ends (``run_rrdbnet_tiled_many_x8``'s passes, with
+    ``slots_per_pass``; include/esrgan_hip.h: esr_tile_set_x8, img = 1): the gather-import divides, the last k range of
+    the stitch-reduce quantises the mean, and between the ranges the partial sums stay in an fp32 buffer of the plan, P
+    windows large (none when all eight slots run in one pass).  Keyed 'tiled_set_x8_img'; bit-identical to
+    ``images_x8_reference(net, ...)`` and to the quantisation of ``run_rrdbnet_tiled_many_x8``'s floats.
+    Out of scope: scales other than 4, 16-bit or alpha images, CPU or numpy inputs, blending."""
+    slots_per_pass = _x8_slots_arg(slots_per_pass, x8)
     tile, pad, wpp = _tiled_many_ints(tile, pad, windows_per_pass)
     images = _images_u8(images)
     if net.in_nc != 3 or net.out_nc != 3:
@@ -949,21 +1092,29 @@ def run_rrdbnet_images(net, images, tile=96, pad=16, windows_per_pass=16, bgr=Fa
     if not images:
         return []
     sizes = [(x.shape[0], x.shape[1]) for x in images]
-    tile, pad, groups, dev = _tiled_set_passes(sizes, [x.device for x in images], tile, pad, wpp)
+    if x8:
+        tile, pad, groups, dev = _tiled_set_x8_passes(sizes, [x.device for x in images], tile, pad, wpp, slots_per_pass)
+        kind, ends = 'tiled_set_x8_img', E.TileSetX8Ends
+    else:
+        tile, pad, groups, dev = _tiled_set_passes(sizes, [x.device for x in images], tile, pad, wpp)
+        kind, ends = 'tiled_img', E.TileImgEnds
     xin = [x.detach().contiguous() for x in images]
-    return _run_tiled_set(net, 'tiled_img', E.TileImgEnds, groups, xin, sizes, dev,
+    return _run_tiled_set(net, kind, ends, groups, xin, sizes, dev,
                           lambda H, W: torch.empty((4 * H, 4 * W, 3), dtype=torch.uint8, device=dev),
-                          tile=tile, pad=pad, bgr=1 if bgr else 0)
+                          img=bool(x8), tile=tile, pad=pad, bgr=1 if bgr else 0)
 
 
-def run_rrdbnet_evaluate(net, lr_images, hr_images, tile=96, pad=16, windows_per_pass=16, bgr=False, crop=None):
+def run_rrdbnet_evaluate(net, lr_images, hr_images, tile=96, pad=16, windows_per_pass=16, bgr=False, crop=None,
+                         x8=False, slots_per_pass=None):
     """codes/test.py:49-110 for one image set: ``run_rrdbnet_images`` on ``lr_images``, then
     ``metrics.device_set_metrics`` on its results against ``hr_images`` (uint8 [4H, 4W, 3] device tensors, one per LR
     image, channel order as ``bgr`` says) -> ``(sr_images, result)``: the uint8 results of ``run_rrdbnet_images`` and a
     ``metrics.SetMetricsResult`` whose ``read()`` gives (psnr, ssim, psnr_y, ssim_y) per image.  ``crop=None`` cuts
     ``net.upscale`` pixels from every side (test.py:75).  Sizes, types and the crop are checked before anything is
-    launched; everything is queued on the current stream and nothing synchronises before ``result.read()``."""
+    launched; everything is queued on the current stream and nothing synchronises before ``result.read()``.  ``x8`` and
+    ``slots_per_pass`` are ``run_rrdbnet_images``': the score of the self-ensemble."""
     from . import metrics as M
+    slots_per_pass = _x8_slots_arg(slots_per_pass, x8)
     lr, hr = _images_u8(lr_images), _images_u8(hr_images)
     if len(lr) != len(hr):
         raise ValueError('evaluate_images compares equally many images: %d lr, %d hr' % (len(lr), len(hr)))
@@ -975,5 +1126,5 @@ def run_rrdbnet_evaluate(net, lr_images, hr_images, tile=96, pad=16, windows_per
         if b.device != a.device:
             raise ValueError('hr image %d is on %s, its lr image on %s' % (i, b.device, a.device))
     crop = M._set_crop([(b.shape[0], b.shape[1]) for b in hr], s if crop is None else crop)
-    sr = run_rrdbnet_images(net, lr, tile, pad, windows_per_pass, bgr)
+    sr = run_rrdbnet_images(net, lr, tile, pad, windows_per_pass, bgr, x8, slots_per_pass)
     return sr, M.device_set_metrics(sr, hr, crop, bgr)

@@ -41,16 +41,19 @@ def _buffer_like(buf, ref):
     return buf
 
 
-def _validate(self, lr_images, hr_images, **tiling):
+def _validate(self, lr_images, hr_images, x8=False, **tiling):
     """The validation pass of codes/train.py:121-159 on one image set: ``finish()``, then the generator's
     ``evaluate_images(lr_images, hr_images, **tiling)`` — always the eval forward, the module's mode left as it is — ->
-    the average RGB PSNR as a float (train.py:148-150; cropped by the scale).  The per-image table (psnr, ssim, psnr_y,
-    ssim_y) stays on ``self.val_result``.  Valid between pipelined steps, as ``test()`` is; the read-back of the table is
-    the one synchronisation."""
+    the average RGB PSNR as a float (train.py:148-150; cropped by the scale).  ``x8=True`` scores the x8 self-ensemble
+    (``evaluate_images(x8=True)``, the reference's ``test_x8``).  The per-image table (psnr, ssim, psnr_y, ssim_y) stays
+    on ``self.val_result``.  Valid between pipelined steps, as ``test()`` is; the read-back of the table is the one
+    synchronisation."""
     self.finish()
     if not hasattr(self.netG, 'evaluate_images'):
         raise ValueError('validate needs a generator with evaluate_images (RRDBNet / RRDB_Net at x4), got %s'
                          % type(self.netG).__name__)
+    if x8:
+        tiling['x8'] = True
     self.val_result = self.netG.evaluate_images(lr_images, hr_images, **tiling)[1]
     return self.val_result.averages()[0]
 

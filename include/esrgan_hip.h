@@ -370,6 +370,56 @@ typedef struct esr_tile_img {
   int32_t bgr;                   /* C == 3: the channel order in memory is B, G, R on this op's side (else R, G, B) */
 } esr_tile_img;
 
+/* The x8 self-ensemble over an image SET: esr_tile_many's table-driven windows, each turned the eight ways of
+ * esr_tile_x8, with fp32 NCHW or 8-bit HWC images outside.  Geometry is esr_tile's per image, derived by the kernels from
+ * the item's H, W and this op's tile, pad; the table (esr_tile_item / esr_tile_img_item, the same 24 bytes) holds ONE
+ * entry per WINDOW p (0 <= p < n_windows), not per slot: the kernels run the k loop.  th x tw is the upright window every
+ * item has; the slots of k >= 4 are tw x th.  Transform k, ys, xs, the gather map and R_k are esr_tile_x8's.
+ * Batch entry of transform k of window p: (k - k_begin) n_windows + p — esr_tile_x8's index at B = 1.  A range may
+ * contain both k < 4 and k >= 4 only when th == tw (else ESR_ERR_INVALID).  C <= 8, with img C is 1 or 3, and
+ * k_count n_windows <= 65535, else ESR_ERR_UNSUPPORTED.  The table's guarantees are esr_tile_many's (img = 0) /
+ * esr_tile_img's (img = 1); this entry cannot read it.
+ *   to_g32 = 1, scale = 1  gather-import: every pixel of window p is read once — img = 0: C strided fp32 reads of
+ *               nchw [C][H][W]; img = 1: C bytes of hwc [H][W][C], float32(v) / 255.0f correctly rounded, channel
+ *               m(c) = 2 - c when bgr and C == 3 (esr_tile_img's arithmetic) — and written, converted to dtype, as a
+ *               finished 32-byte channel group to the logical pixel of every slot of the range in the G32 view (channels
+ *               >= C zero, the halo never touched).  `live` is not read: a filler window is gathered for every k.
+ *   to_g32 = 0, scale = 4  stitch-reduce: slots_nchw is fp32 [k_count * n_windows][C][4 th][4 tw] (k < 4) or
+ *               [...][4 tw][4 th] (k >= 4), 16-byte aligned.  For every HR pixel (Y, X) of the owned rectangle of every
+ *               window with live != 0, (y, x) = (Y - 4 wy, X - 4 wx) its window-local position:
+ *                 a = accumulate ? PARTIAL : 0;   a += R_k(o_k)[y][x] for k ascending, one fp32 add per k
+ *               img = 0: PARTIAL is the result itself, nchw [C][4H][4W] of the item:  nchw = a * mean_scale
+ *                        (esr_tile_x8's protocol: mean_scale = 1 before the last range, 0.125 on it).
+ *               img = 1: an 8-bit result cannot carry a partial sum.  PARTIAL is acc, fp32 [n_windows][C][4 th][4 tw],
+ *                        upright and window-local, element ((p C + c) 4 th + y) 4 tw + x, 16-byte aligned:
+ *                        k_begin + k_count < 8:   acc = a * mean_scale   (the result is not touched)
+ *                        k_begin + k_count == 8:  hwc[(Y 4W + X) C + m(c)] = uint8(rintf(fminf(fmaxf(a * mean_scale, 0), 1)
+ *                                                 * 255.0f))   (esr_tile_img's rounding; acc is not written)
+ *                        acc is read only with accumulate and written only before the last range: all eight slots in one
+ *                        pass never touch it, and it may then be null; else a null acc is ESR_ERR_INVALID.  The two
+ *                        plans of a non-square window shape share one acc.  The bytes of a row of a workgroup's 32
+ *                        pixels go out as aligned dwords (three per four pixels for C = 3, one for C = 1).
+ *               The result does not depend on how the eight slots are split.  Nothing outside the owned rectangles is
+ *               written; windows with live == 0 are neither read nor written (their acc entries included); g32 and
+ *               dtype's storage type are unused.                                                                       */
+typedef struct esr_tile_set_x8 {
+  int32_t dtype, to_g32;
+  int32_t C;
+  int32_t tile, pad;             /* LR pixels */
+  int32_t scale;                 /* 1: gather, 4: stitch */
+  int32_t th, tw;                /* the upright window shape every item has */
+  int32_t n_windows;             /* P: windows of the pass = table entries; batch entries = k_count * n_windows */
+  const esr_tile_item* items;    /* n_windows entries, device memory (img: esr_tile_img_item, the same layout) */
+  esr_g32 g32;
+  const float* slots_nchw;
+  int32_t k_begin, k_count;
+  int32_t accumulate;
+  float mean_scale;
+  int32_t img;                   /* 0: fp32 NCHW images outside, 1: uint8 HWC */
+  int32_t bgr;                   /* img, C == 3: B, G, R in memory on this op's side (else R, G, B) */
+  float* acc;                    /* img stitch-reduce: the partial sums between the ranges (see above) */
+} esr_tile_set_x8;
+
 /* Philox-4x32-7 + Box-Muller N(0,1) fill (csrc/common.h), NCHW fp32 — the exact z the fused noise epilogue uses for
  * (seed, layer); lets tests feed the same z to the oracle (GaussianNoise, block.py:117-122). */
 typedef struct esr_noise_fill {
@@ -852,7 +902,7 @@ enum esr_op_kind { ESR_OP_CONV = 1, ESR_OP_PACK = 2, ESR_OP_LAYOUT = 3, ESR_OP_N
                    ESR_OP_RDB_CHAIN = 11, ESR_OP_FRAG_GATHER = 12, ESR_OP_RDB_WGRAD = 13,
                    ESR_OP_RDB_CHAIN_BWD = 14 /* u.rdb_chain with mode 2 */, ESR_OP_DIHEDRAL = 15,
                    ESR_OP_TILE = 16, ESR_OP_TILE_X8 = 17, ESR_OP_FOLD3 = 18, ESR_OP_TILE_MANY = 19,
-                   ESR_OP_TILE_IMG = 20 };
+                   ESR_OP_TILE_IMG = 20, ESR_OP_TILE_SET_X8 = 21 };
 
 /* esr_op.flags */
 #define ESR_OPF_SIDE 1   /* on a run of consecutive ESR_OP_WGRAD ops: launch the run on the library's side
@@ -900,6 +950,7 @@ typedef struct esr_op {
     esr_fold3 fold3;
     esr_tile_many tile_many;
     esr_tile_img tile_img;
+    esr_tile_set_x8 tile_set_x8;
   } u;
 } esr_op;
 
@@ -917,6 +968,7 @@ int esr_tile_x8_op(const esr_tile_x8* p, esr_stream_t stream);     /* added unde
 int esr_fold3_op(const esr_fold3* p, esr_stream_t stream);         /* added under ABI 6: a pure addition */
 int esr_tile_many_op(const esr_tile_many* p, esr_stream_t stream); /* added under ABI 6: a pure addition */
 int esr_tile_img_op(const esr_tile_img* p, esr_stream_t stream);   /* added under ABI 6: a pure addition */
+int esr_tile_set_x8_op(const esr_tile_set_x8* p, esr_stream_t stream);   /* added under ABI 6: a pure addition */
 int esr_conv_wgrad(const esr_wgrad* p, esr_stream_t stream);
 /* n independent weight-gradient problems (disjoint dw/dbias blocks).  fp16 3x3/s1 and 1x1 entries are
  * packed, up to 8 at a time, into ONE launch (at training sizes a single conv's wgrad is ~64

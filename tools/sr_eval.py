@@ -1,13 +1,14 @@
 #!/usr/bin/env python
 """The reference's test script (``codes/test.py:49-110``) on the HIP path, with PIL instead of cv2:
 
-    python tools/sr_eval.py <model.pth|synthetic> <lr_dir> <hr_dir> [fp16|fp32] [--tile-u8 N[,PAD]] [--save out_dir]
+    python tools/sr_eval.py <model.pth|synthetic> <lr_dir> <hr_dir> [fp16|fp32] [--tile-u8 N[,PAD]] [--x8] [--save out_dir]
 
 The LR and HR images are paired by sorted base name (HR = 4 x LR; x4 only).  Images are queued as ``sr_infer.py
 --tile-u8`` queues them — until they hold at least 4 x 16 windows, or the folder ends — and every queue runs through
 ``model.evaluate_images(lr, hr, tile=N, pad=PAD)``: the 8-bit tiled forward over the set, then PSNR, SSIM, PSNR_Y and
 SSIM_Y of every result against its ground truth in one device pass, cropped by the scale; four doubles per image come
 back.  --tile-u8 defaults to 96,16.  Prints one line per image and the two average blocks in the reference's formats.
+--x8: the score of the x8 self-ensemble per window (the reference's ``test_x8``), ``evaluate_images(..., x8=True)``.
 --save out_dir: the results are written there as ``<name>.png``."""
 import glob
 import os
@@ -44,7 +45,8 @@ def paired_files(lr_dir, hr_dir):
 
 
 def main():
-    argv = sys.argv[1:]
+    argv = [a for a in sys.argv[1:] if a != '--x8']
+    x8 = '--x8' in sys.argv[1:]
     val = _option(argv, '--tile-u8')
     try:
         tiling = [int(v) for v in val.split(',')] if val is not None else [96, 16]
@@ -75,7 +77,7 @@ def main():
     def flush():
         try:
             with torch.no_grad():
-                sr, res = model.evaluate_images([q[1] for q in queue], [q[2] for q in queue], tile, pad)
+                sr, res = model.evaluate_images([q[1] for q in queue], [q[2] for q in queue], tile, pad, x8=x8)
         except ValueError as e:
             sys.exit('sr_eval.py: %s' % e)
         for (name, _, _), img, (psnr, ssim, psnr_y, ssim_y) in zip(queue, sr, res.read()):

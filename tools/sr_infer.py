@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Inference harness reproducing the reference's ``test_image/test.py`` (lines 9-40) on the HIP path
-with PIL instead of cv2:  python tools/sr_infer.py <model.pth|synthetic> <in_dir> <out_dir> [fp16|fp32] [--scale S] [--x8] [--tile N[,PAD]] [--tile-x8 N[,PAD]] [--tile-many N[,PAD]] [--tile-u8 N[,PAD]]
+with PIL instead of cv2:  python tools/sr_infer.py <model.pth|synthetic> <in_dir> <out_dir> [fp16|fp32] [--scale S] [--x8] [--tile N[,PAD]] [--tile-x8 N[,PAD]] [--tile-many N[,PAD]] [--tile-u8 N[,PAD]] [--tile-many-x8 N[,PAD]] [--tile-u8-x8 N[,PAD]]
 
 Per image: RGB /255 -> NCHW float32 -> RRDB_Net(3,3,64,23,...) -> clamp(0,1) -> *255 round -> PNG.
 --scale S (also --scale=S; 1, 2, 3, 4 or 8, default 4): the ``upscale`` the network is built with.
@@ -19,6 +19,9 @@ folder ends), run in one call and written; the output of each image is that of t
 ``model.forward_images(images, tile=N, pad=PAD)``: the 8-bit image goes to the device as it is and the 8-bit result comes
 back, the / 255 and the clamp, x 255, round run inside the gather and stitch kernels — the same arithmetic, no per-pixel
 numpy.  N >= the largest image side runs every image whole.  Not combined with --x8, --tile, --tile-x8 or --tile-many.
+--tile-many-x8 N[,PAD] / --tile-u8-x8 N[,PAD] (also with =): --tile-many / --tile-u8 with the x8 self-ensemble per window,
+``model.forward_tiled_many_x8(images, tile=N, pad=PAD)`` / ``model.forward_images(images, tile=N, pad=PAD, x8=True)``: the
+reference's best-quality result for a folder, the windows of different images sharing the passes.  Each by itself.
 The tiled forms are x4-only: with another --scale the script exits with the library's message."""
 import glob
 import os
@@ -35,7 +38,8 @@ from esrganplus_amd import architecture as arch, synth
 def main():
     argv = [a for a in sys.argv[1:] if a != '--x8']
     x8 = '--x8' in sys.argv[1:]
-    tiles = {'--tile': None, '--tile-x8': None, '--tile-many': None, '--tile-u8': None}
+    tiles = {'--tile': None, '--tile-x8': None, '--tile-many': None, '--tile-u8': None, '--tile-many-x8': None,
+             '--tile-u8-x8': None}
     for flag in tiles:
         for i, a in enumerate(argv):
             if a == flag or a.startswith(flag + '='):
@@ -68,15 +72,21 @@ def main():
     if tiled_u8 and (x8 or tiled or tiled_x8 or tiled_many):
         sys.exit('sr_infer.py: --tile-u8 is the 8-bit tiled forward over the folder by itself: it cannot be combined with '
                  '--x8, --tile, --tile-x8 or --tile-many')
+    for flag in ('--tile-many-x8', '--tile-u8-x8'):
+        if tiles[flag] and (x8 or sum(v is not None for v in tiles.values()) > 1):
+            sys.exit('sr_infer.py: %s is the self-ensemble over the folder by itself: it cannot be combined with --x8 or '
+                     'another --tile form' % flag)
+    set_x8 = tiles['--tile-many-x8'] or tiles['--tile-u8-x8']
     model_path, in_dir, out_dir = argv[0], argv[1], argv[2]
     prec = argv[3] if len(argv) > 3 else 'fp32'
     dev = torch.device('cuda')
     model = arch.RRDB_Net(3, 3, 64, 23, gc=32, upscale=scale, norm_type=None, act_type='leakyrelu',
                           mode='CNA', res_scale=1, upsample_mode='upconv')
-    if tiled or tiled_x8 or tiled_many or tiled_u8:
+    if tiled or tiled_x8 or tiled_many or tiled_u8 or set_x8:
         try:
             # the library's own refusal, before anything is loaded
-            model._x4_only('--tile-x8' if tiled_x8 else '--tile-many' if tiled_many else '--tile-u8' if tiled_u8 else '--tile')
+            model._x4_only('--tile-x8' if tiled_x8 else '--tile-many' if tiled_many else '--tile-u8' if tiled_u8 else
+                           '--tile-many-x8' if tiles['--tile-many-x8'] else '--tile-u8-x8' if tiles['--tile-u8-x8'] else '--tile')
         except ValueError as e:
             sys.exit('sr_infer.py: %s' % e)
     sd = synth.rrdbnet_state_dict(23, 0, upscale=scale) if model_path == 'synthetic' else torch.load(model_path, map_location='cpu')
@@ -90,6 +100,10 @@ def main():
         return run_tile_many(model, dev, in_dir, out_dir, *tiled_many)
     if tiled_u8:
         return run_tile_u8(model, dev, in_dir, out_dir, *tiled_u8)
+    if tiles['--tile-many-x8']:
+        return run_tile_many(model, dev, in_dir, out_dir, *tiles['--tile-many-x8'], x8=True)
+    if tiles['--tile-u8-x8']:
+        return run_tile_u8(model, dev, in_dir, out_dir, *tiles['--tile-u8-x8'], x8=True)
     for idx, path in enumerate(sorted(glob.glob(os.path.join(in_dir, '*'))), 1):
         base = os.path.splitext(os.path.basename(path))[0]
         img = np.array(Image.open(path).convert('RGB')).astype(np.float64) / 255
@@ -103,14 +117,14 @@ def main():
         print(idx, base, img.shape[:2], '->', out.shape[:2])
 
 
-def run_tile_many(model, dev, in_dir, out_dir, tile, pad=16):
+def run_tile_many(model, dev, in_dir, out_dir, tile, pad=16, x8=False):
     """--tile-many: the folder through ``forward_tiled_many`` in flushes of at least 4 x 16 windows; the same per-image
-    arithmetic, files and lines as the loop of ``main``."""
+    arithmetic, files and lines as the loop of ``main``.  x8: through ``forward_tiled_many_x8``."""
     queue, windows = [], 0
 
     def flush():
         with torch.no_grad():
-            ys = model.forward_tiled_many([x for _, _, _, x in queue], tile, pad)
+            ys = (model.forward_tiled_many_x8 if x8 else model.forward_tiled_many)([x for _, _, _, x in queue], tile, pad)
             outs = [y.data.squeeze().float().cpu().clamp_(0, 1).numpy() for y in ys]
         for (idx, base, shape, _), out in zip(queue, outs):
             out = (np.transpose(out, (1, 2, 0)) * 255.0).round().astype(np.uint8)
@@ -130,14 +144,14 @@ def run_tile_many(model, dev, in_dir, out_dir, tile, pad=16):
         flush()
 
 
-def run_tile_u8(model, dev, in_dir, out_dir, tile, pad=16):
+def run_tile_u8(model, dev, in_dir, out_dir, tile, pad=16, x8=False):
     """--tile-u8: run_tile_many's flushes through ``forward_images``; uint8 HWC up, uint8 HWC down, the same files and
-    lines."""
+    lines.  x8: ``forward_images(x8=True)``."""
     queue, windows = [], 0
 
     def flush():
         with torch.no_grad():
-            outs = [y.cpu().numpy() for y in model.forward_images([x for _, _, x in queue], tile, pad)]
+            outs = [y.cpu().numpy() for y in model.forward_images([x for _, _, x in queue], tile, pad, x8=x8)]
         for (idx, base, x), out in zip(queue, outs):
             Image.fromarray(out).save(os.path.join(out_dir, '%s_rlt.png' % base))
             print(idx, base, tuple(x.shape[:2]), '->', out.shape[:2])

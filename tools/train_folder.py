@@ -3,7 +3,7 @@
 decoded uint8 images stay on the device and every batch is one launch):
 
     python tools/train_folder.py HR_DIR [--lr-dir DIR] [--scale S] [--lr-size N] [--batch B] [--iters N] [--nb N]
-                                 [--precision fp16|fp32] [--seed K] [--out DIR] [--val LR_DIR HR_DIR] [--val-freq N]
+                                 [--precision fp16|fp32] [--seed K] [--out DIR] [--val LR_DIR HR_DIR] [--val-freq N] [--val-x8]
 
 HR_DIR: the HR images (sizes may differ; each is cut to a multiple of the scale with ``data.modcrop``, as the reference
 does for validation images — without --lr-dir the LR windows are resampled from them on the fly).  --lr-dir: the LR
@@ -49,6 +49,7 @@ def main():
     ap.add_argument('--out')
     ap.add_argument('--val', nargs=2, metavar=('LR_DIR', 'HR_DIR'))
     ap.add_argument('--val-freq', type=int, default=100)
+    ap.add_argument('--val-x8', action='store_true', help='score the x8 self-ensemble: validate(..., x8=True)')
     a = ap.parse_args()
     random.seed(a.seed)
     torch.manual_seed(a.seed)
@@ -80,7 +81,7 @@ def main():
             print('iter %d  l_pix %.6f' % (it, loss), flush=True)
             if val and it % a.val_freq == 0:
                 try:
-                    print('# Validation # PSNR: {:.4e}'.format(step.validate(*val)), flush=True)
+                    print('# Validation # PSNR: {:.4e}'.format(step.validate(*val, x8=a.val_x8)), flush=True)
                 except ValueError as e:
                     sys.exit('train_folder.py: --val: %s' % e)
             if it == a.iters:
