@@ -338,7 +338,7 @@ EXPORTS = ['esr_packed_weight_bytes', 'esr_g32_dims', 'esr_conv_forward', 'esr_p
            'esr_debug_mfma_probe', 'esr_debug_rdb_wgrad_follow', 'esr_dihedral_op', 'esr_tile_op',
            'esr_tile_x8_op', 'esr_l2_loss_forward', 'esr_fold3_op', 'esr_gan_loss_forward',
            'esr_batch_assemble', 'esr_tile_many_op', 'esr_tile_img_op', 'esr_image_set_metrics',
-           'esr_tile_set_x8_op']
+           'esr_tile_set_x8_op', 'esr_rdb_chain_check', 'esr_rdb_wgrad_check']
 
 _lib = None
 _lock = threading.Lock()
@@ -391,6 +391,8 @@ def lib():
         L.esr_debug_chain_force_general.argtypes = [C.c_int32]
         L.esr_rdb_wgrad_workspace_elems.restype = C.c_int64
         L.esr_rdb_wgrad_workspace_elems.argtypes = [C.c_int32] * 4
+        L.esr_rdb_chain_check.argtypes = [C.POINTER(esr_rdb_chain), C.c_void_p]       # (a host esr_rdb_block array or None)
+        L.esr_rdb_wgrad_check.argtypes = [C.POINTER(esr_rdb_wgrad), C.c_void_p]
         for name, st in (('esr_conv_forward', esr_conv), ('esr_pack_conv_weights', esr_pack),
                          ('esr_convert_layout', esr_layout), ('esr_fill_noise', esr_noise_fill),
                          ('esr_conv_wgrad', esr_wgrad), ('esr_batchnorm', esr_bn),

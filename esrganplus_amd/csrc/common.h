@@ -17,6 +17,15 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 void esr_set_error(const char* fmt, ...);
 int esr_check_launch(const char* what);
 
+// ---- address widths (DESIGN.md "Address widths"): what a launcher compares before it launches a kernel that forms
+// part of an address in 32 bits.  A plane is the esr_g32_dims(H, .) rows of one channel group at the view's pitch; an
+// image is the first ng groups of one batch entry, measured from the image base.
+#define ESR_OFFSET_LIMIT ((int64_t)1 << 31)
+inline int64_t esr_g32_plane_bytes(const esr_g32& v, int H) { return (int64_t)(((H + 31) / 32) * 32 + 6) * v.wp * 32; }
+inline int64_t esr_g32_image_bytes(const esr_g32& v, int H, int ng) {
+  return (int64_t)(ng > 1 ? ng - 1 : 0) * v.group_stride + esr_g32_plane_bytes(v, H);
+}
+
 template <typename T> struct DT;
 template <> struct DT<_Float16> {
   static constexpr int CPG = 16;   // channels per 32-byte group

@@ -852,6 +852,21 @@ __global__ __launch_bounds__(256) void s2_finish_kernel(const esr_conv p) {
   }
 }
 
+// rows of the map `in` holds for an op whose OUTPUT has p.H rows
+static int conv_in_rows(const esr_conv& p) { return p.upsample ? (p.H + 1) / 2 : p.H * (p.stride > 1 ? p.stride : 1); }
+
+// Packed tiles (PACK) reach the images of a tile through the 32-bit staging map: (bi - b) * (int)batch_stride + the
+// offset inside the plane.  Refused where that sum cannot be held.
+static bool pack_addressable(const esr_conv& p, int per_tile) {
+  const int n = per_tile < p.B ? per_tile : p.B;
+  const int64_t bs = p.in.batch_stride;
+  if (n <= 1 || (bs >= 0 && (n - 1) * bs + esr_g32_plane_bytes(p.in, conv_in_rows(p)) < ESR_OFFSET_LIMIT)) return true;
+  esr_set_error("conv: ksplit packs %d images into a tile and addresses them with 32-bit offsets from the first: "
+                "(images - 1) * in.batch_stride (%lld) + one plane must stay below 2^31 bytes — run the layer without ksplit",
+                n, (long long)bs);
+  return false;
+}
+
 // the transposed 4x4/s2 conv (esr_conv.upsample == 2: input gradient of those layers) on output maps of 8 / 16 / 32 columns
 template <typename T, int NCW>
 int launch_ts2_packed(const esr_conv& p, hipStream_t st) {
@@ -963,6 +978,7 @@ int dispatch(const esr_conv& p, hipStream_t st) {
         esr_set_error("conv: ksplit (transposed) needs a plain fp16 layer on an 8 / 16 / 32-column square output map");
         return ESR_ERR_UNSUPPORTED;
       }
+      if (!pack_addressable(p, (64 / p.W) * (p.H <= 8 ? 2 : 1))) return ESR_ERR_UNSUPPORTED;
       return cbk == 1 ? launch_ts2_packed<T, 1>(p, st) : launch_ts2_packed<T, 2>(p, st);
     }
     // several cout blocks: ONE per workgroup while that still leaves the grid below one workgroup per CU (the input
@@ -997,6 +1013,7 @@ int dispatch(const esr_conv& p, hipStream_t st) {
         esr_set_error("conv: ksplit needs a plain fp16 4x4/s2 layer on a 4 / 8 / 16-column square map");
         return ESR_ERR_UNSUPPORTED;
       }
+      if (!pack_addressable(p, (32 / p.W) * (p.H <= 4 ? 2 : 1))) return ESR_ERR_UNSUPPORTED;
       return launch_s2_packed<T>(p, st);
     }
     return launch<T, 4, 2, 0, 2, 1, 4, 1, false, false>(p, st);
@@ -1017,6 +1034,13 @@ extern "C" int esr_conv_forward(const esr_conv* p, esr_stream_t stream) {
   }
   if (p->mask.ptr && !p->out2.ptr) { esr_set_error("esr_conv_forward: mask without out2"); return ESR_ERR_INVALID; }
   if (p->stat_sums && p->ksplit <= 1) { esr_set_error("esr_conv_forward: stat_sums rides on the split-K finishing pass (ksplit > 1)"); return ESR_ERR_INVALID; }
+  // the staging map (conv_body: goff) addresses `in` inside one channel-group plane with 32-bit offsets; every other
+  // operand, and the image and group terms of `in`, are 64-bit
+  if (p->in.wp <= 0 || esr_g32_plane_bytes(p->in, conv_in_rows(*p)) >= ESR_OFFSET_LIMIT) {
+    esr_set_error("esr_conv_forward: a channel-group plane of `in` spans %lld bytes (wp %d): the kernels address a plane with "
+                  "32-bit offsets (limit 2^31 bytes)", (long long)esr_g32_plane_bytes(p->in, conv_in_rows(*p)), p->in.wp);
+    return ESR_ERR_UNSUPPORTED;
+  }
 
   hipStream_t st = (hipStream_t)stream;
   if (p->dtype == ESR_F16) return dispatch<_Float16>(*p, st);

@@ -246,6 +246,36 @@ extern "C" size_t esr_rdb_mask_bytes(int32_t B, int32_t H, int32_t W) {
 
 extern "C" int esr_rdb_max_tiles_per_image(void) { return num_cus_dev(); }
 
+// The chain kernels reach every channel group of an image through ONE buffer descriptor at the image base (img_view:
+// num_records 2^31 - 1) with 32-bit offsets, group * (int)group_stride + the offset inside the plane; a pixel past the
+// image is dropped by an offset of 2^31.  So the first ng groups of an image must end below 2^31 bytes from its base:
+// beyond that the range check drops the stores and answers the loads with 0 — no fault, a wrong result.
+static bool chain_view_ok(const char* name, int blk, const esr_g32& v, int ng, int H) {
+  if (!v.ptr) return true;
+  if (v.wp > 0 && v.group_stride >= 0 && esr_g32_image_bytes(v, H, ng) < ESR_OFFSET_LIMIT) return true;
+  esr_set_error("esr_rdb_chain: %s%s of block %d spans %lld bytes from the base of an image over its %d groups (group_stride %lld, "
+                "wp %d): the chain kernels address one image with 32-bit offsets (limit 2^31 bytes)", name, blk < 0 ? " (chain)" : "",
+                blk, (long long)esr_g32_image_bytes(v, H, ng), ng, (long long)v.group_stride, v.wp);
+  return false;
+}
+extern "C" int esr_rdb_chain_check(const esr_rdb_chain* p, const esr_rdb_block* blocks_host) {
+  if (!p || p->H <= 0 || p->n_blocks < 0) {
+    esr_set_error("esr_rdb_chain_check: invalid arguments");
+    return ESR_ERR_INVALID;
+  }
+  const int g32 = p->dtype == ESR_F16 ? 2 : 4;          // groups of 32 channels
+  if (p->mode == 0 && !chain_view_ok("dense", -1, p->dense, 4 * g32, p->H)) return ESR_ERR_UNSUPPORTED;
+  for (int k = 0; blocks_host && k < p->n_blocks; ++k) {
+    const esr_rdb_block& b = blocks_host[k];
+    if (!chain_view_ok("x_in", k, b.x_in, 2 * g32, p->H) || !chain_view_ok("x_out", k, b.x_out, 2 * g32, p->H) ||
+        !chain_view_ok("res2", k, b.res2, 2 * g32, p->H)) return ESR_ERR_UNSUPPORTED;
+    if (p->mode != 0 && !chain_view_ok("dense", k, b.dense, 4 * g32, p->H)) return ESR_ERR_UNSUPPORTED;
+    if (p->mode == 2 && (!chain_view_ok("aux", k, b.aux, g32, p->H) || !chain_view_ok("out_a", k, b.out_a, 2 * g32, p->H)))
+      return ESR_ERR_UNSUPPORTED;
+  }
+  return ESR_OK;
+}
+
 namespace {
 // ChainFollow (api.hip, follower weight gradients): `after_clear` is recorded on the stream between the clearing of the
 // workspace and the kernel launch — what polls the launch's flags from another stream waits for it, not for the launch;
@@ -265,6 +295,8 @@ int chain_launch(const esr_rdb_chain* p, esr_stream_t stream, const char* who, i
     esr_set_error("%s: the training forward / backward chains are fp16 (fp32 training runs the per-conv launches)", who);
     return ESR_ERR_UNSUPPORTED;
   }
+  // what this side can see of the views (the block table is device memory: esr_rdb_chain_check on its host copy)
+  if (const int rc = esr_rdb_chain_check(p, nullptr)) return rc;
   if (esr_rdb_check_abort()) {
     esr_set_error("%s: an earlier fused-chain launch aborted (a tile waited > 1 s for its neighbours: CUs held by other work?) — its results are invalid", who);
     return ESR_ERR_LAUNCH;

@@ -743,6 +743,33 @@ static int wgrad_cus() {
 
 static int rdb_wgrad_launch(const esr_rdb_wgrad* p, esr_stream_t stream, const uint32_t* follow, int f_tx, int f_ty, unsigned* host_abort);
 
+// The kernel reaches one image of `in` (192 channels) / `q` (224) through a buffer descriptor at the image base whose
+// num_records is the low 32 bits of batch_stride, with uint32 offsets group * group_stride + the offset inside the plane
+// and 0xFFFFFFF0 for the padding slots the range check must answer with zeros.  The offsets are formed in signed int
+// before the cast (and the row advance is an int), so an image's groups must end below 2^31 bytes from its base;
+// batch_stride must cover them and stay at or below 0xFFFFFFF0 (num_records).
+// The block table is device memory: the launcher cannot read it, this check runs on its host copy.
+extern "C" int esr_rdb_wgrad_check(const esr_rdb_wgrad* p, const esr_rdb_wgrad_block* blocks_host) {
+  if (!p || !blocks_host || p->n_blocks <= 0 || p->H <= 0) {
+    esr_set_error("esr_rdb_wgrad_check: invalid arguments");
+    return ESR_ERR_INVALID;
+  }
+  for (int k = 0; k < p->n_blocks; ++k) {
+    const esr_g32* const v[2] = {&blocks_host[k].in, &blocks_host[k].q};
+    const int ng[2] = {12, 14}, rows[2] = {p->H, p->H};
+    for (int i = 0; i < 2; ++i) {
+      const int64_t ext = esr_g32_image_bytes(*v[i], rows[i], ng[i]), bs = v[i]->batch_stride, gs = v[i]->group_stride;
+      if (v[i]->wp > 0 && gs >= 0 && ext < ESR_OFFSET_LIMIT && ext <= bs && bs <= 0xFFFFFFF0ll) continue;
+      esr_set_error("esr_rdb_wgrad: `%s` of block %d spans %lld bytes from the base of an image over its %d groups (group_stride "
+                    "%lld, batch_stride %lld, wp %d): the kernel addresses one image with 32-bit offsets (limit 2^31 bytes) inside "
+                    "batch_stride bytes (at most 2^32 - 16)", i ? "q" : "in", k, (long long)ext, ng[i], (long long)gs, (long long)bs,
+                    v[i]->wp);
+      return ESR_ERR_UNSUPPORTED;
+    }
+  }
+  return ESR_OK;
+}
+
 extern "C" int esr_rdb_wgrad_run(const esr_rdb_wgrad* p, esr_stream_t stream) { return rdb_wgrad_launch(p, stream, nullptr, 0, 0, nullptr); }
 
 // Follower form (api.hip: an ESR_OP_RDB_WGRAD op flagged ESR_OPF_FOLLOW right behind the ESR_OP_RDB_CHAIN_BWD op whose

@@ -570,8 +570,34 @@ Wg16Grid wgrad16_grid(const esr_wgrad& p, int64_t min_wgs, int min_rows, int cap
   return g;
 }
 
+// The fp16 kernels build their staging maps once, as 32-bit offsets from the base of an image that span its channel
+// groups (soff: group * group_stride + the offset inside the plane) and, on packed tiles, the images of a tile as well
+// (poff: image * batch_stride + ...).  Refused where those sums cannot be held; the fp32 kernel is 64-bit throughout.
+static bool wgrad16_addressable(const esr_wgrad& p) {
+  const bool ups = p.upsample != 0;
+  int more = 0;                                        // images past the first that one packed tile reaches
+  if (!ups && (p.stride == 2 ? wgrad16_packed<2, false>(p) : wgrad16_packed<1, false>(p))) {
+    const int ipt = 32 >> (p.stride == 2 ? pack_wl<2>(p.W) : pack_wl<1>(p.W));
+    more = (ipt < p.B ? ipt : p.B) - 1;
+  }
+  const esr_g32* const v[2] = {&p.g, &p.in};
+  const int rows[2] = {p.H, ups ? (p.H + 1) / 2 : p.H * (p.stride > 1 ? p.stride : 1)};
+  for (int i = 0; i < 2; ++i) {
+    const int64_t gs = v[i]->group_stride, bs = v[i]->batch_stride;
+    if (v[i]->wp > 0 && gs >= 0 && (more == 0 || bs >= 0) &&
+        more * bs + esr_g32_image_bytes(*v[i], rows[i], v[i]->ngroups) < ESR_OFFSET_LIMIT) continue;
+    esr_set_error("wgrad: `%s` spans %lld bytes from the base of an image over its %d groups%s (group_stride %lld, batch_stride "
+                  "%lld, wp %d): the fp16 kernels address one image with 32-bit offsets (limit 2^31 bytes)", i ? "in" : "g",
+                  (long long)(more * bs + esr_g32_image_bytes(*v[i], rows[i], v[i]->ngroups)), v[i]->ngroups,
+                  more ? " and the images of a packed tile" : "", (long long)gs, (long long)bs, v[i]->wp);
+    return false;
+  }
+  return true;
+}
+
 template <int KS, int S, bool UPS, int T0, int NT>
 int launch_wgrad16(const esr_wgrad& p_in, hipStream_t st, bool reduce = true) {
+  if (!wgrad16_addressable(p_in)) return ESR_ERR_UNSUPPORTED;
   const Wg16Grid g = wgrad16_grid<S, UPS>(p_in, 64, 8, max_rows());
   dim3 grid(g.gx, g.gy, g.gz);
   esr_wgrad p = p_in;
@@ -742,6 +768,9 @@ static bool wgrad_batchable(const esr_wgrad& p) {
 
 extern "C" int esr_conv_wgrad_multi(const esr_wgrad* items, int32_t n, esr_stream_t stream) {
   if (!items || n <= 0) { esr_set_error("esr_conv_wgrad_multi: invalid arguments"); return ESR_ERR_INVALID; }
+  // the address limits of every fp16 item, before the first launch of the list
+  for (int k = 0; k < n; ++k)
+    if (items[k].dtype == ESR_F16 && items[k].g.ptr && items[k].in.ptr && !wgrad16_addressable(items[k])) return ESR_ERR_UNSUPPORTED;
   int i = 0;
   while (i < n) {
     // greedily pack consecutive batchable entries; anything else goes through the single launch

@@ -39,9 +39,11 @@ class G32:
         self.Hp, self.Wp = L.g32_dims(H, W)
         # The kernels add the image's byte offset (b * batch_stride) in 64 bits, but inside an image some offsets are
         # 32-bit: the conv kernels' staging map inside one channel-group plane (conv_mfma.hip: goff), the fp16
-        # weight-gradient kernel's across the groups of one image (wgrad.hip: soff / poff = group * group_stride + ...).
-        # Refused here, before anything is allocated: a plane (every plan) or — image_limit, the training plans, whose
-        # buffers the weight-gradient kernels read — one image's extent of OFFSET_LIMIT bytes or more.
+        # weight-gradient kernel's across the groups of one image (wgrad.hip: soff / poff = group * group_stride + ...),
+        # the fused chains' likewise (rdb_chain_kernel.h: one buffer descriptor per image).  DESIGN.md 2a has the table.
+        # Refused here, before anything is allocated: a plane (every plan) or — image_limit: the training plans, whose
+        # buffers the weight-gradient kernels read, and the banded trunk's tall buffers (band_buffers) — one image's
+        # extent of OFFSET_LIMIT bytes or more.
         extent = (self.ng if image_limit else 1) * self.Hp * self.Wp * 32
         if extent >= OFFSET_LIMIT:
             raise ValueError('a %d-channel %s buffer of %d x %d pixels spans %d bytes per %s: the kernels address %s with '
@@ -111,6 +113,18 @@ def rdb_band_geometry(H, W):
     n = (H + 16 * t - 1) // (16 * t)
     rows = ((H + n - 1) // n + 15) // 16 * 16
     return rows, margin, n
+
+
+def band_buffers(B, geom, W, dtype, device):
+    """The buffers of the banded trunk (Builder.rdb_chain_banded): two `tall` 64-channel images with band_margin rows of
+    padding above and below, and the band-local block output and dense scratch.  A band's views keep the tall buffer's
+    group stride, and the chain kernels reach the groups of a band through one buffer descriptor with 32-bit offsets
+    (include/esrgan_hip.h, esr_g32): the tall buffers take the per-image limit, so a tall, narrow image whose four
+    planes pass 2^31 bytes is refused here instead of losing the stores of its last groups."""
+    S, m, nbands = geom
+    hb = S + 2 * m
+    tall = [G32(B, 64, nbands * S + 2 * m, W, dtype, device, image_limit=True) for _ in range(2)]
+    return tall, G32(nbands, 64, hb, W, dtype, device), G32(nbands, 128, hb, W, dtype, device)
 
 
 def _conv(dtype_e, B, H, W, src, src_ch, dst, cw, act=L.ACT_NONE, ks=None, stride=1, upsample=0):
@@ -520,6 +534,7 @@ class Builder:
 
     def upload(self, table):
         t = upload_table(table, self.device)
+        t.host_table = table          # what the launchers cannot read: chain() checks the views' address limits on it
         self.bufs.append(t)
         return t
 
@@ -620,6 +635,10 @@ class Builder:
         ch.workspace, ch.workspace_bytes = ws[0].data_ptr(), ws[1]
         if bands is not None:
             ch.band_rows, ch.band_margin, ch.img_H = bands
+        host = getattr(blk_t, 'host_table', None)
+        if host is not None:      # the block table is device memory to the launcher: its views are checked here
+            L.check(L.lib().esr_rdb_chain_check(ch, C.addressof(host) + k0 * C.sizeof(L.esr_rdb_block)),
+                    'esr_rdb_chain_check')
         return ch
 
     def rdb_chain(self, specs):
@@ -659,9 +678,7 @@ class Builder:
         S, m, nbands = geom
         hb = S + 2 * m
         B, H, W, nb = self.B, self.H, self.W, self.nb
-        tall = [G32(B, 64, nbands * S + 2 * m, W, self.dtype, self.device) for _ in range(2)]
-        mid = G32(nbands, 64, hb, W, self.dtype, self.device)
-        dense = G32(nbands, 128, hb, W, self.dtype, self.device)
+        tall, mid, dense = band_buffers(B, geom, W, self.dtype, self.device)
         self.bufs.extend(tall + [mid, dense])
         prefixes = ['model.1.sub.%d.RDB%d' % (i, j + 1) for i in range(nb) for j in range(3)]
         P.streams = RdbStreams(self.wp, prefixes)
@@ -1445,9 +1462,12 @@ class TrainBuilder(Builder):
         rw = L.esr_rdb_wgrad()
         rw.dtype, rw.B, rw.H, rw.W = self.dt_e, self.B, self.H, self.W
         rw.n_blocks, rw.tap_major, rw.scale5, rw.scale = len(grp), 1, 0.2, 1.0
-        rw.blocks = self.upload((L.esr_rdb_wgrad_block * len(grp))(*grp)).data_ptr()
+        table = (L.esr_rdb_wgrad_block * len(grp))(*grp)
+        rw.blocks = self.upload(table).data_ptr()
         rw.partial, rw.partial_elems = arena.data_ptr(), arena.numel()
         rw.max_workgroups = max_wg
+        # the block table is device memory to the launcher: its address limits are checked here, on the host copy
+        L.check(L.lib().esr_rdb_wgrad_check(rw, C.addressof(table)), 'esr_rdb_wgrad_check')
         return self.bwd.add(L.OP_RDB_WGRAD, 'rdb_wgrad', rw, flags=flags)
 
     def bwd_index(self, i, j):

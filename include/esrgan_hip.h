@@ -39,7 +39,25 @@ enum esr_dtype { ESR_F16 = 0, ESR_F32 = 1 };
 enum esr_act { ESR_ACT_NONE = 0, ESR_ACT_LRELU = 1 /* slope 0.2, block.py:12 */, ESR_ACT_RELU = 2 };
 enum esr_noise { ESR_NOISE_OFF = 0, ESR_NOISE_PHILOX = 1, ESR_NOISE_EXPLICIT = 2 };
 
-/* One G32 tensor view (pointer already offset to the first channel group of interest). */
+/* One G32 tensor view (pointer already offset to the first channel group of interest).
+ * Address widths (DESIGN.md "Address widths" has the table).  Every kernel forms b * batch_stride in 64 bits, so
+ * batch_stride itself is free except where noted.  With plane(H) = esr_g32_dims(H).Hp * wp * 32 bytes and
+ * image(n, H) = (n - 1) * group_stride + plane(H) — the first n groups of one batch entry, from its base — the
+ * launchers refuse, with ESR_ERR_UNSUPPORTED and a message naming the limit, before anything runs:
+ *   esr_conv_forward             `in`: plane(input rows) < 2^31 (32-bit staging map inside a plane).  Every other view
+ *                                of esr_conv is addressed in 64 bits: no limit.  With ksplit > 1 (packed tiles) also
+ *                                (images of a tile - 1) * in.batch_stride + plane < 2^31.
+ *   esr_conv_wgrad[_multi] fp16  `g` and `in`: image(view.ngroups, rows) < 2^31; packed tiles (maps of <= 16 columns)
+ *                                also + (images of a tile - 1) * batch_stride.  The fp32 kernel has no limit.
+ *   esr_rdb_forward / _backward  every view: group_stride >= 0 and image(64 / 128 / 32 channels' groups, H) < 2^31
+ *                                (one buffer descriptor per image, 32-bit offsets; beyond it the hardware range check
+ *                                drops stores and answers loads with 0 — a wrong result, no fault).  The launcher
+ *                                checks esr_rdb_chain.dense; the block table is DEVICE memory, so the caller runs
+ *                                esr_rdb_chain_check on its host copy (engine.py does before every upload).
+ *   esr_rdb_wgrad_run            `in` (12 groups) and `q` (14): image < 2^31 (offsets formed in int), and
+ *                                image <= batch_stride <= 2^32 - 16 (it is the descriptor's size).  Device table again: esr_rdb_wgrad_check on the host copy.
+ * The BatchNorm / pooling / pixel-shuffle kernels, esr_convert_layout and the image ends (dihedral, tile ops) add
+ * 64-bit products only: no limit. */
 typedef struct esr_g32 {
   void* ptr;
   int64_t batch_stride; /* bytes */
@@ -827,9 +845,12 @@ typedef struct esr_rdb_chain {
   int32_t _pad2;
   /* Row bands (mode 0, noise off): an image with more 16x32 tiles than CUs cannot run as one chain (a tile spins on
    * its neighbours, so all tiles of an image must be resident).  It is cut into bands of `band_rows` rows and the
-   * bands take the place of the batch: B = number of bands, H = band_rows + 2 * band_margin, every view's
-   * batch_stride = band_rows rows, and view row 0 of band b is image row b * band_rows - band_margin (the caller's
-   * buffers carry band_margin rows of zero padding above and below the image).  A band recomputes band_margin rows
+   * bands take the place of the batch: B = number of bands, H = band_rows + 2 * band_margin.  A view of the IMAGE (the
+   * chain's input, its result, a res2 that is the image) has batch_stride = band_rows rows, and its row 0 of band b is
+   * image row b * band_rows - band_margin (the caller's buffers carry band_margin rows of zero padding above and
+   * below the image).  A view that lives only inside the launch — the outputs of the blocks in between, the dense
+   * scratch — is band-local: one entry of H rows per band at any batch_stride (engine.py: a G32 of B = bands); the
+   * kernels form b * batch_stride in 64 bits, and an image of many bands takes it past 2^32.  A band recomputes band_margin rows
    * of its neighbours on either side — band_margin >= 5 * n_blocks, the chain's dependency radius — and the kernel
    * writes only rows that exist in the image (0 <= row < img_H), and into an ESR_RDB_BAND_OWN block's x_out only the
    * band's own rows.  band_rows = 0: off. */
@@ -853,7 +874,7 @@ typedef struct esr_frag_gather {
  *   in = [x (64) | x1 | x2 | x3 | x4] (192 channels),   q = [g_t (64) | g_a4 | g_a3 | g_a2 | g_a1 | g_x2] (224 channels)
  *   dW_convk += g_ak (x) in[0 : 32 (k + 1))  (3x3; conv5: g_a5 = scale5 * g_t),  dW_1x1 += g_x2 (x) x,  db_k += sum g_ak
  * where g_x2 is the gradient of x2 BEFORE its LeakyReLU mask (it feeds the bias-free 1x1, block.py:263).
- * Both views share one geometry (wp, H, W); one image of either must be < 4 GB.  dw[k]: k = 0..4 conv1..conv5 ([cout][cin][3][3] fp32, or tap-major
+ * Both views share one geometry (wp, H, W); one image of either must be < 2 GB (see esr_g32).  dw[k]: k = 0..4 conv1..conv5 ([cout][cin][3][3] fp32, or tap-major
  * [tap][cout][cin] when tap_major; accumulated: +=), k = 5 the 1x1 ([32][64]); db[k] k = 0..4 (NULL: skipped). */
 typedef struct esr_rdb_wgrad_block {
   esr_g32 in;               /* the block's saved concat buffer (forward) */
@@ -993,6 +1014,11 @@ int esr_rdb_forward(const esr_rdb_chain* p, esr_stream_t stream);
  * block.py:260-268,287-291, triggered at SRRaGAN_model.py:140) in one persistent launch — replaces 5 x n_blocks dgrad
  * launches; the weight gradients follow with esr_rdb_wgrad_run over the Q buffers this launch leaves complete. */
 int esr_rdb_backward(const esr_rdb_chain* p, esr_stream_t stream);
+/* Host-side address check of a chain launch (see esr_g32): every view the kernels would reach must keep the groups of
+ * one image below 2^31 bytes from the image base.  blocks_host: a HOST copy of the n_blocks entries p->blocks names on
+ * the device, or NULL to check esr_rdb_chain's own views only (what esr_rdb_forward / esr_rdb_backward do themselves).
+ * Launches nothing.  ESR_OK, or ESR_ERR_UNSUPPORTED with the view and the limit in esr_last_error(). */
+int esr_rdb_chain_check(const esr_rdb_chain* p, const esr_rdb_block* blocks_host);
 size_t esr_rdb_mask_bytes(int32_t B, int32_t H, int32_t W);   /* esr_rdb_block.mask of one block */
 /* Sticky abort report: 1 if a chain launch — or a follower pass of weight gradients (ESR_OPF_FOLLOW) waiting for one —
  * since the last call gave up on a bounded spin (its results are invalid; e.g. another kernel held CUs for > 1 s), else 0.  Reads a pinned host word: no synchronisation, but only meaningful
@@ -1043,6 +1069,9 @@ int esr_rdb_max_tiles_per_image(void);   /* 16x32 tiles of ONE image must not ex
 int esr_gather_fragments(const esr_frag_gather* g, esr_stream_t stream);
 /* Dense-block weight gradients (replaces 6 x n_blocks esr_conv_wgrad calls). */
 int esr_rdb_wgrad_run(const esr_rdb_wgrad* p, esr_stream_t stream);
+/* Host-side address check of esr_rdb_wgrad_run on a HOST copy of its block table (see esr_g32): one image of `in` / `q`
+ * must end below 2^31 bytes from its base and inside batch_stride, which is at most 2^32 - 16.  Launches nothing. */
+int esr_rdb_wgrad_check(const esr_rdb_wgrad* p, const esr_rdb_wgrad_block* blocks_host);
 int64_t esr_rdb_wgrad_workspace_elems(int32_t B, int32_t H, int32_t W, int32_t n_blocks);
 int esr_image_metrics(const esr_img_metrics* p, esr_stream_t stream);   /* replaces util.py:71-158 on the device */
 int esr_image_set_metrics(const esr_set_metrics* p, esr_stream_t stream);   /* added under ABI 6: a pure addition; test.py:69-110 over an image set */
