@@ -27,6 +27,7 @@ OP_FOLD3 = 18
 OP_TILE_MANY = 19
 OP_TILE_IMG = 20
 OP_TILE_SET_X8 = 21
+OP_TILE_HR = 22
 CHAIN_VARIANT_REGULAR, CHAIN_VARIANT_TRACED = 1, 2     # esr_debug_chain_last_variant (| rows per wave << 8)
 BN_STATS, BN_FINALIZE, BN_APPLY, BN_BWD_REDUCE, BN_BWD_FINAL, BN_BWD_APPLY, BN_RESTAT, BN_FIN_APPLY = 0, 1, 2, 3, 4, 5, 6, 7
 NO_LAYER = 0xFFFFFFFF
@@ -123,6 +124,27 @@ class esr_tile_img_item(C.Structure):
 
 class esr_tile_img(C.Structure):
     _fields_ = esr_tile_many._fields_ + [('bgr', C.c_int32)]
+
+
+TILE_HR_SPAN = 77                    # ESR_TILE_HR_SPAN: the source columns an LDS row of esr_tile_hr's gather holds
+
+
+class esr_tile_hr_desc(C.Structure):
+    """One image of esr_tile_hr's gather: a 64-byte entry in DEVICE memory (the HR bytes, their row pitch in pixels, the
+    modcropped size and the two bicubic tables, as esr_batch_item has them)."""
+    _fields_ = [('hr', C.c_void_p), ('wy', C.c_void_p), ('iy', C.c_void_p), ('wx', C.c_void_p), ('ix', C.c_void_p),
+                ('pitch', C.c_int32), ('hr_h', C.c_int32), ('hr_w', C.c_int32), ('taps_y', C.c_int32), ('taps_x', C.c_int32),
+                ('_pad', C.c_int32)]
+
+
+class esr_tile_hr_item(C.Structure):
+    """One slot of one pass of esr_tile_hr: esr_tile_item's layout; the pointer names a descriptor (gather) or the uint8
+    HR result (stitch)."""
+    _fields_ = [('ptr', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32), ('t', C.c_int32), ('live', C.c_int32)]
+
+
+class esr_tile_hr(C.Structure):
+    _fields_ = list(esr_tile_img._fields_)
 
 
 class esr_tile_set_x8(C.Structure):
@@ -319,7 +341,7 @@ class _op_union(C.Union):
                 ('pack_batch', esr_pack_batch), ('rdb_chain', esr_rdb_chain), ('frag_gather', esr_frag_gather),
                 ('rdb_wgrad', esr_rdb_wgrad), ('dihedral', esr_dihedral), ('tile', esr_tile),
                 ('tile_x8', esr_tile_x8), ('fold3', esr_fold3), ('tile_many', esr_tile_many),
-                ('tile_img', esr_tile_img), ('tile_set_x8', esr_tile_set_x8)]
+                ('tile_img', esr_tile_img), ('tile_set_x8', esr_tile_set_x8), ('tile_hr', esr_tile_hr)]
 
 
 class esr_op(C.Structure):
@@ -338,7 +360,7 @@ EXPORTS = ['esr_packed_weight_bytes', 'esr_g32_dims', 'esr_conv_forward', 'esr_p
            'esr_debug_mfma_probe', 'esr_debug_rdb_wgrad_follow', 'esr_dihedral_op', 'esr_tile_op',
            'esr_tile_x8_op', 'esr_l2_loss_forward', 'esr_fold3_op', 'esr_gan_loss_forward',
            'esr_batch_assemble', 'esr_tile_many_op', 'esr_tile_img_op', 'esr_image_set_metrics',
-           'esr_tile_set_x8_op', 'esr_rdb_chain_check', 'esr_rdb_wgrad_check']
+           'esr_tile_set_x8_op', 'esr_rdb_chain_check', 'esr_rdb_wgrad_check', 'esr_tile_hr_op']
 
 _lib = None
 _lock = threading.Lock()
@@ -407,7 +429,7 @@ def lib():
                          ('esr_tile_x8_op', esr_tile_x8), ('esr_fold3_op', esr_fold3),
                          ('esr_batch_assemble', esr_batch), ('esr_tile_many_op', esr_tile_many),
                          ('esr_tile_img_op', esr_tile_img), ('esr_image_set_metrics', esr_set_metrics),
-                         ('esr_tile_set_x8_op', esr_tile_set_x8)):
+                         ('esr_tile_set_x8_op', esr_tile_set_x8), ('esr_tile_hr_op', esr_tile_hr)):
             getattr(L, name).argtypes = [C.POINTER(st), C.c_void_p]
         if L.esr_sizeof_op() != C.sizeof(esr_op):
             raise HipExtensionError('ABI mismatch: sizeof(esr_op) C=%d ctypes=%d'

@@ -11,7 +11,8 @@ import torch.nn as nn
 
 from . import block as B
 from .functional import (run_rrdbnet, run_rrdbnet_evaluate, run_rrdbnet_images, run_rrdbnet_tiled, run_rrdbnet_tiled_many,
-                         run_rrdbnet_tiled_many_x8, run_rrdbnet_tiled_x8, run_rrdbnet_x8)
+                         run_rrdbnet_tiled_many_x8, run_rrdbnet_tiled_x8, run_rrdbnet_x8, run_rrdbnet_evaluate_hr,
+                         run_rrdbnet_hr_images)
 
 
 SUPPORTED_UPSCALE = (1, 2, 3, 4, 8)
@@ -209,6 +210,28 @@ class _RRDBNetBase(B._PlannedModule):
         self._x4_only('evaluate_images')
         self._join_pending()
         return run_rrdbnet_evaluate(self, lr_images, hr_images, tile, pad, windows_per_pass, bgr, crop, x8, slots_per_pass)
+
+    def forward_hr_images(self, hr_images, tile=96, pad=16, windows_per_pass=16, bgr=False):
+        """``forward_images`` of the LR images the reference's dataset makes of ground-truth images alone
+        (LRHR_dataset.py:44-125 with ``dataroot_LR`` null: ``modcrop``, then the MATLAB-bicubic ``imresize`` of the float
+        image by 1 / 4, neither quantised nor clamped): ``hr_images`` is a sequence of ``torch.uint8`` tensors [H, W, 3]
+        of any sizes >= 4 a side on one GPU -> a list of fresh uint8 device tensors [4 (H // 4), 4 (W // 4), 3].  No LR
+        image is ever stored: the gather of every pass resamples its windows straight out of the HR bytes.  Always the
+        eval forward; ``self.training`` and ``requires_grad`` are left as they are.  Not offered: ``x8`` on this route,
+        scales other than 4, writing LR or Bic files.  See ``functional.run_rrdbnet_hr_images``."""
+        self._x4_only('forward_hr_images')
+        self._join_pending()
+        return run_rrdbnet_hr_images(self, hr_images, tile, pad, windows_per_pass, bgr)
+
+    def evaluate_hr_images(self, hr_images, tile=96, pad=16, windows_per_pass=16, bgr=False, crop=None):
+        """The reference's test script for a folder of ground-truth images alone: ``forward_hr_images(hr_images, ...)``,
+        then PSNR, SSIM, PSNR_Y and SSIM_Y of every result against its modcropped HR image in one device pass ->
+        ``(sr_images, result)`` as ``evaluate_images``.  These are the reference's numbers for ``dataroot_LR: null``;
+        stored 8-bit LR files give others.  Not offered: ``x8``, scales other than 4.  See
+        ``functional.run_rrdbnet_evaluate_hr``."""
+        self._x4_only('evaluate_hr_images')
+        self._join_pending()
+        return run_rrdbnet_evaluate_hr(self, hr_images, tile, pad, windows_per_pass, bgr, crop)
 
 
 class RRDBNet(_RRDBNetBase):

@@ -118,6 +118,7 @@ extern "C" int esr_run_ops(const esr_op* ops, int32_t n, esr_stream_t stream) {
       case ESR_OP_FOLD3: rc = esr_fold3_op(&ops[i].u.fold3, stream); break;
       case ESR_OP_TILE_MANY: rc = esr_tile_many_op(&ops[i].u.tile_many, stream); break;
       case ESR_OP_TILE_IMG: rc = esr_tile_img_op(&ops[i].u.tile_img, stream); break;
+      case ESR_OP_TILE_HR: rc = esr_tile_hr_op(&ops[i].u.tile_hr, stream); break;
       case ESR_OP_TILE_SET_X8: rc = esr_tile_set_x8_op(&ops[i].u.tile_set_x8, stream); break;
       case ESR_OP_WGRAD: {
         // consecutive weight-gradient ops are independent by construction (disjoint dW blocks, read

@@ -4,6 +4,7 @@
 // LR window resampled straight from the HR image with the whole image's MATLAB-bicubic tables.
 // Argument struct and index maps: include/esrgan_hip.h (esr_batch, esr_batch_item).  Plain loads, stores and VALU.
 #include "common.h"
+#include "resample_taps.h"
 
 namespace {
 
@@ -27,8 +28,6 @@ __device__ __forceinline__ float fetch(const void* img, int h, int w, int c, int
   if (FMT == 0) return ((const float*)img)[((int64_t)c * h + y) * w + x];
   return __fdiv_rn((float)((const uint8_t*)img)[((int64_t)y * w + x) * 3 + c], 255.0f);
 }
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // blockIdx = (tile, 0: the HR window / 1: the LR window, sample).  Every tile is cut in WINDOW coordinates (a, b) —
 // before the flips — and staged in the LDS; it is written out with consecutive lanes along the output's x, which for a
@@ -67,12 +66,8 @@ __global__ __launch_bounds__(BA_THREADS) void batch_assemble_kernel(const esr_ba
     // BA_SPAN; the clamps below keep any table inside the image and the LDS)
     if (threadIdx.x < BA_GEN) {
       const int o = clampi(it.x0 + b0 + (int)threadIdx.x, 0, it.lr_w - 1);
-      int lo = it.hr_w - 1, hi = 0;
-      for (int t = 0; t < it.taps_x; ++t) {
-        const int s = clampi(it.ix[(int64_t)o * it.taps_x + t], 0, it.hr_w - 1);
-        lo = s < lo ? s : lo;
-        hi = s > hi ? s : hi;
-      }
+      int lo, hi;
+      resample_col_span(it.ix + (int64_t)o * it.taps_x, it.taps_x, it.hr_w, lo, hi);
       span[threadIdx.x] = lo;
       span[BA_GEN + threadIdx.x] = hi;
     }
@@ -87,15 +82,9 @@ __global__ __launch_bounds__(BA_THREADS) void batch_assemble_kernel(const esr_ba
     for (int e = threadIdx.x; e < BA_GEN * ncol; e += BA_THREADS) {
       const int r = e / ncol, xs = e - r * ncol;
       const int o = clampi(it.y0 + a0 + r, 0, it.lr_h - 1);
-      const float* wy = it.wy + (int64_t)o * it.taps_y;
-      const int32_t* iy = it.iy + (int64_t)o * it.taps_y;
       float acc[3] = {0.f, 0.f, 0.f};
-      for (int t = 0; t < it.taps_y; ++t) {
-        const int sy = clampi(iy[t], 0, it.hr_h - 1);
-        const float wt = wy[t];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += wt * fetch<FMT>(it.hr, it.hr_h, it.hr_w, c, sy, c_lo + xs);
-      }
+      resample_h_taps(it.wy + (int64_t)o * it.taps_y, it.iy + (int64_t)o * it.taps_y, it.taps_y, it.hr_h,
+                      [&](int c, int sy) { return fetch<FMT>(it.hr, it.hr_h, it.hr_w, c, sy, c_lo + xs); }, acc);
 #pragma unroll
       for (int c = 0; c < 3; ++c) rows[(c * BA_GEN + r) * BA_SPAN + xs] = acc[c];
     }
@@ -104,15 +93,9 @@ __global__ __launch_bounds__(BA_THREADS) void batch_assemble_kernel(const esr_ba
     const int a = a0 + ly, b = b0 + lx;
     if (a < n && b < n) {
       const int o = clampi(it.x0 + b, 0, it.lr_w - 1);
-      const float* wx = it.wx + (int64_t)o * it.taps_x;
-      const int32_t* ix = it.ix + (int64_t)o * it.taps_x;
       float acc[3] = {0.f, 0.f, 0.f};
-      for (int t = 0; t < it.taps_x; ++t) {
-        const int xs = clampi(clampi(ix[t], 0, it.hr_w - 1) - c_lo, 0, BA_SPAN - 1);
-        const float wt = wx[t];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += wt * rows[(c * BA_GEN + ly) * BA_SPAN + xs];
-      }
+      resample_w_taps(it.wx + (int64_t)o * it.taps_x, it.ix + (int64_t)o * it.taps_x, it.taps_x, it.hr_w, c_lo, BA_SPAN,
+                      rows + ly * BA_SPAN, BA_GEN * BA_SPAN, acc);
 #pragma unroll
       for (int c = 0; c < 3; ++c) tile[(c * T + ly) * pitch + lx] = acc[c];
     }

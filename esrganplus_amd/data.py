@@ -84,6 +84,51 @@ def _axis_pass(x, axis, w, idx, out_len, stream):
 _TABLES = {}
 
 
+def device_tables(length, scale, dev, antialiasing=True):
+    """``resample_tables(length, scale)`` on the device ``dev``, cached per (length, scale): (weights, indices, out_len).
+    The cache is bounded; whoever hands the tables' addresses to a kernel keeps the tuple referenced until that work is
+    queued."""
+    key = (int(length), float(scale), bool(antialiasing), str(dev))
+    t = _TABLES.get(key)
+    if t is None:
+        w, idx, ol = resample_tables(length, scale, antialiasing)
+        t = (w.to(dev), idx.to(dev), ol)
+        if len(_TABLES) >= 64:            # (length, scale) pairs of a dataset are few; stay bounded anyway
+            _TABLES.clear()
+        _TABLES[key] = t
+    return t
+
+
+def table_resample(x, scale):
+    """``imresize(x, 1 / scale)`` of a [3, H, W] float32 tensor restated with torch on x's device: the tables of
+    ``resample_tables`` evaluated as sums over the taps, H pass then W pass (``batch_reference``'s generated LR)."""
+    wh, ih, _ = resample_tables(x.shape[1], 1.0 / scale)
+    ww, iw, _ = resample_tables(x.shape[2], 1.0 / scale)
+    wh, ih, ww, iw = wh.to(x.device), ih.to(x.device), ww.to(x.device), iw.to(x.device)
+    y = (x[:, ih.long(), :] * wh[None, :, :, None]).sum(2)
+    return (y[:, :, iw.long()] * ww[None, None, :, :]).sum(3)
+
+
+def table_resample_fused(x, scale):
+    """``table_resample`` with the kernels' arithmetic, so that the bits are theirs (``imresize`` on the device,
+    ``esr_batch_assemble``'s generated LR, esr_tile_hr's gather): per pass the taps in ascending order from acc = 0,
+    ``acc = fma(w[o][t], x[idx[o][t]], acc)`` — one rounding per tap.  The fused multiply-add is formed in float64, where
+    the product of two float32 values is exact; the sum is then rounded to float64 and to float32, which differs from
+    the one rounding of the hardware only where the float64 sum lands on a float32 tie, a 29-bit coincidence."""
+    def axis_pass(x, w, idx, dim):
+        acc = None
+        shape = [1, -1, 1] if dim == 1 else [1, 1, -1]
+        for t in range(w.shape[1]):
+            term = w[:, t].double().reshape(shape) * x.index_select(dim, idx[:, t].long()).double()
+            acc = (term if acc is None else term + acc.double()).float()
+        return acc
+
+    wh, ih, _ = resample_tables(x.shape[1], 1.0 / scale)
+    ww, iw, _ = resample_tables(x.shape[2], 1.0 / scale)
+    y = axis_pass(x.float(), wh.to(x.device), ih.to(x.device), 1)
+    return axis_pass(y, ww.to(x.device), iw.to(x.device), 2)
+
+
 def imresize(img, scale, antialiasing=True):
     """img: [C,H,W] or [N,C,H,W] float32 on the MI355X, range [0,1], not rounded (util.py:276-343)."""
     E.require_cuda(img, 'image')
@@ -91,17 +136,7 @@ def imresize(img, scale, antialiasing=True):
     x = (img.unsqueeze(0) if squeeze else img).contiguous().float()
     n, c, h, wd = x.shape
     dev, st = x.device, E.current_stream()
-    tabs = []
-    for length in (h, wd):
-        key = (length, float(scale), bool(antialiasing), str(dev))
-        t = _TABLES.get(key)
-        if t is None:
-            w, idx, ol = resample_tables(length, scale, antialiasing)
-            t = (w.to(dev), idx.to(dev), ol)
-            if len(_TABLES) >= 64:            # (length, scale) pairs of a dataset are few; stay bounded anyway
-                _TABLES.clear()
-            _TABLES[key] = t
-        tabs.append(t)
+    tabs = [device_tables(length, scale, dev, antialiasing) for length in (h, wd)]
     y = _axis_pass(x, 0, tabs[0][0], tabs[0][1], tabs[0][2], st)
     y = _axis_pass(y, 1, tabs[1][0], tabs[1][1], tabs[1][2], st)
     return y[0] if squeeze else y
@@ -428,10 +463,7 @@ def batch_reference(hr_images, lr_images, scale, lr_size, draws, bgr=False):
         return torch.from_numpy(np.ascontiguousarray(np.transpose(a.astype(np.float32) / np.float32(255.), (2, 0, 1))))
 
     def resample(x):
-        wh, ih, _ = resample_tables(x.shape[1], 1.0 / scale)
-        ww, iw, _ = resample_tables(x.shape[2], 1.0 / scale)
-        y = (x[:, ih.long(), :] * wh[None, :, :, None]).sum(2)
-        return (y[:, :, iw.long()] * ww[None, None, :, :]).sum(3)
+        return table_resample(x, scale)
 
     outl, outh = [], []
     whole = {}                                                        # the resample of an image used more than once

@@ -187,12 +187,14 @@ class PinnedRing:
             slot[0] = torch.empty(max(nbytes, 4096), dtype=torch.uint8).pin_memory()
         return slot
 
-    def upload(self, rec, device):
-        """The 1-D numpy array `rec` as a fresh uint8 device tensor: one non-blocking copy on the current stream."""
+    def upload(self, rec, device, out=None):
+        """The 1-D numpy array `rec` as a fresh uint8 device tensor: one non-blocking copy on the current stream.  `out`:
+        that tensor, allocated by a caller whose table holds addresses inside itself."""
         nbytes = rec.nbytes
         slot = self.slot(nbytes)
         slot[0].numpy()[:nbytes].view(rec.dtype)[:] = rec
-        table = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        table = torch.empty(nbytes, dtype=torch.uint8, device=device) if out is None else out
+        assert table.numel() == nbytes and table.dtype == torch.uint8 and table.is_contiguous()
         table.copy_(slot[0][:nbytes], non_blocking=True)
         if slot[1] is None:
             slot[1] = torch.cuda.Event()
@@ -467,6 +469,13 @@ class TileImgEnds(TileManyEnds):
     per_run = _both('tile', 'pad', 'bgr')
 
 
+class TileHrEnds(TileImgEnds):
+    """TileImgEnds whose gather makes the LR window itself, out of the 8-bit HR image through the whole image's bicubic
+    tables (esr_tile_hr: the gather's table entries name per-image descriptors); the stitch is esr_tile_img's."""
+
+    kind, field, struct = L.OP_TILE_HR, 'tile_hr', L.esr_tile_hr
+
+
 class TileSetX8Ends(TileManyEnds):
     """Image-set self-ensemble ends (esr_tile_set_x8) of a batch of slots x P windows: the gather-import of the transforms
     [k0, k0 + slots) of the P upright th x tw windows the pass's table names (the builder's H x W is tw x th for the
@@ -495,7 +504,8 @@ class TileSetX8Ends(TileManyEnds):
         return d
 
 
-ENDS_OF_KIND = {e.kind: e for e in (Ends, DihedralEnds, TileEnds, TileX8Ends, TileManyEnds, TileImgEnds, TileSetX8Ends)}
+ENDS_OF_KIND = {e.kind: e for e in (Ends, DihedralEnds, TileEnds, TileX8Ends, TileManyEnds, TileImgEnds, TileSetX8Ends,
+                                         TileHrEnds)}
 
 
 def set_nchw(op, ptr):

@@ -967,7 +967,7 @@ def _one_gpu(devices):
     return dev
 
 
-def _run_tiled_set(net, kind, ends, groups, xin, sizes, dev, new_out, img=False, **bound):
+def _run_tiled_set(net, kind, ends, groups, xin, sizes, dev, new_out, img=False, desc=None, **bound):
     """The passes ``groups`` (``tiled_many_passes``) of a tiled forward over the device images ``xin`` of the LR sizes
     ``sizes``, on the current stream -> the results, one ``new_out(H, W)`` per image.  One slot table for the call, the
     gather's entries of every pass of every group, then the stitch's (the 24-byte layout of esr_tile_item), uploaded
@@ -975,7 +975,9 @@ def _run_tiled_set(net, kind, ends, groups, xin, sizes, dev, new_out, img=False,
     (kind, S, th, tw, precision, generation) and bound to ``bound`` (tile, pad, ...); every pass runs it on its gather
     slice and its stitch slice.  Groups of ``tiled_many_x8_passes`` (th, tw, slots, P, passes) run the self-ensemble
     instead: the table holds one entry per WINDOW, the plan is keyed (kind, slots, P, th, tw, precision, generation) and
-    runs its ``x8_passes`` on every pass's slices between ``E.TileSetX8Ends``; ``img``: the images outside are 8-bit."""
+    runs its ``x8_passes`` on every pass's slices between ``E.TileSetX8Ends``; ``img``: the images outside are 8-bit.
+    ``desc``: a numpy record array with one descriptor per image (esr_tile_hr_desc) in the place of ``xin``: it travels
+    behind the slot table in the same copy, and the gather's entries name the descriptors' device addresses."""
     import numpy as np
     with E.StreamOrder.of(net).call():
         wp = net._weights(dev)
@@ -984,7 +986,8 @@ def _run_tiled_set(net, kind, ends, groups, xin, sizes, dev, new_out, img=False,
         n = len(flat)
         idx = np.fromiter((w[0] for w in flat), dtype=np.int64, count=n)
         rec = np.zeros(2 * n, dtype=_tile_item_dtype())
-        rec['nchw'][:n] = np.array([x.data_ptr() for x in xin], dtype=np.uint64)[idx]
+        if desc is None:
+            rec['nchw'][:n] = np.array([x.data_ptr() for x in xin], dtype=np.uint64)[idx]
         rec['nchw'][n:] = np.array([o.data_ptr() for o in outs], dtype=np.uint64)[idx]
         hw = np.array(sizes, dtype=np.int32)[idx]
         rec['H'][:n] = rec['H'][n:] = hw[:, 0]
@@ -995,7 +998,13 @@ def _run_tiled_set(net, kind, ends, groups, xin, sizes, dev, new_out, img=False,
         ring = rings.get(dev.index)
         if ring is None:
             ring = rings[dev.index] = E.PinnedRing()
-        table = ring.upload(rec, dev)
+        if desc is None:
+            table = ring.upload(rec, dev)
+        else:
+            # the device tensor first: the gather's entries hold addresses inside it
+            table = torch.empty(rec.nbytes + desc.nbytes, dtype=torch.uint8, device=dev)
+            rec['nchw'][:n] = (table.data_ptr() + rec.nbytes + idx * desc.dtype.itemsize).astype(np.uint64)
+            ring.upload(np.concatenate([rec.view(np.uint8), desc.view(np.uint8)]), dev, out=table)
         isz, stream, at = rec.dtype.itemsize, E.current_stream(), 0
         for th, tw, *per_pass, passes in groups:
             # no H, W in the key: whatever images have this window
@@ -1128,3 +1137,122 @@ def run_rrdbnet_evaluate(net, lr_images, hr_images, tile=96, pad=16, windows_per
     crop = M._set_crop([(b.shape[0], b.shape[1]) for b in hr], s if crop is None else crop)
     sr = run_rrdbnet_images(net, lr, tile, pad, windows_per_pass, bgr, x8, slots_per_pass)
     return sr, M.device_set_metrics(sr, hr, crop, bgr)
+
+
+# ---- a generator scored from HR images alone: the LR is made in the gather (include/esrgan_hip.h: esr_tile_hr) ---------
+def _hr_images(net, hr_images):
+    """The HR images of ``run_rrdbnet_hr_images`` as a list, checked without a device: what ``_images_u8`` refuses, HR
+    sides below 4, nets that are not 3 -> 3."""
+    images = _images_u8(hr_images)
+    for i, x in enumerate(images):
+        if x.shape[0] < 4 or x.shape[1] < 4:
+            raise ValueError('hr image %d of forward_hr_images is %d x %d: below 4 pixels a side there is no x4 LR image'
+                             % (i, x.shape[0], x.shape[1]))
+    if net.in_nc != 3 or net.out_nc != 3:
+        raise ValueError('forward_hr_images takes and gives 3-channel 8-bit images: this net has in_nc = %d, out_nc = %d'
+                         % (net.in_nc, net.out_nc))
+    return images
+
+
+def _hr_desc_dtype():
+    import ctypes as C
+    import numpy as np
+    from . import _lib as L
+    dt = np.dtype([(n, {C.c_void_p: '<u8', C.c_int32: '<i4'}[t]) for n, t in L.esr_tile_hr_desc._fields_], align=True)
+    assert dt.itemsize == C.sizeof(L.esr_tile_hr_desc) == 64
+    return dt
+
+
+def hr_lr_reference(hr_images, bgr=False):
+    """The two float images ``LRHRDataset.__getitem__`` makes of an HR image when ``dataroot_LR`` is null and the phase is
+    not 'train' (codes/data/LRHR_dataset.py:44-125), restated with torch on the images' device, per uint8 [H, W, 3]
+    image: ``data.modcrop(., 4)``, ``float32(v) / 255`` as a true division (the look-up table of ``images_reference``),
+    R, G, B order; the LR is the resample of ``data.batch_reference`` — the tables of ``data.resample_tables`` as sums
+    over the taps, H pass then W pass — in the kernels' order and rounding (``data.table_resample_fused``: taps
+    ascending, one fused multiply-add each; ``data.table_resample``'s products and torch's summation order round
+    differently in most values, by an ulp), not quantised and not clamped.
+    -> (lr [3, H // 4, W // 4] float32 list, hr [3, 4 (H // 4), 4 (W // 4)] float32 list)."""
+    from . import data as D
+    images = _images_u8(hr_images)
+    lut = torch.arange(256, dtype=torch.float32) / 255.0
+    hrs = [lut.to(x.device)[D.modcrop((x.flip(2) if bgr else x).permute(2, 0, 1), 4).long()] for x in images]
+    return [D.table_resample_fused(h, 4) for h in hrs], hrs
+
+
+def hr_images_reference(fn, hr_images, tile, pad, windows_per_pass=16, bgr=False):
+    """Pure-torch restatement of ``run_rrdbnet_hr_images`` and a x4 forward ``fn``, on any device: the LR images of
+    ``hr_lr_reference``, ``tiled_many_reference(fn, ...)`` on them, and ``images_reference``'s quantisation
+    ``(y.clamp(0, 1) * 255.0).round()`` -> uint8 [4 (H // 4), 4 (W // 4), 3] in the inputs' channel order."""
+    lrs, _ = hr_lr_reference(hr_images, bgr)
+    ys = tiled_many_reference(fn, lrs, tile, pad, windows_per_pass)
+    outs = [(y.clamp(0, 1) * 255.0).round().to(torch.uint8).permute(1, 2, 0) for y in ys]
+    return [(o.flip(2) if bgr else o).contiguous() for o in outs]
+
+
+def run_rrdbnet_hr_images(net, hr_images, tile=96, pad=16, windows_per_pass=16, bgr=False):
+    """``run_rrdbnet_images`` of the LR images the reference's dataset makes of ground-truth images alone
+    (codes/data/LRHR_dataset.py:44-125 with ``dataroot_LR`` null, phase 'val' / 'test': ``modcrop(HR, 4)``, then
+    ``imresize_np(HR, 1 / 4)`` on the float image — neither quantised nor clamped).  ``hr_images``: a sequence of
+    ``torch.uint8`` tensors [H, W, 3] of any sizes >= 4 a side on one GPU -> a list of fresh uint8 device tensors
+    [4 (H // 4), 4 (W // 4), 3], in input order, without gradient; an empty list gives [].  No LR image ever exists: the
+    gather of every pass (include/esrgan_hip.h: esr_tile_hr) cuts each window straight out of the HR bytes through the
+    whole image's MATLAB-bicubic tables — ``float32(v) / 255.0f`` per sample, H pass then W pass, taps ascending in fp32,
+    the bits of ``data.imresize(hr_float, 1 / 4)`` — and the stitch is ``run_rrdbnet_images``'.  A modcropped image is
+    read through its row pitch, not copied.  Windows, passes, filler, the grouping by window shape and the cutting of
+    tile / pad down to the largest LR image are ``run_rrdbnet_tiled_many``'s on the LR sizes; one plan per (S, window
+    shape, precision, weight generation), keyed 'tiled_hr' — no image size and no ``bgr`` in the key.  The per-image
+    descriptors (HR bytes, pitch, size, tables) go up behind the slot table in the same non-blocking copy; the tables are
+    cached on the device per (length, scale).  Everything runs on the current stream without a device synchronisation.
+    Bit-identical to ``metrics.device_tensor2img`` of ``run_rrdbnet_tiled_many`` on ``data.imresize`` of the float
+    images.  Refused before the device is touched: what ``run_rrdbnet_images`` refuses, HR sides below 4, nets that are
+    not 3 -> 3, more than one device, CPU tensors.
+    Not offered: the x8 self-ensemble on this route (there is no such keyword), scales other than 4, and writing LR or Bic
+    image files (the reference's scripts/generate_mod_LR_bic.py resamples 0..255 values and lets ``cv2.imwrite`` round:
+    other numbers than the dataset's)."""
+    import numpy as np
+    from . import data as D
+    tile, pad, wpp = _tiled_many_ints(tile, pad, windows_per_pass)
+    images = _hr_images(net, hr_images)
+    if not images:
+        return []
+    sizes = [(x.shape[0] // 4, x.shape[1] // 4) for x in images]
+    tile, pad, groups, dev = _tiled_set_passes(sizes, [x.device for x in images], tile, pad, wpp)
+    xin = [x.detach().contiguous() for x in images]
+    with torch.cuda.device(dev):
+        desc, tables = np.zeros(len(xin), dtype=_hr_desc_dtype()), []        # `tables` keeps them referenced until queued
+        for i, (x, (H, W)) in enumerate(zip(xin, sizes)):
+            (wy, iy, oh), (wx, ix, ow) = D.device_tables(4 * H, 0.25, dev), D.device_tables(4 * W, 0.25, dev)
+            assert (oh, ow) == (H, W) and wy.shape == iy.shape and wx.shape == ix.shape
+            tables.append((wy, iy, wx, ix))
+            d = desc[i]
+            d['hr'], d['pitch'], d['hr_h'], d['hr_w'] = x.data_ptr(), x.shape[1], 4 * H, 4 * W
+            d['wy'], d['iy'], d['taps_y'] = wy.data_ptr(), iy.data_ptr(), wy.shape[1]
+            d['wx'], d['ix'], d['taps_x'] = wx.data_ptr(), ix.data_ptr(), wx.shape[1]
+        outs = _run_tiled_set(net, 'tiled_hr', E.TileHrEnds, groups, None, sizes, dev,
+                              lambda H, W: torch.empty((4 * H, 4 * W, 3), dtype=torch.uint8, device=dev),
+                              desc=desc, tile=tile, pad=pad, bgr=1 if bgr else 0)
+    del tables, xin
+    return outs
+
+
+def _modcropped(images):
+    """The images cut to multiples of 4 a side: the image itself where nothing is cut, else a contiguous copy."""
+    return [x if (x.shape[0] % 4 == 0 and x.shape[1] % 4 == 0)
+            else x[:x.shape[0] - x.shape[0] % 4, :x.shape[1] - x.shape[1] % 4].contiguous() for x in images]
+
+
+def run_rrdbnet_evaluate_hr(net, hr_images, tile=96, pad=16, windows_per_pass=16, bgr=False, crop=None):
+    """codes/test.py:49-110 for a folder of ground-truth images alone: ``run_rrdbnet_hr_images``, then
+    ``metrics.device_set_metrics`` of its results against the modcropped HR images -> ``(sr_images, result)`` as
+    ``run_rrdbnet_evaluate``.  ``crop=None`` cuts ``net.upscale`` pixels from every side.  The set metric's items have
+    no row pitch: only the images that modcrop cuts are copied, cropped and contiguous, on the device.  Types, sizes and
+    the crop are checked before anything is launched; nothing synchronises before ``result.read()``.  These are the
+    reference's numbers for the HR-only configuration; ``run_rrdbnet_evaluate`` on stored 8-bit LR files gives others,
+    because a stored LR has been rounded.  Not offered: ``x8``, scales other than 4."""
+    from . import metrics as M
+    _tiled_many_ints(tile, pad, windows_per_pass)
+    images = _hr_images(net, hr_images)
+    crop = M._set_crop([(x.shape[0] - x.shape[0] % 4, x.shape[1] - x.shape[1] % 4) for x in images],
+                       net.upscale if crop is None else crop)
+    sr = run_rrdbnet_hr_images(net, images, tile, pad, windows_per_pass, bgr)
+    return sr, M.device_set_metrics(sr, _modcropped(images), crop, bgr)

@@ -58,6 +58,18 @@ def _validate(self, lr_images, hr_images, x8=False, **tiling):
     return self.val_result.averages()[0]
 
 
+def _validate_hr(self, hr_images, **tiling):
+    """``validate`` from ground-truth images alone (the reference's ``dataroot_LR: null``): ``finish()``, then the
+    generator's ``evaluate_hr_images(hr_images, **tiling)`` -> the average RGB PSNR as a float; the per-image table stays
+    on ``self.val_result``.  Valid between pipelined steps, as ``validate`` is.  Not offered: ``x8``."""
+    self.finish()
+    if not hasattr(self.netG, 'evaluate_hr_images'):
+        raise ValueError('validate_hr needs a generator with evaluate_hr_images (RRDBNet / RRDB_Net at x4), got %s'
+                         % type(self.netG).__name__)
+    self.val_result = self.netG.evaluate_hr_images(hr_images, **tiling)[1]
+    return self.val_result.averages()[0]
+
+
 def _check_channels(what, netG, netD, netF):
     """The generator's images are what the discriminator and the feature extractor read: their channel counts must
     agree before a step is built (the networks' plans take the first conv's channels on trust from their caller)."""
@@ -259,6 +271,7 @@ class ESRGANPlusStep:
         return {'optimizers': [self.optimizer_G.state_dict(), self.optimizer_D.state_dict()]}
 
     validate = _validate
+    validate_hr = _validate_hr
 
     def finish(self):
         """Orders what a pipelined step (``step(..., sync_log=False)``) left on the side stream — the end of the D
@@ -775,6 +788,7 @@ class PSNRStep:
             torch.cuda.current_stream().wait_event(self._ev_tail)
 
     validate = _validate
+    validate_hr = _validate_hr
 
     def state_dict(self):
         """The optimizer's state (base_model.py:65-74 `save_training_state`), behind whatever is still in flight."""
@@ -851,6 +865,7 @@ class SRGANStep:
     comm_report = ESRGANPlusStep.comm_report
     finish = ESRGANPlusStep.finish
     validate = _validate
+    validate_hr = _validate_hr
 
     @staticmethod
     def g_update_due(iteration, D_update_ratio=1, D_init_iters=0):

@@ -388,6 +388,60 @@ typedef struct esr_tile_img {
   int32_t bgr;                   /* C == 3: the channel order in memory is B, G, R on this op's side (else R, G, B) */
 } esr_tile_img;
 
+/* esr_tile_img whose gather makes the LR window itself: every slot's window is cut straight out of the 8-bit HR image
+ * through the MATLAB-bicubic tables of the WHOLE image (esr_resample's layout, for (hr_h, 1/4) and (hr_w, 1/4)), so that
+ * a generator is scored from ground-truth images alone (LRHR_dataset.py:44-125 with dataroot_LR null: modcrop,
+ * imresize_np(HR, 1/4) on the float image, not quantised, not clamped).  x4 only.  Fields, slots, th x tw, tile, pad,
+ * n_slots, the limits and the 24-byte table are esr_tile_img's; C is 3, else ESR_ERR_UNSUPPORTED.
+ *   to_g32 = 1, scale = 1  gather: an item's pointer names a per-image DESCRIPTOR in device memory (esr_tile_hr_desc,
+ *               64 bytes, 8-byte aligned); H, W of the item are the LR size (hr_h / 4, hr_w / 4), t and live as in
+ *               esr_tile_img.  A source sample is float32(byte) / 255.0f, one correctly rounded division; slot channel c
+ *               reads byte m(c) = 2 - c when bgr, else c, of pixel (Y, X) at hr[(Y pitch + X) 3 + m(c)] — pitch in
+ *               PIXELS, so a modcropped view of a larger image needs no copy.  LR pixel (wy + y, wx + x) is the H pass then
+ *               the W pass, each an fp32 sum over the taps in ascending order, acc += w * x — the bits of esr_resample_axis
+ *               run twice on the float image and of esr_batch_assemble's generated LR.  One workgroup makes one 16 x 16 LR
+ *               tile: the H pass of its rows over the source columns its 16 LR columns touch (at most ESR_TILE_HR_SPAN:
+ *               15 * 4 + the 17 taps of a x4 table, mirrored taps folding inside) into LDS, the W pass out of it.  Source
+ *               rows and columns are clamped into the image and the LDS row whatever the tables hold.  The result is
+ *               converted to dtype and written as esr_tile_img's gather writes: finished 32-byte channel groups at the
+ *               logical pixels of the G32 view, channels >= 3 zero, the halo never touched, filler slots filled like any
+ *               other.
+ *   to_g32 = 0, scale = 4  stitch: esr_tile_img's stitch itself (the same kernel): an item's pointer is the uint8 HR
+ *               result [4H][4W][3], 4-byte aligned.
+ * Items and descriptors live in device memory: this entry cannot check them (pointers, sizes, tables, alignment);
+ * functional.run_rrdbnet_hr_images builds them from validated sizes, and keeps the tables referenced until the call's
+ * work is queued.                                                                                                      */
+#define ESR_TILE_HR_SPAN 77          /* source columns staged per LDS row: 15 * 4 + 17 */
+typedef struct esr_tile_hr_desc {    /* one per image; lives in DEVICE memory */
+  const uint8_t* hr;                 /* uint8 [>= hr_h][pitch][3] */
+  const float* wy; const int32_t* iy;   /* [hr_h / 4][taps_y] weights / source rows */
+  const float* wx; const int32_t* ix;   /* [hr_w / 4][taps_x] weights / source columns */
+  int32_t pitch;                     /* pixels from one row to the next, >= hr_w */
+  int32_t hr_h, hr_w;                /* the modcropped HR size: multiples of 4 */
+  int32_t taps_y, taps_x;
+  int32_t _pad;
+} esr_tile_hr_desc;
+
+typedef struct esr_tile_hr_item {    /* esr_tile_item's layout; lives in DEVICE memory */
+  void* ptr;                         /* gather: const esr_tile_hr_desc*; stitch: uint8_t* HR result [4H][4W][3] */
+  int32_t H, W;                      /* LR size of that image (on both sides) */
+  int32_t t;                         /* tile index in that image's own ny x nx grid */
+  int32_t live;                      /* 0: a filler slot — the gather fills it, the stitch skips it */
+} esr_tile_hr_item;
+
+typedef struct esr_tile_hr {         /* esr_tile_img's fields */
+  int32_t dtype, to_g32;
+  int32_t C;                         /* 3 */
+  int32_t tile, pad;                 /* LR pixels */
+  int32_t scale;                     /* 1: gather, 4: stitch */
+  int32_t th, tw;                    /* the window shape every item has */
+  int32_t n_slots;                   /* batch entries = slots, one image per slot */
+  const esr_tile_hr_item* items;     /* n_slots entries, device memory */
+  esr_g32 g32;
+  const float* slots_nchw;
+  int32_t bgr;                       /* the channel order in memory is B, G, R on this op's side (else R, G, B) */
+} esr_tile_hr;
+
 /* The x8 self-ensemble over an image SET: esr_tile_many's table-driven windows, each turned the eight ways of
  * esr_tile_x8, with fp32 NCHW or 8-bit HWC images outside.  Geometry is esr_tile's per image, derived by the kernels from
  * the item's H, W and this op's tile, pad; the table (esr_tile_item / esr_tile_img_item, the same 24 bytes) holds ONE
@@ -923,7 +977,7 @@ enum esr_op_kind { ESR_OP_CONV = 1, ESR_OP_PACK = 2, ESR_OP_LAYOUT = 3, ESR_OP_N
                    ESR_OP_RDB_CHAIN = 11, ESR_OP_FRAG_GATHER = 12, ESR_OP_RDB_WGRAD = 13,
                    ESR_OP_RDB_CHAIN_BWD = 14 /* u.rdb_chain with mode 2 */, ESR_OP_DIHEDRAL = 15,
                    ESR_OP_TILE = 16, ESR_OP_TILE_X8 = 17, ESR_OP_FOLD3 = 18, ESR_OP_TILE_MANY = 19,
-                   ESR_OP_TILE_IMG = 20, ESR_OP_TILE_SET_X8 = 21 };
+                   ESR_OP_TILE_IMG = 20, ESR_OP_TILE_SET_X8 = 21, ESR_OP_TILE_HR = 22 };
 
 /* esr_op.flags */
 #define ESR_OPF_SIDE 1   /* on a run of consecutive ESR_OP_WGRAD ops: launch the run on the library's side
@@ -972,6 +1026,7 @@ typedef struct esr_op {
     esr_tile_many tile_many;
     esr_tile_img tile_img;
     esr_tile_set_x8 tile_set_x8;
+    esr_tile_hr tile_hr;
   } u;
 } esr_op;
 
@@ -990,6 +1045,7 @@ int esr_fold3_op(const esr_fold3* p, esr_stream_t stream);         /* added unde
 int esr_tile_many_op(const esr_tile_many* p, esr_stream_t stream); /* added under ABI 6: a pure addition */
 int esr_tile_img_op(const esr_tile_img* p, esr_stream_t stream);   /* added under ABI 6: a pure addition */
 int esr_tile_set_x8_op(const esr_tile_set_x8* p, esr_stream_t stream);   /* added under ABI 6: a pure addition */
+int esr_tile_hr_op(const esr_tile_hr* p, esr_stream_t stream);     /* added under ABI 6: a pure addition */
 int esr_conv_wgrad(const esr_wgrad* p, esr_stream_t stream);
 /* n independent weight-gradient problems (disjoint dw/dbias blocks).  fp16 3x3/s1 and 1x1 entries are
  * packed, up to 8 at a time, into ONE launch (at training sizes a single conv's wgrad is ~64
@@ -1119,7 +1175,7 @@ int esr_graph_destroy(esr_graph_t g);
 int esr_run_ops_timed(const esr_op* ops, int32_t n, esr_stream_t stream, float* ms_out);
 
 const char* esr_last_error(void);
-int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8, esr_fold3 / esr_fold3_op / ESR_OP_FOLD3 with esr_pool modes 4 / 5, esr_batch / esr_batch_item / esr_batch_assemble, esr_tile_many / esr_tile_item / esr_tile_many_op / ESR_OP_TILE_MANY, esr_tile_img / esr_tile_img_item / esr_tile_img_op / ESR_OP_TILE_IMG, and esr_set_metrics / esr_set_metrics_item / esr_image_set_metrics were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
+int esr_abi_version(void);   /* 6 (round 6: ESR_OPF_FOLLOW, esr_debug_rdb_wgrad_follow; esr_dihedral / esr_dihedral_op / ESR_OP_DIHEDRAL, esr_tile / esr_tile_op / ESR_OP_TILE esr_tile_x8 / esr_tile_x8_op / ESR_OP_TILE_X8, esr_fold3 / esr_fold3_op / ESR_OP_FOLD3 with esr_pool modes 4 / 5, esr_batch / esr_batch_item / esr_batch_assemble, esr_tile_many / esr_tile_item / esr_tile_many_op / ESR_OP_TILE_MANY, esr_tile_img / esr_tile_img_item / esr_tile_img_op / ESR_OP_TILE_IMG, esr_tile_hr / esr_tile_hr_item / esr_tile_hr_desc / esr_tile_hr_op / ESR_OP_TILE_HR, and esr_set_metrics / esr_set_metrics_item / esr_image_set_metrics were added later under 6: no existing struct or entry changed); 5 (round 5: esr_rdb_wgrad.max_workgroups, esr_debug_device_alias / esr_debug_chain_order_waits); 4 (round 4: esr_conv.ksplit / split_ws / stat_sums, ESR_BN_FIN_APPLY / ESR_BN_RESTAT); 3 (round 3: esr_ragan_loss.mode / sums / ext, ...; 2 = round 2: esr_bn.groups / num_batches_tracked,
                                 esr_l1_loss, esr_ragan_loss, ESR_OPF_SIDE_FREE) */
 size_t esr_sizeof_op(void);
 

@@ -3,7 +3,8 @@
 decoded uint8 images stay on the device and every batch is one launch):
 
     python tools/train_folder.py HR_DIR [--lr-dir DIR] [--scale S] [--lr-size N] [--batch B] [--iters N] [--nb N]
-                                 [--precision fp16|fp32] [--seed K] [--out DIR] [--val LR_DIR HR_DIR] [--val-freq N] [--val-x8]
+                                 [--precision fp16|fp32] [--seed K] [--out DIR] [--val LR_DIR HR_DIR | --val-hr HR_DIR] [--val-freq N]
+                                 [--val-x8]
 
 HR_DIR: the HR images (sizes may differ; each is cut to a multiple of the scale with ``data.modcrop``, as the reference
 does for validation images — without --lr-dir the LR windows are resampled from them on the fly).  --lr-dir: the LR
@@ -13,7 +14,9 @@ the loss of every iteration and a last line ``iters N, last loss X``.  --out DIR
 there as ``G_iters<N>.pth``; nothing else is written, nothing is downloaded.  --val LR_DIR HR_DIR: a validation set, paired
 by sorted name (HR = 4 x LR; x4 only), scored every --val-freq iterations (default 100) with ``PSNRStep.validate`` — the
 validation pass of the reference's train loop, one device pass — and printed as the reference logs it:
-``# Validation # PSNR: 2.3456e+01``."""
+``# Validation # PSNR: 2.3456e+01``.  --val-hr HR_DIR: a validation set of ground-truth images alone (the reference's
+``dataroot_LR: null``), scored with ``PSNRStep.validate_hr``: the LR is made from the HR images inside the gather, not
+rounded to 8 bits; x4 only, no --val-x8."""
 import argparse
 import glob
 import os
@@ -48,9 +51,14 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--out')
     ap.add_argument('--val', nargs=2, metavar=('LR_DIR', 'HR_DIR'))
+    ap.add_argument('--val-hr', metavar='HR_DIR', help='validate from ground-truth images alone: validate_hr(...)')
     ap.add_argument('--val-freq', type=int, default=100)
     ap.add_argument('--val-x8', action='store_true', help='score the x8 self-ensemble: validate(..., x8=True)')
     a = ap.parse_args()
+    if a.val and a.val_hr:
+        sys.exit('train_folder.py: --val and --val-hr are two ways to validate: give one')
+    if a.val_hr and a.val_x8:
+        sys.exit('train_folder.py: --val-x8 is not offered with --val-hr')
     random.seed(a.seed)
     torch.manual_seed(a.seed)
     hr = read_dir(a.hr_dir)
@@ -69,10 +77,10 @@ def main():
     netG.load_state_dict(synth.rrdbnet_state_dict(nb=a.nb, seed=a.seed, upscale=a.scale), strict=True)
     step = train.PSNRStep(netG, loss_scale='dynamic' if a.precision == 'fp16' else 1.0)
     val = None
-    if a.val:
+    if a.val or a.val_hr:
         if a.val_freq < 1:
             sys.exit('train_folder.py: --val-freq takes an int >= 1, got %d' % a.val_freq)
-        val = [[torch.from_numpy(im).to(dev) for im in read_dir(d)] for d in a.val]
+        val = [[torch.from_numpy(im).to(dev) for im in read_dir(d)] for d in (a.val or [a.val_hr])]
     it, loss = 0, float('nan')
     while it < a.iters:
         for var_L, real_H in ts.epoch(a.batch):
@@ -81,9 +89,10 @@ def main():
             print('iter %d  l_pix %.6f' % (it, loss), flush=True)
             if val and it % a.val_freq == 0:
                 try:
-                    print('# Validation # PSNR: {:.4e}'.format(step.validate(*val, x8=a.val_x8)), flush=True)
+                    psnr = step.validate_hr(val[0]) if a.val_hr else step.validate(*val, x8=a.val_x8)
+                    print('# Validation # PSNR: {:.4e}'.format(psnr), flush=True)
                 except ValueError as e:
-                    sys.exit('train_folder.py: --val: %s' % e)
+                    sys.exit('train_folder.py: %s: %s' % ('--val-hr' if a.val_hr else '--val', e))
             if it == a.iters:
                 break
     step.finish()
