@@ -1,6 +1,6 @@
 // metrics_set.hip — PSNR, SSIM, PSNR_Y and SSIM_Y of a whole image SET in one launch set (esr_image_set_metrics): what
 // codes/test.py:69-110 and the validation loop of codes/train.py:121-159 compute per image, from 8-bit HWC image pairs
-// that stay on the device (forward_images' results against their ground truth).  Table-driven like tile_img.hip: one
+// that stay on the device (forward_images' results against their ground truth).  Table-driven like tile_io.hip: one
 // item per pair in device memory, one workgroup per 16 x 32 tile of one image's cropped region.  The bytes are read once:
 // a workgroup stages its tile plus the 10-pixel window halo of both images in LDS, derives the unrounded luma there and
 // produces all four sums from that staging — no fp64 plane and no float image goes to memory.  The 11 x 11 window is

@@ -1,5 +1,5 @@
 // resample_taps.h — the two tap loops of the in-kernel MATLAB-bicubic resample (util.py:323-341), shared by
-// batch_assemble.hip's generated LR and tile_img.hip's HR gather so that both give the same bits: an fp32 sum over the
+// batch_assemble.hip's generated LR and tile_io.hip's HR gather so that both give the same bits: an fp32 sum over the
 // taps in ascending order, acc += w * x, for three channels at a time.  The clamps keep any table inside the image and
 // the LDS row.
 #pragma once

@@ -1,215 +1,242 @@
-// tile_io.hip — the two ends of tiled inference: gather = fixed-size windows of an NCHW fp32 image -> G32 slots,
-// stitch = the owned rectangle of every window's fp32 NCHW output -> the caller's NCHW image.  Geometry:
-// include/esrgan_hip.h (esr_tile); both kernels derive it from tile, pad and the tile index.  Plain loads and stores.
-// esr_tile_many is the same pair over an image set: a device table names each slot's image and tile.
-#include "tile_geom.h"
+// tile_io.hip — the plain ends of tiled inference: gather = fixed-size windows of an image -> G32 slots, stitch = the owned
+// rectangle of every window's fp32 NCHW output -> the result image.  Four ops share the bodies of tile_ends.h:
+//   esr_tile       windows named per image, fp32 NCHW outside
+//   esr_tile_many  windows named by a device table (an image set), fp32 NCHW outside
+//   esr_tile_img   the table, uint8 HWC outside: / 255 in, clamp, x 255, round out
+//   esr_tile_hr    esr_tile_img with a gather that makes the LR window itself, out of the 8-bit HR image through the
+//                  whole image's bicubic tables; its stitch is esr_tile_img's kernel
+// Geometry and index maps: include/esrgan_hip.h and tile_geom.h.  Plain loads, stores and VALU.
+#include "tile_checks.h"
+#include "resample_taps.h"
 
 namespace {
 
-constexpr int TB_X = 64, TB_Y = 4;   // 64 pixels along x by 4 rows per workgroup
+static_assert(sizeof(esr_tile_hr) == sizeof(esr_tile_img) && offsetof(esr_tile_hr, items) == offsetof(esr_tile_img, items) &&
+              offsetof(esr_tile_hr, g32) == offsetof(esr_tile_img, g32) && offsetof(esr_tile_hr, bgr) == offsetof(esr_tile_img, bgr),
+              "esr_tile_hr has esr_tile_img's fields: its stitch is esr_tile_img's");
+static_assert(sizeof(esr_tile_hr_desc) == 64, "one 64-byte descriptor per image");
 
-// One thread = one pixel of one window: C strided fp32 reads along x, one finished 32-byte channel group out.
+constexpr int HR_T = 16;                     // one workgroup = one 16 x 16 LR tile of one slot's window, one pixel per thread
+constexpr int HR_SPAN = ESR_TILE_HR_SPAN;    // source columns of an LDS row: 15 * 4 + 17 taps at x4, odd
+static_assert(HR_SPAN >= (HR_T - 1) * 4 + 17, "the span of 16 consecutive LR columns of a x4 table");
+
 template <typename T>
 __global__ __launch_bounds__(TB_X * TB_Y) void tile_gather_kernel(const esr_tile p, int th, int tw, int nx, int ntiles) {
-  constexpr int CPG = DT<T>::CPG;
-  const int col = blockIdx.x * TB_X + (threadIdx.x & (TB_X - 1)), row = blockIdx.y * TB_Y + threadIdx.x / TB_X;
-  if (col >= tw || row >= th) return;
-  const int s = blockIdx.z / p.B, b = blockIdx.z - s * p.B;
-  const int t = p.t_begin + s < ntiles ? p.t_begin + s : ntiles - 1;   // a tail pass repeats the last tile
-  const TileAxis ay = tile_axis(p.H, p.tile, p.pad, th, t / nx), ax = tile_axis(p.W, p.tile, p.pad, tw, t % nx);
-  const int64_t plane = (int64_t)p.H * p.W;
-  const float* const src = p.nchw + (int64_t)b * p.C * plane + (int64_t)(ay.w0 + row) * p.W + ax.w0 + col;
-  alignas(16) T v[CPG];
-#pragma unroll
-  for (int e = 0; e < CPG; ++e) v[e] = (T)((e < 8 && e < p.C) ? src[e * plane] : 0.f);
-  char* const dst = (char*)p.g32.ptr + (int64_t)blockIdx.z * p.g32.batch_stride + ((int64_t)(row + 1) * p.g32.wp + col + 1) * 32;
-  ((u32x4*)dst)[0] = ((const u32x4*)v)[0];
-  ((u32x4*)dst)[1] = ((const u32x4*)v)[1];
+  plain_gather<T>(TILE_PER_IMAGE(p, th, tw, nx, ntiles), PxF32<8>{}, p.C, p.g32);
 }
-
-// One thread = four HR pixels along x (one LR column) of one HR row of a tile's owned rectangle, all C channels: 16-byte
-// loads and stores (every HR offset and row pitch is a multiple of four floats).  p.H, p.W are the HR image.
 __global__ __launch_bounds__(TB_X * TB_Y) void tile_stitch_kernel(const esr_tile p, int th, int tw, int nx, int ntiles) {
-  const int s = blockIdx.z / p.B, b = blockIdx.z - s * p.B;
-  const int t = p.t_begin + s;
-  if (t >= ntiles) return;                          // a tail pass: the repeated windows are not written
-  const TileAxis ay = tile_axis(p.H >> 2, p.tile, p.pad, th, t / nx), ax = tile_axis(p.W >> 2, p.tile, p.pad, tw, t % nx);
-  const int col = blockIdx.x * TB_X + (threadIdx.x & (TB_X - 1)), row = blockIdx.y * TB_Y + threadIdx.x / TB_X;
-  if (col >= ax.on || row >= 4 * ay.on) return;
-  const int64_t src_plane = (int64_t)4 * th * tw, dst_plane = (int64_t)p.H * (p.W >> 2);   // in 16-byte units
-  const f32x4* const src = (const f32x4*)p.slots_nchw + (int64_t)blockIdx.z * p.C * src_plane +
-                           (int64_t)(4 * (ay.o0 - ay.w0) + row) * tw + (ax.o0 - ax.w0) + col;
-  f32x4* const dst = (f32x4*)p.nchw + (int64_t)b * p.C * dst_plane + (int64_t)(4 * ay.o0 + row) * (p.W >> 2) + ax.o0 + col;
-  for (int c = 0; c < p.C; ++c) dst[c * dst_plane] = src[c * src_plane];
+  plain_stitch(TILE_PER_IMAGE(p, th, tw, nx, ntiles), p.C, p.slots_nchw);
 }
-
-// The table-driven pair (esr_tile_many): blockIdx.z is the slot, and the slot's item — one 24-byte table entry per thread,
-// the same for a whole workgroup — names the image and the tile; everything else is the arithmetic of the kernels above.
-static_assert(sizeof(esr_tile_item) == 24, "esr_tile_item is a 24-byte table entry");
 
 template <typename T>
 __global__ __launch_bounds__(TB_X * TB_Y) void tile_many_gather_kernel(const esr_tile_many p) {
-  constexpr int CPG = DT<T>::CPG;
-  const int col = blockIdx.x * TB_X + (threadIdx.x & (TB_X - 1)), row = blockIdx.y * TB_Y + threadIdx.x / TB_X;
-  if (col >= p.tw || row >= p.th) return;
-  const esr_tile_item it = p.items[blockIdx.z];     // a filler slot is filled like any other
-  const int nx = tile_count(it.W, p.tile);
-  const TileAxis ay = tile_axis(it.H, p.tile, p.pad, p.th, it.t / nx), ax = tile_axis(it.W, p.tile, p.pad, p.tw, it.t % nx);
-  const int64_t plane = (int64_t)it.H * it.W;
-  const float* const src = it.nchw + (int64_t)(ay.w0 + row) * it.W + ax.w0 + col;
-  alignas(16) T v[CPG];
-#pragma unroll
-  for (int e = 0; e < CPG; ++e) v[e] = (T)((e < 8 && e < p.C) ? src[e * plane] : 0.f);
-  char* const dst = (char*)p.g32.ptr + (int64_t)blockIdx.z * p.g32.batch_stride + ((int64_t)(row + 1) * p.g32.wp + col + 1) * 32;
-  ((u32x4*)dst)[0] = ((const u32x4*)v)[0];
-  ((u32x4*)dst)[1] = ((const u32x4*)v)[1];
+  plain_gather<T>(TILE_BY_TABLE(p), PxF32<8>{}, p.C, p.g32);
+}
+__global__ __launch_bounds__(TB_X * TB_Y) void tile_many_stitch_kernel(const esr_tile_many p) {
+  plain_stitch(TILE_BY_TABLE(p), p.C, p.slots_nchw);
 }
 
-// it.H, it.W are the LR image: its HR rows are it.W 16-byte units long.
-__global__ __launch_bounds__(TB_X * TB_Y) void tile_many_stitch_kernel(const esr_tile_many p) {
-  const esr_tile_item it = p.items[blockIdx.z];
-  if (!it.live) return;                             // a filler slot: neither read nor written
-  const int nx = tile_count(it.W, p.tile);
-  const TileAxis ay = tile_axis(it.H, p.tile, p.pad, p.th, it.t / nx), ax = tile_axis(it.W, p.tile, p.pad, p.tw, it.t % nx);
-  const int col = blockIdx.x * TB_X + (threadIdx.x & (TB_X - 1)), row = blockIdx.y * TB_Y + threadIdx.x / TB_X;
-  if (col >= ax.on || row >= 4 * ay.on) return;
-  const int64_t src_plane = (int64_t)4 * p.th * p.tw, dst_plane = (int64_t)4 * it.H * it.W;   // in 16-byte units
-  const f32x4* const src = (const f32x4*)p.slots_nchw + (int64_t)blockIdx.z * p.C * src_plane +
-                           (int64_t)(4 * (ay.o0 - ay.w0) + row) * p.tw + (ax.o0 - ax.w0) + col;
-  f32x4* const dst = (f32x4*)it.nchw + (int64_t)(4 * ay.o0 + row) * it.W + ax.o0 + col;
-  for (int c = 0; c < p.C; ++c) dst[c * dst_plane] = src[c * src_plane];
+template <typename T>
+__global__ __launch_bounds__(TB_X * TB_Y) void tile_img_gather_kernel(const esr_tile_img p) {
+  plain_gather<T>(TILE_BY_TABLE(p), PxU8{p.bgr}, p.C, p.g32);
+}
+
+// One workgroup = one 16 x 16 LR tile of one window, resampled from the 8-bit HR image of its slot: the span of source
+// columns its 16 LR columns touch, the H pass of its rows over that span into the LDS (3 x 16 x 77 floats = 14 784 bytes),
+// the W pass out of it, one finished 32-byte channel group per thread.  The loops are batch_assemble.hip's
+// (resample_taps.h); rows and columns beyond the window are clamped into the image, computed by nobody or not written.
+template <typename T>
+__global__ __launch_bounds__(HR_T * HR_T) void tile_hr_gather_kernel(const esr_tile_hr p) {
+  __shared__ float rows[3 * HR_T * HR_SPAN];
+  __shared__ int span[2 * HR_T];
+  const TileWin w = TileTable::gather(TILE_BY_TABLE(p), blockIdx.z);     // a filler slot is filled like any other
+  const esr_tile_hr_desc d = *(const esr_tile_hr_desc*)w.img;
+  const TileAxis ay = w.ay, ax = w.ax;
+  const int a0 = blockIdx.y * HR_T, b0 = blockIdx.x * HR_T;
+  const int lx = threadIdx.x % HR_T, ly = threadIdx.x / HR_T;
+  const int s0 = p.bgr ? 2 : 0, sd = p.bgr ? -1 : 1;     // slot channel c reads byte s0 + sd c
+
+  if (threadIdx.x < HR_T) {
+    const int o = clampi(ax.w0 + b0 + (int)threadIdx.x, 0, w.W - 1);
+    int lo, hi;
+    resample_col_span(d.ix + (int64_t)o * d.taps_x, d.taps_x, d.hr_w, lo, hi);
+    span[threadIdx.x] = lo;
+    span[HR_T + threadIdx.x] = hi;
+  }
+  __syncthreads();
+  int c_lo = span[0], c_hi = span[HR_T];
+  for (int k = 1; k < HR_T; ++k) {
+    c_lo = span[k] < c_lo ? span[k] : c_lo;
+    c_hi = span[HR_T + k] > c_hi ? span[HR_T + k] : c_hi;
+  }
+  const int ncol = c_hi - c_lo + 1 < HR_SPAN ? c_hi - c_lo + 1 : HR_SPAN;
+  const int nrow = p.th - a0 < HR_T ? p.th - a0 : HR_T;
+  // H pass of the tile's rows on those columns
+  for (int e = threadIdx.x; e < nrow * ncol; e += HR_T * HR_T) {
+    const int r = e / ncol, xs = e - r * ncol;
+    const int o = clampi(ay.w0 + a0 + r, 0, w.H - 1);
+    const uint8_t* const col = d.hr + (int64_t)(c_lo + xs) * 3 + s0;
+    float acc[3] = {0.f, 0.f, 0.f};
+    resample_h_taps(d.wy + (int64_t)o * d.taps_y, d.iy + (int64_t)o * d.taps_y, d.taps_y, d.hr_h,
+                    [&](int c, int sy) { return __fdiv_rn((float)col[(int64_t)sy * d.pitch * 3 + sd * c], 255.0f); }, acc);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rows[(c * HR_T + r) * HR_SPAN + xs] = acc[c];
+  }
+  __syncthreads();
+  // W pass from the LDS
+  const int row = a0 + ly, colx = b0 + lx;
+  if (row >= p.th || colx >= p.tw) return;
+  const int o = clampi(ax.w0 + colx, 0, w.W - 1);
+  float acc[3] = {0.f, 0.f, 0.f};
+  resample_w_taps(d.wx + (int64_t)o * d.taps_x, d.ix + (int64_t)o * d.taps_x, d.taps_x, d.hr_w, c_lo, HR_SPAN,
+                  rows + ly * HR_SPAN, HR_T * HR_SPAN, acc);
+  u32x4 grp[2];
+  make_group<T, 3>(grp, 3, [&](int e) { return acc[e]; });
+  u32x4* const dst = g32_px(p.g32, blockIdx.z, row, colx);
+  dst[0] = grp[0];
+  dst[1] = grp[1];
+}
+
+// uint8 HWC out: one 16-byte load per channel, quantised, NC aligned dwords out.  The image's HR rows are 4 W pixels =
+// W groups of NC dwords.
+template <int NC>
+__global__ __launch_bounds__(TB_X * TB_Y) void tile_img_stitch_kernel(const esr_tile_img p) {
+  const TileTable r = TILE_BY_TABLE(p);
+  const TileWin w = TileTable::stitch(r, blockIdx.z);
+  if (!w.live) return;                              // a filler slot: neither read nor written
+  const f32x4* src;
+  int64_t src_plane, dst_unit;
+  if (!stitch_lane(r, w, NC, p.slots_nchw, src, src_plane, dst_unit)) return;
+  uint32_t q[NC][4];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const f32x4 v = src[c * src_plane];
+    q[c][0] = quant8_unit(v.x); q[c][1] = quant8_unit(v.y); q[c][2] = quant8_unit(v.z); q[c][3] = quant8_unit(v.w);
+  }
+  uint32_t* const dst = (uint32_t*)w.img + dst_unit * NC;
+  if constexpr (NC == 1) {
+    dst[0] = q[0][0] | q[0][1] << 8 | q[0][2] << 16 | q[0][3] << 24;
+  } else {
+    if (p.bgr) {                                    // q[0] / q[2]: the channels at bytes 0 / 2 of a pixel
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { const uint32_t t = q[0][j]; q[0][j] = q[2][j]; q[2][j] = t; }
+    }
+    dst[0] = q[0][0] | q[1][0] << 8 | q[2][0] << 16 | q[0][1] << 24;
+    dst[1] = q[1][1] | q[2][1] << 8 | q[0][2] << 16 | q[1][2] << 24;
+    dst[2] = q[2][2] | q[0][3] << 8 | q[1][3] << 16 | q[2][3] << 24;
+  }
+}
+
+// What the plain pair launches, once the op's own checks are through: th x tw the window, oh x ow the largest owned
+// rectangle (LR pixels).  gather / stitch launch on (grid, block); gather may still refuse, and returns the status.
+template <typename G, typename S>
+int plain_launch(const char* who, int to_g32, const esr_g32& g32, int th, int tw, int oh, int ow, unsigned slots,
+                 uintptr_t align_bits, const char* align_what, G&& gather, S&& stitch) {
+  const dim3 block(TB_X * TB_Y);
+  if (to_g32) {
+    TILE_TRY(chk_g32(who, g32, tw, th, tw, ""));
+    TILE_TRY(gather(dim3((tw + TB_X - 1) / TB_X, (th + TB_Y - 1) / TB_Y, slots), block));
+  } else {
+    TILE_TRY(chk_aligned(who, align_bits, align_what));
+    const dim3 grid((ow + TB_X - 1) / TB_X, oh, slots);   // 4 oh HR rows, TB_Y per workgroup
+    TILE_TRY(chk_tile_rows(who, oh, grid.y));
+    stitch(grid, block);
+  }
+  return 0;
+}
+
+// The table ops' common checks (esr_tile_many, esr_tile_img, esr_tile_hr: the same fields); c8 = the 8-bit forms' channels.
+template <typename P>
+int table_checks(const char* who, const P* p, bool c8, bool only3) {
+  if (!p) return chk_args(who, false, 0, nullptr, nullptr, 0, 0);
+  TILE_TRY(chk_args(who, p->items && p->th > 0 && p->tw > 0, p->to_g32, &p->g32, p->slots_nchw, p->C, p->dtype));
+  TILE_TRY(chk_tile_pad_scale(who, p->tile, p->pad, p->scale, false, 0, 0));
+  TILE_TRY(c8 ? chk_channels_8bit(who, p->C, only3) : chk_channels(who, p->C));
+  TILE_TRY(chk_side_scale(who, p->to_g32, p->scale));
+  TILE_TRY(chk_window(who, p->th, p->tw, p->tile, p->pad));
+  TILE_TRY(chk_count(who, "n_slots", p->n_slots));
+  TILE_TRY(chk_slots(who, "n_slots", p->n_slots));
+  TILE_TRY(chk_window_rows(who, p->th, TB_Y));
+  return chk_items(who, p->items);
+}
+
+// The two 8-bit entries: esr_tile_hr has esr_tile_img's fields, `hr` picks its gather.
+int tile_img_run(const esr_tile_img* p, esr_stream_t stream, const char* who, bool hr) {
+  TILE_TRY(table_checks(who, p, true, hr));
+  hipStream_t st = (hipStream_t)stream;
+  if (hr && p->to_g32) {
+    TILE_TRY(chk_g32(who, p->g32, p->tw, p->th, p->tw, ""));
+    const esr_tile_hr q = *(const esr_tile_hr*)p;
+    const dim3 grid((p->tw + HR_T - 1) / HR_T, (p->th + HR_T - 1) / HR_T, (unsigned)p->n_slots);   // y <= 65535: checked above
+    if (p->dtype == ESR_F16) hipLaunchKernelGGL(tile_hr_gather_kernel<_Float16>, grid, dim3(HR_T * HR_T), 0, st, q);
+    else hipLaunchKernelGGL(tile_hr_gather_kernel<float>, grid, dim3(HR_T * HR_T), 0, st, q);
+    return esr_check_launch("tile_hr_gather_kernel");
+  }
+  // the largest owned rectangle of any image with this window: min(tile, H) = min(tile, th), and alike along x
+  const int ow = p->tile < p->tw ? p->tile : p->tw, oh = p->tile < p->th ? p->tile : p->th;
+  TILE_TRY(plain_launch(who, p->to_g32, p->g32, p->th, p->tw, oh, ow, (unsigned)p->n_slots, (uintptr_t)p->slots_nchw,
+                        "slots_nchw (and 4-byte aligned images)",
+                        [&](dim3 grid, dim3 block) {
+                          if (p->dtype == ESR_F16) hipLaunchKernelGGL(tile_img_gather_kernel<_Float16>, grid, block, 0, st, *p);
+                          else hipLaunchKernelGGL(tile_img_gather_kernel<float>, grid, block, 0, st, *p);
+                          return 0;
+                        },
+                        [&](dim3 grid, dim3 block) {
+                          if (p->C == 1) hipLaunchKernelGGL(tile_img_stitch_kernel<1>, grid, block, 0, st, *p);
+                          else hipLaunchKernelGGL(tile_img_stitch_kernel<3>, grid, block, 0, st, *p);
+                        }));
+  return esr_check_launch("tile_img_kernel");
 }
 
 }  // namespace
 
 extern "C" int esr_tile_op(const esr_tile* p, esr_stream_t stream) {
-  if (!p || !p->nchw || (p->to_g32 ? !p->g32.ptr : !p->slots_nchw) || p->B <= 0 || p->C <= 0 || p->H <= 0 || p->W <= 0 ||
-      (p->dtype != ESR_F16 && p->dtype != ESR_F32)) {
-    esr_set_error("esr_tile_op: invalid arguments");
-    return ESR_ERR_INVALID;
-  }
-  if (p->tile < 1 || p->pad < 0 || (p->scale != 1 && p->scale != 4) || p->H % p->scale || p->W % p->scale) {
-    esr_set_error("esr_tile_op: tile = %d (>= 1), pad = %d (>= 0), scale = %d (1 or 4, dividing H and W)", p->tile, p->pad, p->scale);
-    return ESR_ERR_INVALID;
-  }
-  if (p->C > 8) {
-    esr_set_error("esr_tile_op: C = %d does not fit one fp32 channel group", p->C);
-    return ESR_ERR_UNSUPPORTED;
-  }
-  if (p->scale != (p->to_g32 ? 1 : 4)) {
-    esr_set_error("esr_tile_op: the gather runs at scale 1 and the stitch at scale 4, got %d", p->scale);
-    return ESR_ERR_UNSUPPORTED;
-  }
-  const int hl = p->H / p->scale, wl = p->W / p->scale;
-  const int th = tile_window(hl, p->tile, p->pad), tw = tile_window(wl, p->tile, p->pad);
-  const int ny = tile_count(hl, p->tile), nx = tile_count(wl, p->tile);
-  const int64_t ntiles = (int64_t)ny * nx;
-  if (ntiles > (1 << 30)) {
-    esr_set_error("esr_tile_op: %lld tiles are more than one image may have", (long long)ntiles);
-    return ESR_ERR_UNSUPPORTED;
-  }
-  if (p->t_begin < 0 || p->t_begin >= ntiles || p->t_count < 1) {
-    esr_set_error("esr_tile_op: tiles [%d, %d + %d) of %lld", p->t_begin, p->t_begin, p->t_count, (long long)ntiles);
-    return ESR_ERR_INVALID;
-  }
-  if ((int64_t)p->t_count * p->B > 65535) {
-    esr_set_error("esr_tile_op: t_count * B = %lld slots are too many for one launch", (long long)p->t_count * p->B);
-    return ESR_ERR_UNSUPPORTED;
-  }
+  const char* const who = "esr_tile_op";
+  if (!p) return chk_args(who, false, 0, nullptr, nullptr, 0, 0);
+  TILE_TRY(chk_args(who, p->nchw && p->B > 0 && p->H > 0 && p->W > 0, p->to_g32, &p->g32, p->slots_nchw, p->C, p->dtype));
+  TILE_TRY(chk_tile_pad_scale(who, p->tile, p->pad, p->scale, true, p->H, p->W));
+  TILE_TRY(chk_channels(who, p->C));
+  TILE_TRY(chk_side_scale(who, p->to_g32, p->scale));
+  TileImageGeom g;
+  TILE_TRY(chk_per_image(who, p->H, p->W, p->tile, p->pad, p->scale, p->t_begin, p->t_count, &g));
+  TILE_TRY(chk_slots(who, "t_count * B", (int64_t)p->t_count * p->B));
   hipStream_t st = (hipStream_t)stream;
-  const dim3 block(TB_X * TB_Y);
-  const unsigned slots = (unsigned)(p->t_count * p->B);
-  if (p->to_g32) {
-    if (p->g32.wp < tw + 2 || p->g32.ngroups < 1) {
-      esr_set_error("esr_tile_op: the G32 view (wp = %d) is narrower than the %d x %d window", p->g32.wp, th, tw);
-      return ESR_ERR_INVALID;
-    }
-    const dim3 grid((tw + TB_X - 1) / TB_X, (th + TB_Y - 1) / TB_Y, slots);
-    if (grid.y > 65535) {
-      esr_set_error("esr_tile_op: a window of %d rows is too tall for one launch", th);
-      return ESR_ERR_UNSUPPORTED;
-    }
-    if (p->dtype == ESR_F16) hipLaunchKernelGGL(tile_gather_kernel<_Float16>, grid, block, 0, st, *p, th, tw, nx, (int)ntiles);
-    else hipLaunchKernelGGL(tile_gather_kernel<float>, grid, block, 0, st, *p, th, tw, nx, (int)ntiles);
-  } else {
-    if (((uintptr_t)p->nchw | (uintptr_t)p->slots_nchw) & 15) {
-      esr_set_error("esr_tile_op: the stitch needs 16-byte aligned nchw and slots_nchw");
-      return ESR_ERR_INVALID;
-    }
-    const int ow = p->tile < wl ? p->tile : wl, oh = p->tile < hl ? p->tile : hl;   // the largest owned rectangle
-    const dim3 grid((ow + TB_X - 1) / TB_X, oh, slots);                               // 4 oh HR rows, TB_Y per workgroup
-    if (grid.y > 65535) {
-      esr_set_error("esr_tile_op: tiles of %d rows are too tall for one launch", oh);
-      return ESR_ERR_UNSUPPORTED;
-    }
-    hipLaunchKernelGGL(tile_stitch_kernel, grid, block, 0, st, *p, th, tw, nx, (int)ntiles);
-  }
+  const int ow = p->tile < g.wl ? p->tile : g.wl, oh = p->tile < g.hl ? p->tile : g.hl;   // the largest owned rectangle
+  TILE_TRY(plain_launch(who, p->to_g32, p->g32, g.th, g.tw, oh, ow, (unsigned)(p->t_count * p->B),
+                        (uintptr_t)p->nchw | (uintptr_t)p->slots_nchw, "nchw and slots_nchw",
+                        [&](dim3 grid, dim3 block) {
+                          TILE_TRY(chk_window_rows(who, g.th, TB_Y));   // the table ops refuse this before they come here
+                          if (p->dtype == ESR_F16) hipLaunchKernelGGL(tile_gather_kernel<_Float16>, grid, block, 0, st, *p, g.th, g.tw, g.nx, g.ntiles);
+                          else hipLaunchKernelGGL(tile_gather_kernel<float>, grid, block, 0, st, *p, g.th, g.tw, g.nx, g.ntiles);
+                          return 0;
+                        },
+                        [&](dim3 grid, dim3 block) { hipLaunchKernelGGL(tile_stitch_kernel, grid, block, 0, st, *p, g.th, g.tw, g.nx, g.ntiles); }));
   return esr_check_launch("tile_kernel");
 }
 
 // Per-item fields (image pointer, H, W, t, live) are device memory and cannot be checked here: see the header.
 extern "C" int esr_tile_many_op(const esr_tile_many* p, esr_stream_t stream) {
-  if (!p || !p->items || (p->to_g32 ? !p->g32.ptr : !p->slots_nchw) || p->C <= 0 || p->th <= 0 || p->tw <= 0 ||
-      (p->dtype != ESR_F16 && p->dtype != ESR_F32)) {
-    esr_set_error("esr_tile_many_op: invalid arguments");
-    return ESR_ERR_INVALID;
-  }
-  if (p->tile < 1 || p->pad < 0 || (p->scale != 1 && p->scale != 4)) {
-    esr_set_error("esr_tile_many_op: tile = %d (>= 1), pad = %d (>= 0), scale = %d (1 or 4)", p->tile, p->pad, p->scale);
-    return ESR_ERR_INVALID;
-  }
-  if (p->C > 8) {
-    esr_set_error("esr_tile_many_op: C = %d does not fit one fp32 channel group", p->C);
-    return ESR_ERR_UNSUPPORTED;
-  }
-  if (p->scale != (p->to_g32 ? 1 : 4)) {
-    esr_set_error("esr_tile_many_op: the gather runs at scale 1 and the stitch at scale 4, got %d", p->scale);
-    return ESR_ERR_UNSUPPORTED;
-  }
-  const int64_t win = (int64_t)p->tile + 2 * (int64_t)p->pad;
-  if (p->th > win || p->tw > win) {
-    esr_set_error("esr_tile_many_op: a %d x %d window is larger than tile + 2 pad = %lld", p->th, p->tw, (long long)win);
-    return ESR_ERR_INVALID;
-  }
-  if (p->n_slots < 1) {
-    esr_set_error("esr_tile_many_op: n_slots = %d (>= 1)", p->n_slots);
-    return ESR_ERR_INVALID;
-  }
-  if (p->n_slots > 65535) {
-    esr_set_error("esr_tile_many_op: n_slots = %d slots are too many for one launch", p->n_slots);
-    return ESR_ERR_UNSUPPORTED;
-  }
-  if ((p->th + TB_Y - 1) / TB_Y > 65535) {
-    esr_set_error("esr_tile_many_op: a window of %d rows is too tall for one launch", p->th);
-    return ESR_ERR_UNSUPPORTED;
-  }
-  if ((uintptr_t)p->items & 7) {
-    esr_set_error("esr_tile_many_op: the item table needs 8-byte alignment");
-    return ESR_ERR_INVALID;
-  }
+  const char* const who = "esr_tile_many_op";
+  TILE_TRY(table_checks(who, p, false, false));
   hipStream_t st = (hipStream_t)stream;
-  const dim3 block(TB_X * TB_Y);
-  if (p->to_g32) {
-    if (p->g32.wp < p->tw + 2 || p->g32.ngroups < 1) {
-      esr_set_error("esr_tile_many_op: the G32 view (wp = %d) is narrower than the %d x %d window", p->g32.wp, p->th, p->tw);
-      return ESR_ERR_INVALID;
-    }
-    const dim3 grid((p->tw + TB_X - 1) / TB_X, (p->th + TB_Y - 1) / TB_Y, (unsigned)p->n_slots);
-    if (p->dtype == ESR_F16) hipLaunchKernelGGL(tile_many_gather_kernel<_Float16>, grid, block, 0, st, *p);
-    else hipLaunchKernelGGL(tile_many_gather_kernel<float>, grid, block, 0, st, *p);
-  } else {
-    if ((uintptr_t)p->slots_nchw & 15) {
-      esr_set_error("esr_tile_many_op: the stitch needs 16-byte aligned slots_nchw (and images)");
-      return ESR_ERR_INVALID;
-    }
-    // the largest owned rectangle of any image with this window: min(tile, H) = min(tile, th), and alike along x
-    const int ow = p->tile < p->tw ? p->tile : p->tw, oh = p->tile < p->th ? p->tile : p->th;
-    const dim3 grid((ow + TB_X - 1) / TB_X, oh, (unsigned)p->n_slots);                // 4 oh HR rows, TB_Y per workgroup
-    if (grid.y > 65535) {
-      esr_set_error("esr_tile_many_op: tiles of %d rows are too tall for one launch", oh);
-      return ESR_ERR_UNSUPPORTED;
-    }
-    hipLaunchKernelGGL(tile_many_stitch_kernel, grid, block, 0, st, *p);
-  }
+  // the largest owned rectangle of any image with this window: min(tile, H) = min(tile, th), and alike along x
+  const int ow = p->tile < p->tw ? p->tile : p->tw, oh = p->tile < p->th ? p->tile : p->th;
+  TILE_TRY(plain_launch(who, p->to_g32, p->g32, p->th, p->tw, oh, ow, (unsigned)p->n_slots, (uintptr_t)p->slots_nchw,
+                        "slots_nchw (and images)",
+                        [&](dim3 grid, dim3 block) {
+                          if (p->dtype == ESR_F16) hipLaunchKernelGGL(tile_many_gather_kernel<_Float16>, grid, block, 0, st, *p);
+                          else hipLaunchKernelGGL(tile_many_gather_kernel<float>, grid, block, 0, st, *p);
+                          return 0;
+                        },
+                        [&](dim3 grid, dim3 block) { hipLaunchKernelGGL(tile_many_stitch_kernel, grid, block, 0, st, *p); }));
   return esr_check_launch("tile_many_kernel");
+}
+
+extern "C" int esr_tile_img_op(const esr_tile_img* p, esr_stream_t stream) {
+  return tile_img_run(p, stream, "esr_tile_img_op", false);
+}
+
+// Items and descriptors (pointers, sizes, tables) are device memory and cannot be checked here: see the header.
+extern "C" int esr_tile_hr_op(const esr_tile_hr* p, esr_stream_t stream) {
+  return tile_img_run((const esr_tile_img*)p, stream, "esr_tile_hr_op", true);
 }
