@@ -29,6 +29,7 @@
 #endif
 
 #include "mfma_tile.h"
+#include "conv_plain.h"
 
 namespace {
 
@@ -51,6 +52,9 @@ __device__ __forceinline__ void epilogue_block(const esr_conv& p, Acc8& acc, Acc
     // D / VGG conv in inference): straight-line form without the residual / noise / second-output stages of the general
     // epilogue below (measured on the 512x512 tail: 435 -> 394 us for the 64 -> 64 conv, tools/tail_conv_probe.py).
     // max(x, x * slope) is LeakyReLU (slope 0.2) and the identity (slope 1).
+    // fp16 layers of this kind run the PLAIN instantiation (conv_plain.h, chosen by launch()) and never get here; this
+    // path serves fp32, and fp16 calls that a store flavour (debug_flags & 0x18) keeps on the general kernel leave it
+    // at the test below.
     const bool g32_only = p.out.ptr && p.nchw_out_c <= 0, nchw_only = !p.out.ptr && p.nchw_out_c > 0;
     if (!p.res1.ptr && !p.res2.ptr && !p.aux_out.ptr && p.noise_mode == ESR_NOISE_OFF && (g32_only || nchw_only) &&
         !(p.debug_flags & 0x18)) {
@@ -286,7 +290,7 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <typename T, int KS, int S, int UPS, int WR, int WC, int NCG, int NCW, bool WLDS, bool HAS1X1, bool BWD, bool PIPE = false, int RW = 4, bool PACK = false>
+template <typename T, int KS, int S, int UPS, int WR, int WC, int NCG, int NCW, bool WLDS, bool HAS1X1, bool BWD, bool PIPE = false, int RW = 4, bool PACK = false, int PLAIN = 0>
 __device__ __forceinline__ void conv_body(const esr_conv& p, char* const smem, const int block_x, const int grid_x,
                                           const int block_y, const int block_z = 0) {
   using G = Geo<KS, S, UPS, WR, WC, NCG, NCW, WLDS, HAS1X1, PIPE, RW, PACK>;
@@ -295,6 +299,7 @@ __device__ __forceinline__ void conv_body(const esr_conv& p, char* const smem, c
   constexpr int R = G::R;
   constexpr int NSA = G::NSA;
   static_assert(!HAS1X1 || (NCW == 1 && NCG == 1 && KS == 3 && S == 1 && !UPS && WLDS), "fused 1x1 only on the N=32 3x3 conv");
+  static_assert(!PLAIN || (sizeof(T) == 2 && !HAS1X1 && !BWD && !PACK), "plain form: fp16 forward layers (conv_plain.h)");
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -767,6 +772,11 @@ __device__ __forceinline__ void conv_body(const esr_conv& p, char* const smem, c
   const int ox = UPS == 2 ? ox0 + 2 * j + wc : UPS == 3 ? 2 * (ox0 + wc * 32 + j) + pdx : ox0 + wc * 32 + j;
   if (ox >= p.W || (dbg & 1)) return;
   const int oyb = UPS == 3 ? 2 * (oy0 + wr * R) + pdy : oy0 + wr * R;
+  if constexpr (PLAIN != 0) {
+    // bias + activation into one output, tested by launch() on the host: nothing else is compiled in
+    plain_epilogue<R, NCW, (UPS == 3 ? 2 : 1)>(p, acc, b, cb0, h, oyb, ox);
+    return;
+  }
   sfor<NCW>([&](auto CW) __attribute__((always_inline)) {
     constexpr int cw = decltype(CW)::value;
     const int cb = cb0 + cw;
@@ -775,11 +785,13 @@ __device__ __forceinline__ void conv_body(const esr_conv& p, char* const smem, c
   });
 }
 
-template <typename T, int KS, int S, int UPS, int WR, int WC, int NCG, int NCW, bool WLDS, bool HAS1X1, bool BWD, bool PIPE = false, int RW = 4, bool PACK = false>
+// PLAIN (last, so that the tools that read the first ten arguments out of a kernel's name keep working): 1 = the fp16
+// forward layer that is bias + activation into one output, with conv_plain.h's epilogue alone
+template <typename T, int KS, int S, int UPS, int WR, int WC, int NCG, int NCW, bool WLDS, bool HAS1X1, bool BWD, bool PIPE = false, int RW = 4, bool PACK = false, int PLAIN = 0>
 __global__ __launch_bounds__(WR * WC * NCG * 64, 2) void conv_kernel(const esr_conv p) {
   using G = Geo<KS, S, UPS, WR, WC, NCG, NCW, WLDS, HAS1X1, PIPE, RW, PACK>;
   __shared__ __attribute__((aligned(16))) char smem[G::LDS_BYTES];
-  conv_body<T, KS, S, UPS, WR, WC, NCG, NCW, WLDS, HAS1X1, BWD, PIPE, RW, PACK>(p, smem, blockIdx.x, gridDim.x, blockIdx.y, blockIdx.z);
+  conv_body<T, KS, S, UPS, WR, WC, NCG, NCW, WLDS, HAS1X1, BWD, PIPE, RW, PACK, PLAIN>(p, smem, blockIdx.x, gridDim.x, blockIdx.y, blockIdx.z);
 }
 
 // ---- the deep 4x4/s2 convs of the discriminators (maps of 4 / 8 / 16 output columns, 256-512 channels) ----------------
@@ -867,10 +879,18 @@ static bool pack_addressable(const esr_conv& p, int per_tile) {
   return false;
 }
 
+// debug_flags & 512 (test hook): the caller expects a plain kernel (conv_plain.h) and this call would not get one
+static int refuse_not_plain() {
+  esr_set_error("conv: debug_flags & 512 asks for a plain kernel, and this call is not a plain fp16 forward layer "
+                "(bias + activation into one output, no ksplit, no store flavour)");
+  return ESR_ERR_UNSUPPORTED;
+}
+
 // the transposed 4x4/s2 conv (esr_conv.upsample == 2: input gradient of those layers) on output maps of 8 / 16 / 32 columns
 template <typename T, int NCW>
 int launch_ts2_packed(const esr_conv& p, hipStream_t st) {
   using G = Geo<4, 1, 2, 4, 2, 1, NCW, true, false, false, 4, true>;
+  if (p.debug_flags & 512) return refuse_not_plain();
   const int per_tile = (64 / p.W) * (p.H <= 8 ? 2 : 1);
   const int tyn = p.H <= 8 ? 1 : (p.H + G::TH - 1) / G::TH;
   dim3 grid(((p.B + per_tile - 1) / per_tile) * tyn, (p.cout_blocks + NCW - 1) / NCW, p.ksplit);
@@ -885,6 +905,7 @@ int launch_ts2_packed(const esr_conv& p, hipStream_t st) {
 template <typename T>
 int launch_s2_packed(const esr_conv& p, hipStream_t st) {
   using G = Geo<4, 2, 0, 2, 1, 4, 1, false, false, false, 4, true>;
+  if (p.debug_flags & 512) return refuse_not_plain();
   const int per_tile = (32 / p.W) * (p.H <= 4 ? 2 : 1);
   const int tyn = p.H <= 4 ? 1 : (p.H + G::TH - 1) / G::TH;
   dim3 grid(((p.B + per_tile - 1) / per_tile) * tyn, (p.cout_blocks + 3) / 4, p.ksplit);
@@ -908,6 +929,19 @@ int launch(const esr_conv& p, hipStream_t st) {
   const bool bwd = p.mask.ptr || p.out3.ptr || (!p.res1.ptr && p.alpha != 1.0f) ||
                    (p.res1.ptr && p.res1.ngroups < p.cout_blocks * GPB && p.res1.ngroups < p.out.ngroups) ||
                    (p.res2.ptr && p.res2.ngroups < p.cout_blocks * GPB && p.res2.ngroups < p.out.ngroups);
+  // plain fp16 forward layers (bias + activation into ONE output, G32 or NCHW — the test epilogue_block makes on the
+  // device, made here): the instantiation that holds conv_plain.h's epilogue and nothing else.  debug_flags & 0x18
+  // (a store flavour) keeps a call on the general kernel; debug_flags & 512 refuses a call that is not plain.
+  const bool g32_only = p.out.ptr && p.nchw_out_c <= 0, nchw_only = !p.out.ptr && p.nchw_out_c > 0;
+  const bool plain = sizeof(T) == 2 && !HAS1X1 && !bwd && !p.res1.ptr && !p.res2.ptr && !p.aux_out.ptr &&
+                     p.noise_mode == ESR_NOISE_OFF && (g32_only || nchw_only) && !(p.debug_flags & 0x18);
+  if ((p.debug_flags & 512) && !plain) return refuse_not_plain();
+  if constexpr (sizeof(T) == 2 && !HAS1X1) {
+    if (plain) {
+      hipLaunchKernelGGL((conv_kernel<T, KS, S, UPS, WR, WC, NCG, NCW, WLDS, false, false, PIPE, RW, false, 1>), grid, dim3(G::NT), 0, st, p);
+      return esr_check_launch("conv_kernel (plain)");
+    }
+  }
   if (bwd) hipLaunchKernelGGL((conv_kernel<T, KS, S, UPS, WR, WC, NCG, NCW, WLDS, HAS1X1, true, PIPE, RW>), grid, dim3(G::NT), 0, st, p);
   else hipLaunchKernelGGL((conv_kernel<T, KS, S, UPS, WR, WC, NCG, NCW, WLDS, HAS1X1, false, PIPE, RW>), grid, dim3(G::NT), 0, st, p);
   return esr_check_launch("conv_kernel");
