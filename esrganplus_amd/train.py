@@ -13,6 +13,10 @@ Launch economy (the step is a few thousand small launches): each network sees it
 (``forward_pair``: per-operand BatchNorm statistics), the losses are single launches that also produce their
 gradients (``losses``), and the D step is enqueued on a second stream under the G backward (one GPU and
 data-parallel alike: the step that is measured on one GPU is the step that scales).
+
+Three steps share one base (``_StepBase``) and, in their hand-written form, one set of phases (``_ManualPass`` and
+what derives from it; DESIGN.md 7 has the table of streams, waits and records): ``ESRGANPlusStep``, ``PSNRStep`` (the
+generator-only subset) and ``SRGANStep``.
 """
 import contextlib
 import os
@@ -84,16 +88,14 @@ def _check_channels(what, netG, netD, netF):
                          'train such a generator without it (SRGANStep with feature_weight = 0, or PSNRStep)' % (what, g))
 
 
-class ESRGANPlusStep:
-    def __init__(self, netG, netD, netF, lr_G=1e-4, lr_D=1e-4, beta1_G=0.9, beta1_D=0.9,
-                 pixel_weight=1e-2, feature_weight=1.0, gan_weight=5e-3, loss_scale=1.0, data_parallel=None,
-                 pixel_criterion='l1', feature_criterion='l1'):
-        _check_channels('ESRGANPlusStep', netG, netD, netF)
-        self.netG, self.netD, self.netF = netG, netD, netF
-        # 'l1' / 'l2' (SRRaGAN_model.py:31-53): the raw and the autograd form of each criterion's one launch
-        self._pix_raw, self._pix_loss = LS.criterion(pixel_criterion)
-        self._fea_raw, self._fea_loss = LS.criterion(feature_criterion)
-        self.l_pix_w, self.l_fea_w, self.l_gan_w = pixel_weight, feature_weight, gan_weight
+class _StepBase:
+    """What the three steps share: the loss scale, the optimizer / exchange pair of each network that trains, the
+    stream and knob helpers, and the public calls that do not depend on the losses."""
+
+    _nets = ('G', 'D')            # the networks this step trains: net<X>, optimizer_<X>, ex<X>
+
+    def __init__(self, netG, loss_scale, data_parallel):
+        self.netG = netG
         # data_parallel: None = follow torch.distributed (world size > 1); False inside a multi-rank job = this rank's
         # own step without any exchange (bench.py's no-exchange figure next to the data-parallel one)
         self.data_parallel = DP.active() if data_parallel is None else bool(data_parallel)
@@ -104,13 +106,6 @@ class ESRGANPlusStep:
             self.scaler = DynamicLossScaler(next(netG.parameters()).device)
             loss_scale = 1.0
         self.loss_scale = loss_scale
-        # one fused launch per optimizer (optim.FusedAdam == torch.optim.Adam arithmetic; it stays a
-        # torch.optim.Optimizer, so the reference's MultiStepLR schedulers attach unchanged)
-        self.optimizer_G = FusedAdam([p for p in netG.parameters() if p.requires_grad],
-                                     lr=lr_G, betas=(beta1_G, 0.999))
-        self.optimizer_D = FusedAdam(netD.parameters(), lr=lr_D, betas=(beta1_D, 0.999))
-        self.exG = DP.GradExchange(netG, enabled=self.data_parallel, measure=self.data_parallel)
-        self.exD = DP.GradExchange(netD, enabled=self.data_parallel, measure=self.data_parallel)
         self.log = {}
         self.fake_H = None
         self._steps = 0
@@ -128,29 +123,18 @@ class ESRGANPlusStep:
         # shares the chip with other launches runs at the pace of its most-delayed tile, and the small launches slow
         # each other 2-5x.  What mode 1 overlaps is what the default stream's hardware queue lets through.
         self.overlap = self._knob_int('ESR_TRAIN_OVERLAP', '1', (0, 1))
-        # ESR_SHARED_D=0: the D step runs its own forward pair (round 3) instead of re-using the G step's pass
-        self.shared_d = os.environ.get('ESR_SHARED_D', '1') != '0'
         # ESR_TRAIN_MANUAL=0: the step is written with autograd (losses as autograd Functions, torch.autograd.backward
-        # over the three networks' nodes: ~100 glue launches — clones, gradient copies / sums, zero fills — and their
+        # over the networks' nodes: ~100 glue launches — clones, gradient copies / sums, zero fills — and their
         # host time per step).  Default: the same launch lists driven directly (`_step_manual`), when the networks
         # allow it (`_manual_ok`)
         self.manual = os.environ.get('ESR_TRAIN_MANUAL', '1') != '0'
-        # netF(fake): forward, feature loss and input-gradient pass on the SIDE stream, next to netD's forward and its
-        # G-step pass on the main stream (both hang off fake_H only; their two contributions to dL/d fake_H meet in one add)
-        self.netf_side = os.environ.get('ESR_TRAIN_NETF_SIDE', '1') == '1'
-        self.d_when = self._knob('ESR_TRAIN_DSTEP', 'last', ('first', 'mid', 'last'))       # see _ManualPass.place_d_step
-        # The logging form (sync_log=True: the host reads the losses every step and the call returns with the D-side tail
-        # ordered on the caller's stream) wants the D step EARLY and the follower pass of G's weight gradients BIG: the main
-        # stream waits for the side stream's tail at the end of the call, so what the D step gains by running late under the
-        # backward chain is lost again.  Round 6, same box, ms per logging-form step (tools/train_marks.py sync, two runs):
-        # last / 80 workgroups 7.06 / 7.02; first / 96: 6.90 / 7.02; first / 112: 6.65 / 6.68; mid / 112: 6.66 / 6.63; first /
-        # 128: 6.59 / 6.66; mid / 128: 6.60 / 6.58.  An explicit ESR_TRAIN_DSTEP / ESR_BWD_FOLLOW_WGS rules both forms.
-        self.d_when_sync = self._knob('ESR_TRAIN_DSTEP_SYNC', os.environ.get('ESR_TRAIN_DSTEP', 'mid'), ('first', 'mid', 'last'))
-        fw = os.environ.get('ESR_TRAIN_SYNC_FOLLOW_WGS', '' if os.environ.get('ESR_BWD_FOLLOW_WGS') else '128')
-        self.follow_wgs_sync = int(fw) if fw else None
-        # netD's forward in two stages: the `real` half on the side stream under the generator's forward (its input is
-        # known when the step starts), the `fake` half alone behind the generator (A/B knob, round 5)
-        self.d_split = os.environ.get('ESR_TRAIN_DSPLIT', '1') == '1'
+
+    def _optimizer(self, net, params, lr, beta1, weight_decay=0.0):
+        """One fused launch per optimizer (optim.FusedAdam == torch.optim.Adam arithmetic; it stays a
+        torch.optim.Optimizer, so the reference's MultiStepLR schedulers attach unchanged) and the network's gradient
+        exchange -> (optimizer, exchange)."""
+        return (FusedAdam(params, lr=lr, betas=(beta1, 0.999), weight_decay=weight_decay),
+                DP.GradExchange(net, enabled=self.data_parallel, measure=self.data_parallel))
 
     @staticmethod
     def _knob(name, default, allowed):
@@ -174,22 +158,521 @@ class ESRGANPlusStep:
             self._scale_value = float(self.loss_scale)
         return t
 
+    def _scale(self, dev):
+        """The loss scale the autograd forms multiply into their backward: the scaler's device scalar, or the static one."""
+        return self.scaler.scale if self.scaler else self._scale_t(dev)
+
+    def _zero_stale_grads(self):
+        netG = self.netG
+        if not (hasattr(netG, 'mark_grads_stale') and netG.mark_grads_stale()):
+            self.optimizer_G.zero_grad(set_to_none=True)     # (first step / gradients that are not the module's store)
+
+    def _grad_buffer(self, fake):
+        """The buffer dL/d fake_H is collected in (uninitialised: the pixel loss, or the first pass into it, writes it)."""
+        self._gy = _buffer_like(self._gy, fake)
+        return self._gy
+
+    def _generator(self, var_L, z):
+        return self.netG(var_L, z=z) if z is not None else self.netG(var_L)
+
+    def _trained(self, what):
+        return [getattr(self, what + t) for t in self._nets]
+
     # ---- exchange accounting (bench.py dp_train) ----
     def comm_reset(self):
         self._steps = 0
-        self.exG.reset_counters()
-        self.exD.reset_counters()
+        for ex in self._trained('ex'):
+            ex.reset_counters()
 
     def comm_report(self):
-        """Per step: all-reduce calls / bytes of the two gradient exchanges and the milliseconds the compute streams
-        spent blocked on them (HIP events around the waits).  Synchronises the device."""
+        """Per step: all-reduce calls / bytes of the step's gradient exchanges and the milliseconds the compute streams
+        spent blocked on them (HIP events around the waits); with two exchanges, the latter for each as well.
+        Synchronises the device."""
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         n = max(self._steps, 1)
-        return {'calls_per_step': (self.exG.calls + self.exD.calls) / n,
-                'bytes_per_step': (self.exG.bytes + self.exD.bytes) / n,
-                'exposed_ms_per_step': (self.exG.exposed_ms() + self.exD.exposed_ms()) / n,
-                'exposed_ms_per_step_G': self.exG.exposed_ms() / n, 'exposed_ms_per_step_D': self.exD.exposed_ms() / n}
+        exs = self._trained('ex')
+        rep = {'calls_per_step': sum(ex.calls for ex in exs) / n,
+               'bytes_per_step': sum(ex.bytes for ex in exs) / n,
+               'exposed_ms_per_step': sum(ex.exposed_ms() for ex in exs) / n}
+        if len(exs) > 1:
+            rep.update(('exposed_ms_per_step_' + t, ex.exposed_ms() / n) for t, ex in zip(self._nets, exs))
+        return rep
+
+    def _defer_networks(self, ev):
+        # the networks' PUBLIC entry points (forward / forward_pair / state_dict) order this event in front of their
+        # caller's stream (block._PlannedModule._join_pending): a validation forward or a checkpoint between two steps
+        # sees the finished optimizer updates and weight packs without the loop having to call finish()
+        for net in self._trained('net'):
+            if hasattr(net, '_defer_to'):
+                net._defer_to(ev)
+
+    def state_dict(self):
+        """The optimizers' states (base_model.py:65-74 `save_training_state`), ordered behind whatever a pipelined
+        step left in flight."""
+        self.finish()
+        return {'optimizers': [o.state_dict() for o in self._trained('optimizer_')]}
+
+    def finish(self):
+        """Orders what a pipelined step (``step(..., sync_log=False)``) left on the side stream — the end of the D
+        step, D's Adam, the weight packs — in front of the current stream: call it (or synchronise the device) before
+        reading the networks' parameters, buffers or the logged losses after such a step."""
+        if self._ev_tail is not None:
+            torch.cuda.current_stream().wait_event(self._ev_tail)
+
+    def test(self, var_L):
+        """The reference models' ``test`` (SR_model.py:76-80, SRGAN_model.py:180-184): the eval forward without
+        gradient; the generator is back in training mode afterwards.  Valid between pipelined steps (the generator's
+        forward joins what they left in flight)."""
+        E.require_cuda(var_L, '%s.test: var_L' % type(self).__name__)
+        self.netG.eval()
+        try:
+            with torch.no_grad():
+                self.fake_H = self.netG(var_L)
+        finally:
+            self.netG.train()
+        return self.fake_H
+
+
+class _ManualPass:
+    """One call of a `_step_manual`: what its phases hand to each other, and the phases themselves.  This class has the
+    generator's own (all of `PSNRStep`'s but the tail); `_GANPass` adds netF's and netD's.  Every phase only enqueues;
+    `read_log` is the one place where the host waits.  The drivers list the phases in the order in which the HOST
+    enqueues them; DESIGN.md 7 lists what each waits for and records."""
+
+    def __init__(self, st, var_L, var_H, z, sync_log):
+        self.st, self.sync_log = st, sync_log
+        self.var_L, self.var_H, self.z = var_L, var_H, z
+        self.n = var_L.shape[0]
+        self.S = float(st.loss_scale)
+        self.sdev = st.scaler.state if st.scaler else None          # state[0] = the dynamic loss scale (device)
+        self.main = torch.cuda.current_stream()
+        self.side = st._side(var_L.device) if st.overlap >= 1 else None
+        self.fake = self.stG = self.gy = self.l_g_pix = None
+        self.ev0 = self.ev_prep = self.ev_log = None
+
+    def mark(self, name):
+        marks = self.st._marks          # measurement (tools/train_marks.py): timed events on the main stream
+        if marks is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(self.main)
+            marks.append((name, e))
+
+    def generator_forward(self):
+        st = self.st
+        if self.side is not None:
+            self.ev0 = torch.cuda.Event()
+            # var_H, whatever the caller did before the step, and the previous step's Adam (it read the buffer that
+            # `prepare_backward` zeroes)
+            self.ev0.record(self.main)
+        # the generator's forward is enqueued FIRST: a loop that reads its losses every step has the host running
+        # behind the GPU, and the step's critical path starts with this launch list, not with netF(real)
+        self.fake, self.stG = Fn.rrdbnet_train_forward(st.netG, self.var_L, self.z)
+        st.fake_H = self.fake
+        self.mark('G forward')
+
+    def prepare_backward(self):
+        # the G backward's step-independent preliminaries (zero fills of the gradient buffers, the backward
+        # chain's weight-stream gather) under the generator's forward instead of in front of the backward
+        Fn.rrdbnet_train_prepare(self.st.netG, self.stG)
+        self.ev_prep = torch.cuda.Event()
+        self.ev_prep.record(self.side)
+
+    def under_generator_forward(self):
+        """What does not depend on the generator, on the side stream under its forward (behind the previous step's
+        input-gradient packs, in order).  Without a side stream the backward prepares itself."""
+        if self.side is None:
+            return
+        self.side.wait_event(self.ev0)
+        with torch.cuda.stream(self.side):
+            self.prepare_backward()
+
+    def pixel_loss(self):
+        # writes dL/d fake_H's buffer; a step without the term (`_pix_raw` None) leaves that to the first pass into it
+        st = self.st
+        self.gy = st._grad_buffer(self.fake)
+        if st._pix_raw is not None:
+            self.l_g_pix = st._pix_raw(self.fake, self.var_H, st.l_pix_w, grad_out=self.gy, grad_scale=self.S,
+                                       scale_dev=self.sdev)
+
+    def generator_backward(self):
+        st = self.st
+        if self.ev_prep is not None:
+            self.main.wait_event(self.ev_prep)
+        Fn.rrdbnet_train_backward(st.netG, self.stG, self.gy, follow_wgs=st.follow_wgs_sync if self.sync_log else None)
+        self.mark('G backward (tail, chain, weight gradients, unpermute)')
+        st.exG.start()
+
+
+class _PSNRPass(_ManualPass):
+    """`PSNRStep`'s own: the loss copied to the host right behind its launch, and a tail whose Adam stays on the main
+    stream (with the scaler), the input-gradient packs alone behind it on the side stream."""
+
+    def pixel_loss(self):
+        super().pixel_loss()
+        if self.sync_log:
+            # the host reads the loss, not the end of the step: copied right behind the loss launch
+            st = self.st
+            if st._log_host is None:
+                st._log_host = torch.empty(1, dtype=torch.float32).pin_memory()
+            st._log_host.copy_(self.l_g_pix.reshape(1), non_blocking=True)
+            self.ev_log = torch.cuda.Event()
+            self.ev_log.record(self.main)
+
+    def tail(self):
+        st, netG, side = self.st, self.st.netG, self.side
+        st.exG.wait()
+        st.optimizer_G.step(grad_scale=1.0 / self.S, scaler=st.scaler)
+        if st.scaler:
+            st.scaler.update()
+        netG.prepack(fwd=True, dgrad=False)       # what the next forward starts with
+        if side is None:
+            netG.prepack(fwd=False, dgrad=True)
+            return
+        side.wait_stream(self.main)               # G's new weights
+        with torch.cuda.stream(side):
+            netG.prepack(fwd=False, dgrad=True)
+            st._ev_tail = torch.cuda.Event()
+            st._ev_tail.record(side)
+        st._defer_networks(st._ev_tail)           # netG's public entry points (forward, state_dict) join the tail
+
+    def read_log(self):
+        st = self.st
+        if not self.sync_log:
+            st.log = {'l_pix': self.l_g_pix}
+            return st.log
+        self.ev_log.synchronize()
+        st.log = {'l_pix': float(st._log_host[0])}
+        st.finish()                               # the default call: everything ordered on the current stream
+        return st.log
+
+
+class _GANPass(_ManualPass):
+    """The phases of a step with a discriminator (and, unless the step has no feature term, netF) around the
+    generator's.  The step's policy is read from its attributes `d_when` / `d_when_sync`, `netf_side`, `d_split` and
+    `follow_wgs_sync`; what the two GAN steps compute differently is in `_ESRGANPass` / `_SRGANPass`: `g_gan_loss`,
+    `d_gan_loss`, `d_restat`, `in_sequence`, `tail_on_main`, `read_log`, and `join_netd`."""
+
+    join_netd = False             # netD._join_pending() in front of a netD forward that had no early half
+
+    def __init__(self, st, var_L, var_H, var_ref, z, sync_log):
+        super().__init__(st, var_L, var_H, z, sync_log)
+        self.var_ref = var_ref
+        self.has_fea = st._fea_raw is not None
+        self.d_when = st.d_when_sync if sync_log else st.d_when
+        self.real_fea = self.d_early = self.ev_f = None
+        self.leaseF = self.PF = self.leaseD = self.PD = self.out = None
+        self.l_g_fea = self.l_g_gan = self.aux = None
+
+    def under_generator_forward(self):
+        """What does not depend on the generator, on the side stream under its forward: netF(real), the G backward's
+        preliminaries, the `real` half of a two-stage netD forward."""
+        st, side = self.st, self.side
+        if side is None:
+            return
+        netD = st.netD
+        dsplit = (st.d_split and netD._has_bn and netD.training and not E.use_graphs()
+                  and not getattr(netD, '_per_call_weights', False))
+        side.wait_event(self.ev0)
+        with torch.cuda.stream(side):
+            if self.has_fea:
+                self.real_fea = st.netF._run_forward(self.var_H, need_bwd=False)[0]
+            self.prepare_backward()
+            if dsplit:
+                # netD(real): the previous step's D-side tail (Adam, packs) sits on this stream, in front of it
+                self.var_ref.record_stream(side)
+                self.d_early = netD._pair_begin(self.var_ref) + (torch.cuda.Event(),)
+                self.d_early[2].record(side)
+        if self.has_fea:
+            self.real_fea.record_stream(self.main)
+
+    def netf_fake(self):
+        st = self.st
+        fake_fea, self.leaseF = st.netF._run_forward(self.fake, need_bwd=True)
+        self.PF = self.leaseF.plan
+        self.l_g_fea = st._fea_raw(fake_fea, self.real_fea, st.l_fea_w, grad_out=self.PF.gy_tensor,
+                                   grad_scale=self.S, scale_dev=self.sdev)
+
+    def netd_forward(self):
+        st, main, d_early = self.st, self.main, self.d_early
+        netD = st.netD
+        if st._ev_tail is not None:
+            main.wait_event(st._ev_tail)              # the previous step's D step, D's Adam and packs (side stream)
+        # ONE netD forward for all of the step's calls (forward_shared): groups (fake, real)
+        if d_early is not None:
+            self.PD, self.leaseD = d_early[0], d_early[1]
+            main.wait_event(d_early[2])               # the real half (side stream)
+            self.out = netD._pair_finish(self.PD, self.fake)
+        else:
+            if self.join_netd:
+                netD._join_pending()
+            self.out, self.leaseD = netD._run_forward(torch.cat([self.fake, self.var_ref]), need_bwd=True,
+                                                      groups=2 if netD._has_bn else 1, dual=self.n)
+            self.PD = self.leaseD.plan
+        if self.side is not None:
+            self.out.record_stream(self.side)         # (the D step reads it there)
+        self.l_g_gan = self.g_gan_loss(self.out, self.PD.second.gy_tensor)
+
+    def feature_and_gan_forward(self):
+        """netF(fake) with the feature loss and netD's forward with the GAN loss, next to each other or in sequence."""
+        st, main, side = self.st, self.main, self.side
+        if not self.has_fea:
+            self.netd_forward()
+        elif st.netf_side and side is not None:
+            # netF(fake) — forward, feature loss, input-gradient pass — on the side stream next to netD's forward and
+            # G-step pass on the main stream.  The HOST enqueues the main stream's netD forward first (it is the longer
+            # chain: the G backward hangs off it); the two input gradients meet in one add.
+            st._gy2 = _buffer_like(st._gy2, self.fake)
+            side.wait_stream(main)                        # fake_H (behind the pixel loss)
+            self.fake.record_stream(side)
+            self.netd_forward()
+            with torch.cuda.stream(side):
+                self.netf_fake()
+                CN.run_pass_into(self.PF, gx_into=st._gy2, accumulate=False)
+                self.ev_f = torch.cuda.Event()
+                self.ev_f.record(side)
+        else:
+            if side is not None:
+                main.wait_stream(side)
+            else:
+                self.real_fea = st.netF._run_forward(self.var_H, need_bwd=False)[0]
+            self.in_sequence()
+        self.mark('pixel loss, netD(fake) forward, GAN loss')
+
+    def fork_d_step(self):
+        if self.side is not None:
+            # all the D step waits for, WHEREVER it is enqueued: netD's forward and the GAN loss (not the G backward)
+            self.side.wait_stream(self.main)
+
+    def d_step(self):
+        # the D step (SRRaGAN_model.py:143-168, SRGAN_model.py:137-160): its calls see the first pass's values
+        st, PD = self.st, self.PD
+        cur = E.current_stream()
+        if self.d_early is not None and PD.restat1.ops:
+            PD.restat1.run(cur)                           # the running-statistics update the early half still owes
+        if PD.restat is not None and PD.restat.ops:
+            self.d_restat(PD).run(cur)
+        self.aux = self.d_gan_loss(self.out, PD.gy_tensor)        # plan order [fake; real]
+        CN.run_pass_into(PD)
+        CN.bind_param_grads(PD, st.netD)
+        st.exD.start()
+
+    def place_d_step(self, pos):
+        """Enqueues the D step on the side stream if `pos` ('first', 'mid', 'last': where the driver stands) is where
+        this call wants it; without a side stream, once on the main stream behind the G backward ('last').  The side
+        stream's wait for the D step's inputs is `fork_d_step`, in front of the 'first' position."""
+        # When the host enqueues the D step (~60 launches, ~0.5-1 ms of host time during which the main stream gets
+        # nothing new).  Round 4, same box, ms per step with netF(fake) on the main / side stream: 'first' (before
+        # the main stream's backward passes) 8.03 / 7.92, 'mid' 8.05 / 7.92, 'last' (behind the G backward's launch:
+        # it then runs under the backward chain) 8.35 / 7.57.
+        # Where the HOST enqueues it matters as much: the D step is ~60 launches (~1 ms of host time) during which the
+        # main stream gets nothing new.  'mid': the main stream's netD / netF input-gradient passes (two C calls,
+        # ~0.9 ms of GPU work) go out first and run while the host enqueues the D step; the G backward follows.
+        side = self.side
+        if side is None:
+            if pos == 'last':
+                self.d_step()
+            return
+        if pos == self.d_when:
+            with torch.cuda.stream(side):
+                self.d_step()
+
+    def input_gradients(self):
+        # dL/d fake_H: + d l_gan (netD, first pair) + d l_fea (netF), added by the passes' last layout ops (netD's
+        # WRITES the buffer when no pixel loss did)
+        gy = self.gy
+        CN.run_pass_into(self.PD.second, gx_into=gy, accumulate=self.l_g_pix is not None)
+        self.mark('netD input-gradient pass (G step)')
+        if self.ev_f is not None:
+            self.main.wait_event(self.ev_f)
+            gy.add_(self.st._gy2)
+            self.mark('wait for netF(fake) pass, add')
+        elif self.PF is not None:
+            CN.run_pass_into(self.PF, gx_into=gy, accumulate=True)
+
+    def release(self):
+        if self.leaseF is not None:
+            self.leaseF.release()
+        self.leaseD.release()
+
+    def tail(self):
+        # The step's tail.  With a side stream and a static loss scale the main stream only carries what the NEXT
+        # generator forward waits for — G's Adam and the pack of its forward weights; the D step's end, D's Adam, D's
+        # packs and G's input-gradient packs stay on the side stream, and the main stream meets them again (_ev_tail)
+        # in front of the next netD forward.  Else (dynamic loss scaler, or no side stream): ordered on the main stream.
+        # Only in the pipelined form of the call (sync_log=False: the caller reads nothing before `finish()` / a device
+        # synchronisation); the default call returns with everything ordered on the current stream (`read_log`).
+        st, main, side = self.st, self.main, self.side
+        if side is None or st.scaler is not None:
+            if side is not None:
+                main.wait_stream(side)
+            self.tail_on_main()
+            return
+        inv = 1.0 / st.loss_scale
+        st.exG.wait()
+        st.optimizer_G.step(grad_scale=inv, scaler=None)
+        st.netG.prepack(fwd=True, dgrad=False)
+        self.mark('Adam(G), forward weight pack')
+        side.wait_stream(main)                        # G's new weights (its input-gradient packs read them)
+        with torch.cuda.stream(side):
+            st.exD.wait()
+            st.optimizer_D.step(grad_scale=inv, scaler=None)
+            st.netD.prepack()
+            st.netG.prepack(fwd=False, dgrad=True)
+            st._ev_tail = torch.cuda.Event()
+            st._ev_tail.record(side)
+        st._defer_networks(st._ev_tail)
+
+
+class _ESRGANPass(_GANPass):
+    """`ESRGANPlusStep`'s own: the relativistic-average losses, netD's whole replay of running statistics, and the log
+    gathered into pinned memory on the side stream (`gather_log` / `read_log`)."""
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        self.ev_glog = self.log_keep = None
+
+    def g_gan_loss(self, out, grad_fake):
+        # G step: BCE(pred_d_real - mean(pred_g_fake), 0) + BCE(pred_g_fake - mean(pred_d_real), 1), gradient to the fake half
+        n, st = self.n, self.st
+        return LS.ragan_raw(out[n:], out[:n], False, True, st.l_gan_w, grad_x=None, grad_y=grad_fake,
+                            grad_scale=self.S, scale_dev=self.sdev, global_mean=st.data_parallel)[0]
+
+    def d_gan_loss(self, out, gyt):
+        n = self.n
+        return LS.ragan_raw(out[n:], out[:n], True, False, 1.0, grad_x=gyt[n:], grad_y=gyt[:n],
+                            grad_scale=self.S, scale_dev=self.sdev, global_mean=self.st.data_parallel)[1]
+
+    def d_restat(self, PD):
+        return PD.restat                  # the second pair of calls: real, fake
+
+    def in_sequence(self):
+        self.netf_fake()
+        self.netd_forward()
+
+    def feature_and_gan_forward(self):
+        super().feature_and_gan_forward()
+        if self.sync_log and self.side is not None:
+            self.ev_glog = torch.cuda.Event()         # the G step's three losses are enqueued (main; l_g_fea maybe on side)
+            self.ev_glog.record(self.main)
+
+    def gather_log(self):
+        # sync_log (the reference reads seven .item()s per step, SRRaGAN_model.py:171-186): round 5 — the host no longer
+        # waits for the END of the step.  The seven scalars are gathered and copied to pinned memory on the side stream
+        # right behind the D step's loss kernel (ev_log); the tail is enqueued first, THEN the host waits for
+        # ev_log only (`read_log`): it returns ~1.3 ms of GPU work early and enqueues the next step under the rest of
+        # this one (8.1 -> ~7 ms per step for a loop that logs every step).
+        if self.ev_glog is None:
+            return
+        st, side = self.st, self.side
+        with torch.cuda.stream(side):
+            side.wait_event(self.ev_glog)
+            if st._log_host is None:
+                st._log_host = torch.empty(len(LOG_KEYS), dtype=torch.float32).pin_memory()
+            self.log_keep = torch.stack([t.detach().reshape(()).float() for t in
+                                         _log_values(self.l_g_pix, self.l_g_fea, self.l_g_gan, self.aux)])
+            st._log_host.copy_(self.log_keep, non_blocking=True)
+            self.ev_log = torch.cuda.Event()
+            self.ev_log.record(side)
+
+    def tail_on_main(self):
+        st, side = self.st, self.side
+        st._tail_on_main(self.main, side)
+        if side is not None:
+            st._ev_tail = torch.cuda.Event()
+            st._ev_tail.record(side)
+            st._defer_networks(st._ev_tail)
+
+    def read_log(self):
+        st = self.st
+        if not self.sync_log:
+            st.log = dict(zip(LOG_KEYS, _log_values(self.l_g_pix, self.l_g_fea, self.l_g_gan, self.aux)))
+        elif self.ev_log is not None:
+            self.ev_log.synchronize()                         # the losses, not the end of the step
+            st.log = dict(zip(LOG_KEYS, st._log_host.tolist()))
+            self.log_keep = None
+            # the default call's contract: everything it enqueued is ordered on the CURRENT stream when it returns
+            self.main.wait_event(st._ev_tail)
+        else:                                                 # (no side stream: everything is on the current stream)
+            st.log = {k: float(v) for k, v in
+                      zip(LOG_KEYS, _log_values(self.l_g_pix, self.l_g_fea, self.l_g_gan, self.aux))}
+        return st.log
+
+
+class _SRGANPass(_GANPass):
+    """`SRGANStep`'s own on a G-update iteration: `GANLoss` against constant labels, the THIRD netD call's update of
+    the running statistics, a tail that is all on the main stream when it cannot be split, and the log left on the
+    device for `SRGANStep.step`."""
+
+    join_netd = True
+
+    def g_gan_loss(self, out, grad_fake):
+        st = self.st
+        return LS.gan_raw(out[:self.n], True, st.gan_type, st.l_gan_w, grad_x=grad_fake,
+                          grad_scale=self.S, scale_dev=self.sdev)[0]
+
+    def d_gan_loss(self, out, gyt):
+        # SRGAN_model.py:137-160: netD(real) and netD(fake.detach()) are groups 1 and 0 of the iteration's ONE pass;
+        # the first is the second call (its values, its buffer update), the second a THIRD call on unchanged weights
+        n, gyt = self.n, gyt.view(-1)
+        return LS.gan_raw(out[n:], True, self.st.gan_type, 1.0, grad_x=gyt[n:], y=out[:n], y_is_real=False,
+                          grad_y=gyt[:n], grad_scale=self.S, scale_dev=self.sdev)[1]
+
+    def d_restat(self, PD):
+        return CN.group0_restat(PD, self.n)           # call three: fake again
+
+    def in_sequence(self):
+        self.netd_forward()
+        self.netf_fake()
+
+    def tail_on_main(self):
+        self.st._adam(True)
+        self.st._ev_tail = None
+
+    def read_log(self):
+        """-> (the G terms this step has, `aux`), device scalars.  The default call: the tail ordered on the current
+        stream first."""
+        st = self.st
+        if self.sync_log and st._ev_tail is not None:
+            self.main.wait_event(st._ev_tail)
+        g = (('l_g_pix', self.l_g_pix), ('l_g_gan', self.l_g_gan), ('l_g_fea', self.l_g_fea))
+        return {k: v for k, v in g if v is not None}, self.aux
+
+
+class ESRGANPlusStep(_StepBase):
+    def __init__(self, netG, netD, netF, lr_G=1e-4, lr_D=1e-4, beta1_G=0.9, beta1_D=0.9,
+                 pixel_weight=1e-2, feature_weight=1.0, gan_weight=5e-3, loss_scale=1.0, data_parallel=None,
+                 pixel_criterion='l1', feature_criterion='l1'):
+        _check_channels('ESRGANPlusStep', netG, netD, netF)
+        super().__init__(netG, loss_scale, data_parallel)
+        self.netD, self.netF = netD, netF
+        # 'l1' / 'l2' (SRRaGAN_model.py:31-53): the raw and the autograd form of each criterion's one launch
+        self._pix_raw, self._pix_loss = LS.criterion(pixel_criterion)
+        self._fea_raw, self._fea_loss = LS.criterion(feature_criterion)
+        self.l_pix_w, self.l_fea_w, self.l_gan_w = pixel_weight, feature_weight, gan_weight
+        self.optimizer_G, self.exG = self._optimizer(netG, [p for p in netG.parameters() if p.requires_grad], lr_G, beta1_G)
+        self.optimizer_D, self.exD = self._optimizer(netD, netD.parameters(), lr_D, beta1_D)
+        # ESR_SHARED_D=0: the D step runs its own forward pair (round 3) instead of re-using the G step's pass
+        self.shared_d = os.environ.get('ESR_SHARED_D', '1') != '0'
+        # netF(fake): forward, feature loss and input-gradient pass on the SIDE stream, next to netD's forward and its
+        # G-step pass on the main stream (both hang off fake_H only; their two contributions to dL/d fake_H meet in one add)
+        self.netf_side = os.environ.get('ESR_TRAIN_NETF_SIDE', '1') == '1'
+        self.d_when = self._knob('ESR_TRAIN_DSTEP', 'last', ('first', 'mid', 'last'))       # see _GANPass.place_d_step
+        # The logging form (sync_log=True: the host reads the losses every step and the call returns with the D-side tail
+        # ordered on the caller's stream) wants the D step EARLY and the follower pass of G's weight gradients BIG: the main
+        # stream waits for the side stream's tail at the end of the call, so what the D step gains by running late under the
+        # backward chain is lost again.  Round 6, same box, ms per logging-form step (tools/train_marks.py sync, two runs):
+        # last / 80 workgroups 7.06 / 7.02; first / 96: 6.90 / 7.02; first / 112: 6.65 / 6.68; mid / 112: 6.66 / 6.63; first /
+        # 128: 6.59 / 6.66; mid / 128: 6.60 / 6.58.  An explicit ESR_TRAIN_DSTEP / ESR_BWD_FOLLOW_WGS rules both forms.
+        self.d_when_sync = self._knob('ESR_TRAIN_DSTEP_SYNC', os.environ.get('ESR_TRAIN_DSTEP', 'mid'), ('first', 'mid', 'last'))
+        fw = os.environ.get('ESR_TRAIN_SYNC_FOLLOW_WGS', '' if os.environ.get('ESR_BWD_FOLLOW_WGS') else '128')
+        self.follow_wgs_sync = int(fw) if fw else None
+        # netD's forward in two stages: the `real` half on the side stream under the generator's forward (its input is
+        # known when the step starts), the `fake` half alone behind the generator (A/B knob, round 5)
+        self.d_split = os.environ.get('ESR_TRAIN_DSPLIT', '1') == '1'
+
+    validate = _validate
+    validate_hr = _validate_hr
 
     def _manual_ok(self):
         netG, netD, netF = self.netG, self.netD, self.netF
@@ -209,26 +692,22 @@ class ESRGANPlusStep:
           * netD's parameter gradients stay in its plan's flat buffer (the parameters' .grad are persistent views of
             it: FusedAdam reads them in place); RRDBNet's leave the backward as one flat buffer which the parameters'
             `.grad` alias (`_deliver_flat_grads(adopt=True)`: no copy) and FusedAdam reads in place.
-        The phases are `_ManualPass`'s methods; the order below is the order in which the HOST enqueues them."""
-        p = _ManualPass(self, var_L, sync_log)
-        if not self.netG.mark_grads_stale():
-            self.optimizer_G.zero_grad(set_to_none=True)
+        The phases are `_ESRGANPass`'s methods; the order below is the order in which the HOST enqueues them."""
+        p = _ESRGANPass(self, var_L, var_H, var_ref, z, sync_log)
+        self._zero_stale_grads()
         p.mark('start')
         with torch.no_grad():
-            p.generator_forward(var_L, z)
-            p.under_generator_forward(var_H, var_ref)
-            p.pixel_loss(var_H)
-            p.feature_and_gan_forward(var_H, var_ref)
-            if p.side is not None:
-                # all the D step waits for, WHEREVER it is enqueued below: netD's forward and the GAN loss (not the G backward)
-                p.side.wait_stream(p.main)
+            p.generator_forward()
+            p.under_generator_forward()
+            p.pixel_loss()
+            p.feature_and_gan_forward()
+            p.fork_d_step()
             p.place_d_step('first')
             p.input_gradients()
             p.place_d_step('mid')
             p.generator_backward()
             p.place_d_step('last')
-            p.leaseF.release()
-            p.leaseD.release()
+            p.release()
             p.gather_log()
             p.tail()
         return p.read_log()
@@ -256,30 +735,6 @@ class ESRGANPlusStep:
             self.netD.prepack()
             self.netG.prepack(fwd=False, dgrad=True)
 
-    def _defer_networks(self, ev):
-        # the networks' PUBLIC entry points (forward / forward_pair / state_dict) order this event in front of their
-        # caller's stream (block._PlannedModule._join_pending): a validation forward or a checkpoint between two steps
-        # sees the finished optimizer updates and weight packs without the loop having to call finish()
-        for net in (self.netG, self.netD):
-            if hasattr(net, '_defer_to'):
-                net._defer_to(ev)
-
-    def state_dict(self):
-        """The two optimizers' states (base_model.py:65-74 `save_training_state`), ordered behind whatever a pipelined
-        step left in flight."""
-        self.finish()
-        return {'optimizers': [self.optimizer_G.state_dict(), self.optimizer_D.state_dict()]}
-
-    validate = _validate
-    validate_hr = _validate_hr
-
-    def finish(self):
-        """Orders what a pipelined step (``step(..., sync_log=False)``) left on the side stream — the end of the D
-        step, D's Adam, the weight packs — in front of the current stream: call it (or synchronise the device) before
-        reading the networks' parameters, buffers or the logged losses after such a step."""
-        if self._ev_tail is not None:
-            torch.cuda.current_stream().wait_event(self._ev_tail)
-
     def step(self, var_L, var_H, var_ref=None, z=None, sync_log=True):
         """One optimisation step (SRRaGAN_model.py:113-168).  sync_log=False: the pipelined form for training loops —
         the logged losses stay device tensors and the step's discriminator-side tail may still be in flight on the side
@@ -297,8 +752,7 @@ class ESRGANPlusStep:
         # ---------------- G ----------------
         for p in netD.parameters():
             p.requires_grad = False
-        if not (hasattr(netG, 'mark_grads_stale') and netG.mark_grads_stale()):
-            self.optimizer_G.zero_grad(set_to_none=True)     # (first step / gradients that are not the module's store)
+        self._zero_stale_grads()
         if self.overlap >= 1:
             # netF(var_H) does not depend on G: on the second stream, under the generator's forward
             main = torch.cuda.current_stream()
@@ -307,8 +761,7 @@ class ESRGANPlusStep:
             with torch.cuda.stream(side), torch.no_grad():
                 real_fea = netF(var_H)
             real_fea.record_stream(main)
-        fake_H = netG(var_L, z=z) if z is not None else netG(var_L)
-        self.fake_H = fake_H
+        fake_H = self.fake_H = self._generator(var_L, z)
         l_g_pix = self._pix_loss(fake_H, var_H, self.l_pix_w)
         if side is not None:
             # join BEFORE netF runs on the main stream: the first netF call of a process packs its weights on the
@@ -327,7 +780,7 @@ class ESRGANPlusStep:
         else:
             pg, pr = netD.forward_pair(fake_H, var_ref)
         l_g_gan = LS.ragan_loss(pr, pg, False, True, self.l_gan_w, mean)[0]
-        scale = self.scaler.scale if self.scaler else self._scale_t(fake_H.device)
+        scale = self._scale(fake_H.device)
         aux = self._backward_autograd((l_g_pix, l_g_fea, l_g_gan), fake_H, var_ref, shared, scale, main, side)
         # (with overlap: the side stream's packs are joined at the next step's `main.wait_stream(side)` in front of
         # netF(fake_H): before any consumer)
@@ -380,248 +833,7 @@ class ESRGANPlusStep:
         return aux
 
 
-class _ManualPass:
-    """One call of `ESRGANPlusStep._step_manual`: what its phases hand to each other, and the phases themselves in the
-    order the driver lists them.  Every phase only enqueues; `read_log` is the one place where the host waits."""
-
-    def __init__(self, st, var_L, sync_log):
-        self.st, self.sync_log = st, sync_log
-        self.n = var_L.shape[0]
-        self.S = float(st.loss_scale)
-        self.sdev = st.scaler.state if st.scaler else None          # state[0] = the dynamic loss scale (device)
-        self.main = torch.cuda.current_stream()
-        self.side = st._side(var_L.device) if st.overlap >= 1 else None
-        self.d_when = st.d_when_sync if sync_log else st.d_when
-        self.fake = self.stG = self.real_fea = self.d_early = None
-        self.ev0 = self.ev_prep = self.ev_f = self.ev_glog = self.ev_log = self.log_keep = None
-        self.leaseF = self.PF = self.leaseD = self.PD = self.pg = self.pr = None
-        self.l_g_pix = self.l_g_fea = self.l_g_gan = self.aux = None
-
-    def mark(self, name):
-        marks = self.st._marks          # measurement (tools/train_marks.py): timed events on the main stream
-        if marks is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record(self.main)
-            marks.append((name, e))
-
-    def generator_forward(self, var_L, z):
-        st = self.st
-        if self.side is not None:
-            self.ev0 = torch.cuda.Event()
-            self.ev0.record(self.main)                    # var_H (and whatever the caller did before the step)
-        # the generator's forward is enqueued FIRST: a loop that reads its losses every step has the host running
-        # behind the GPU, and the step's critical path starts with this launch list, not with netF(real)'s
-        self.fake, self.stG = Fn.rrdbnet_train_forward(st.netG, var_L, z)
-        st.fake_H = self.fake
-        self.mark('G forward')
-
-    def under_generator_forward(self, var_H, var_ref):
-        """What does not depend on the generator, on the side stream under its forward: netF(real), the G backward's
-        preliminaries, the `real` half of a two-stage netD forward."""
-        st, side = self.st, self.side
-        if side is None:
-            return
-        netD, netF = st.netD, st.netF
-        dsplit = (st.d_split and netD._has_bn and netD.training and not E.use_graphs()
-                  and not getattr(netD, '_per_call_weights', False))
-        side.wait_event(self.ev0)
-        with torch.cuda.stream(side):
-            self.real_fea = netF._run_forward(var_H, need_bwd=False)[0]
-            # the G backward's step-independent preliminaries (zero fills of the gradient buffers, the backward
-            # chain's weight-stream gather) under the generator's forward instead of in front of the backward
-            Fn.rrdbnet_train_prepare(st.netG, self.stG)
-            self.ev_prep = torch.cuda.Event()
-            self.ev_prep.record(side)
-            if dsplit:
-                # netD(real): the previous step's D-side tail (Adam, packs) sits on this stream, in front of it
-                var_ref.record_stream(side)
-                self.d_early = netD._pair_begin(var_ref) + (torch.cuda.Event(),)
-                self.d_early[2].record(side)
-        self.real_fea.record_stream(self.main)
-
-    def pixel_loss(self, var_H):
-        st = self.st
-        st._gy = _buffer_like(st._gy, self.fake)
-        self.l_g_pix = st._pix_raw(self.fake, var_H, st.l_pix_w, grad_out=st._gy, grad_scale=self.S, scale_dev=self.sdev)
-
-    def netf_fake(self):
-        st = self.st
-        fake_fea, self.leaseF = st.netF._run_forward(self.fake, need_bwd=True)
-        self.PF = self.leaseF.plan
-        self.l_g_fea = st._fea_raw(fake_fea, self.real_fea, st.l_fea_w, grad_out=self.PF.gy_tensor,
-                                   grad_scale=self.S, scale_dev=self.sdev)
-
-    def netd_forward(self, var_ref):
-        st, main, n, d_early = self.st, self.main, self.n, self.d_early
-        netD = st.netD
-        if st._ev_tail is not None:
-            main.wait_event(st._ev_tail)              # the previous step's D step, D's Adam and packs (side stream)
-        # ONE netD forward for the step's four calls (forward_shared): groups (fake, real)
-        if d_early is not None:
-            self.PD, self.leaseD = d_early[0], d_early[1]
-            main.wait_event(d_early[2])               # the real half (side stream)
-            out = netD._pair_finish(self.PD, self.fake)
-        else:
-            out, self.leaseD = netD._run_forward(torch.cat([self.fake, var_ref]), need_bwd=True,
-                                                 groups=2 if netD._has_bn else 1, dual=n)
-            self.PD = self.leaseD.plan
-        if self.side is not None:
-            out.record_stream(self.side)              # (the D step reads it there)
-        self.pg, self.pr = out[:n], out[n:]
-        # G step: BCE(pred_d_real - mean(pred_g_fake), 0) + BCE(pred_g_fake - mean(pred_d_real), 1), gradient to the fake half
-        self.l_g_gan, _ = LS.ragan_raw(out[n:], out[:n], False, True, st.l_gan_w, grad_x=None, grad_y=self.PD.second.gy_tensor,
-                                       grad_scale=self.S, scale_dev=self.sdev, global_mean=st.data_parallel)
-
-    def feature_and_gan_forward(self, var_H, var_ref):
-        """netF(fake) with the feature loss and netD's forward with the GAN loss, next to each other or in sequence."""
-        st, main, side = self.st, self.main, self.side
-        if st.netf_side and side is not None:
-            # netF(fake) — forward, feature loss, input-gradient pass — on the side stream next to netD's forward and
-            # G-step pass on the main stream.  The HOST enqueues the main stream's netD forward first (it is the longer
-            # chain: the G backward hangs off it); the two input gradients meet in one add.
-            st._gy2 = _buffer_like(st._gy2, self.fake)
-            side.wait_stream(main)                        # fake_H
-            self.fake.record_stream(side)
-            self.netd_forward(var_ref)
-            with torch.cuda.stream(side):
-                self.netf_fake()
-                CN.run_pass_into(self.PF, gx_into=st._gy2, accumulate=False)
-                self.ev_f = torch.cuda.Event()
-                self.ev_f.record(side)
-        else:
-            if side is not None:
-                main.wait_stream(side)
-            else:
-                self.real_fea = st.netF._run_forward(var_H, need_bwd=False)[0]
-            self.netf_fake()
-            self.netd_forward(var_ref)
-        self.mark('pixel loss, netD(fake) forward, GAN loss')
-        if self.sync_log and side is not None:
-            self.ev_glog = torch.cuda.Event()         # the G step's three losses are enqueued (main; l_g_fea maybe on side)
-            self.ev_glog.record(main)
-
-    def d_step(self):
-        # D step (SRRaGAN_model.py:143-168): the second pair of calls sees the first pair's values
-        st, PD, n = self.st, self.PD, self.n
-        if self.d_early is not None and PD.restat1.ops:
-            PD.restat1.run(E.current_stream())            # the running-statistics update the early half still owes
-        if PD.restat is not None and PD.restat.ops:
-            PD.restat.run(E.current_stream())
-        gyt = PD.gy_tensor                                # plan order [fake; real]
-        _, self.aux = LS.ragan_raw(self.pr, self.pg, True, False, 1.0, grad_x=gyt[n:], grad_y=gyt[:n],
-                                   grad_scale=self.S, scale_dev=self.sdev, global_mean=st.data_parallel)
-        CN.run_pass_into(PD)
-        CN.bind_param_grads(PD, st.netD)
-        st.exD.start()
-
-    def place_d_step(self, pos):
-        """Enqueues the D step on the side stream if `pos` ('first', 'mid', 'last': where the driver stands) is where
-        this call wants it; without a side stream, once on the main stream behind the G backward ('last').  The side
-        stream's wait for the D step's inputs is the driver's, in front of the 'first' position."""
-        # When the host enqueues the D step (~60 launches, ~0.5-1 ms of host time during which the main stream gets
-        # nothing new).  Round 4, same box, ms per step with netF(fake) on the main / side stream: 'first' (before
-        # the main stream's backward passes) 8.03 / 7.92, 'mid' 8.05 / 7.92, 'last' (behind the G backward's launch:
-        # it then runs under the backward chain) 8.35 / 7.57.
-        # Where the HOST enqueues it matters as much: the D step is ~60 launches (~1 ms of host time) during which the
-        # main stream gets nothing new.  'mid': the main stream's netD / netF input-gradient passes (two C calls,
-        # ~0.9 ms of GPU work) go out first and run while the host enqueues the D step; the G backward follows.
-        side = self.side
-        if side is None:
-            if pos == 'last':
-                self.d_step()
-            return
-        if pos == self.d_when:
-            with torch.cuda.stream(side):
-                self.d_step()
-
-    def input_gradients(self):
-        # dL/d fake_H: + d l_gan (netD, first pair) + d l_fea (netF), added by the passes' last layout ops
-        gy = self.st._gy
-        CN.run_pass_into(self.PD.second, gx_into=gy, accumulate=True)
-        self.mark('netD input-gradient pass (G step)')
-        if self.ev_f is not None:
-            self.main.wait_event(self.ev_f)
-            gy.add_(self.st._gy2)
-            self.mark('wait for netF(fake) pass, add')
-        else:
-            CN.run_pass_into(self.PF, gx_into=gy, accumulate=True)
-
-    def generator_backward(self):
-        st = self.st
-        if self.ev_prep is not None:
-            self.main.wait_event(self.ev_prep)
-        Fn.rrdbnet_train_backward(st.netG, self.stG, st._gy, follow_wgs=st.follow_wgs_sync if self.sync_log else None)
-        self.mark('G backward (tail, chain, weight gradients, unpermute)')
-        st.exG.start()
-
-    def gather_log(self):
-        # sync_log (the reference reads seven .item()s per step, SRRaGAN_model.py:171-186): round 5 — the host no longer
-        # waits for the END of the step.  The seven scalars are gathered and copied to pinned memory on the side stream
-        # right behind the D step's loss kernel (ev_log); the tail is enqueued first, THEN the host waits for
-        # ev_log only (`read_log`): it returns ~1.3 ms of GPU work early and enqueues the next step under the rest of
-        # this one (8.1 -> ~7 ms per step for a loop that logs every step).
-        if self.ev_glog is None:
-            return
-        st, side = self.st, self.side
-        with torch.cuda.stream(side):
-            side.wait_event(self.ev_glog)
-            if st._log_host is None:
-                st._log_host = torch.empty(len(LOG_KEYS), dtype=torch.float32).pin_memory()
-            self.log_keep = torch.stack([t.detach().reshape(()).float() for t in
-                                         _log_values(self.l_g_pix, self.l_g_fea, self.l_g_gan, self.aux)])
-            st._log_host.copy_(self.log_keep, non_blocking=True)
-            self.ev_log = torch.cuda.Event()
-            self.ev_log.record(side)
-
-    def tail(self):
-        # The step's tail.  With a side stream and a static loss scale the main stream only carries what the NEXT
-        # generator forward waits for — G's Adam and the pack of its forward weights; the D step's end, D's Adam, D's
-        # packs and G's input-gradient packs stay on the side stream, and the main stream meets them again (_ev_tail)
-        # in front of the next netD forward.  Else (dynamic loss scaler, or no side stream): ordered on the main stream.
-        # Only in the pipelined form of the call (sync_log=False: the caller reads nothing before `finish()` / a device
-        # synchronisation); the default call returns with everything ordered on the current stream (`read_log`).
-        st, main, side = self.st, self.main, self.side
-        if side is None or st.scaler is not None:
-            if side is not None:
-                main.wait_stream(side)
-            st._tail_on_main(main, side)
-            if side is not None:
-                st._ev_tail = torch.cuda.Event()
-                st._ev_tail.record(side)
-                st._defer_networks(st._ev_tail)
-            return
-        inv = 1.0 / st.loss_scale
-        st.exG.wait()
-        st.optimizer_G.step(grad_scale=inv, scaler=None)
-        st.netG.prepack(fwd=True, dgrad=False)
-        self.mark('Adam(G), forward weight pack')
-        side.wait_stream(main)                        # G's new weights (its input-gradient packs read them)
-        with torch.cuda.stream(side):
-            st.exD.wait()
-            st.optimizer_D.step(grad_scale=inv, scaler=None)
-            st.netD.prepack()
-            st.netG.prepack(fwd=False, dgrad=True)
-            st._ev_tail = torch.cuda.Event()
-            st._ev_tail.record(side)
-        st._defer_networks(st._ev_tail)
-
-    def read_log(self):
-        st = self.st
-        if not self.sync_log:
-            st.log = dict(zip(LOG_KEYS, _log_values(self.l_g_pix, self.l_g_fea, self.l_g_gan, self.aux)))
-        elif self.ev_log is not None:
-            self.ev_log.synchronize()                         # the losses, not the end of the step
-            st.log = dict(zip(LOG_KEYS, st._log_host.tolist()))
-            self.log_keep = None
-            # the default call's contract: everything it enqueued is ordered on the CURRENT stream when it returns
-            self.main.wait_event(st._ev_tail)
-        else:                                                 # (no side stream: everything is on the current stream)
-            st.log = {k: float(v) for k, v in
-                      zip(LOG_KEYS, _log_values(self.l_g_pix, self.l_g_fea, self.l_g_gan, self.aux))}
-        return st.log
-
-
-class PSNRStep:
+class PSNRStep(_StepBase):
     """The PSNR-oriented pretraining step — ``SRModel.optimize_parameters`` (codes/models/SR_model.py:66-74) with the
     set-up of its constructor (SR_model.py:24-53; codes/options/train/train_sr.json): one pixel criterion ('l1' /
     'l2') on the generator's output, Adam(lr_G, weight_decay_G) over the parameters that train.  Stage one of the
@@ -636,30 +848,21 @@ class PSNRStep:
     frozen parameter, a network without the flat gradient route): ``netG(var_L)``, the criterion's autograd face,
     ``torch.autograd.backward`` with the scale."""
 
+    _nets = ('G',)
+    follow_wgs_sync = None             # (the generator's backward as its plan sizes it)
+
     def __init__(self, netG, lr_G=2e-4, weight_decay_G=0, beta1_G=0.9, pixel_criterion='l1', pixel_weight=1.0,
                  loss_scale=1.0, data_parallel=None):
-        self.netG = netG
+        super().__init__(netG, loss_scale, data_parallel)
         self._pix_raw, self._pix_loss = LS.criterion(pixel_criterion)
         self.l_pix_w = pixel_weight
-        self.data_parallel = DP.active() if data_parallel is None else bool(data_parallel)
-        self.scaler = None
-        if loss_scale == 'dynamic':
-            self.scaler = DynamicLossScaler(next(netG.parameters()).device)
-            loss_scale = 1.0
-        self.loss_scale = loss_scale
         # "can optimize for a part of the model" (SR_model.py:40-44): a frozen parameter is left out
-        self.optimizer_G = FusedAdam([p for p in netG.parameters() if p.requires_grad], lr=lr_G,
-                                     betas=(beta1_G, 0.999), weight_decay=weight_decay_G if weight_decay_G else 0)
-        self.exG = DP.GradExchange(netG, enabled=self.data_parallel, measure=self.data_parallel)
-        self.log = {}
-        self.fake_H = None
-        self._steps = 0
+        self.optimizer_G, self.exG = self._optimizer(netG, [p for p in netG.parameters() if p.requires_grad], lr_G,
+                                                     beta1_G, weight_decay_G if weight_decay_G else 0)
         self._gys = {}                     # dL/d fake_H, one buffer per (shape, device): mixed LR buckets alternate
-        self._log_host = self._ev_tail = self._scale_tensor = self._scale_value = None
-        self.overlap = ESRGANPlusStep._knob_int('ESR_TRAIN_OVERLAP', '1', (0, 1))
-        self.manual = os.environ.get('ESR_TRAIN_MANUAL', '1') != '0'
 
-    _scale_t = ESRGANPlusStep._scale_t
+    validate = _validate
+    validate_hr = _validate_hr
 
     def _manual_ok(self):
         netG = self.netG
@@ -674,62 +877,15 @@ class PSNRStep:
         return gy
 
     def _step_manual(self, var_L, real_H, z, sync_log):
-        netG = self.netG
-        main = torch.cuda.current_stream()
-        side = E.concurrent_streams(var_L.device, 1)[0] if self.overlap >= 1 else None
-        S = float(self.loss_scale)
-        if not netG.mark_grads_stale():
-            self.optimizer_G.zero_grad(set_to_none=True)
-        ev_log = None
+        p = _PSNRPass(self, var_L, real_H, z, sync_log)
+        self._zero_stale_grads()
         with torch.no_grad():
-            if side is not None:
-                ev0 = torch.cuda.Event()
-                ev0.record(main)                      # the previous step's Adam (it read the buffer `prepare` zeroes)
-            fake, stG = Fn.rrdbnet_train_forward(netG, var_L, z)
-            self.fake_H = fake
-            ev_prep = None
-            if side is not None:
-                side.wait_event(ev0)
-                with torch.cuda.stream(side):         # (behind the previous step's input-gradient packs, in order)
-                    Fn.rrdbnet_train_prepare(netG, stG)
-                    ev_prep = torch.cuda.Event()
-                    ev_prep.record(side)
-            gy = self._grad_buffer(fake)
-            l_pix = self._pix_raw(fake, real_H, self.l_pix_w, grad_out=gy, grad_scale=S,
-                                  scale_dev=self.scaler.state if self.scaler else None)
-            if sync_log:
-                # the host reads the loss, not the end of the step: copied right behind the loss launch
-                if self._log_host is None:
-                    self._log_host = torch.empty(1, dtype=torch.float32).pin_memory()
-                self._log_host.copy_(l_pix.reshape(1), non_blocking=True)
-                ev_log = torch.cuda.Event()
-                ev_log.record(main)
-            if ev_prep is not None:
-                main.wait_event(ev_prep)
-            Fn.rrdbnet_train_backward(netG, stG, gy)
-            self.exG.start()
-            self.exG.wait()
-            self.optimizer_G.step(grad_scale=1.0 / S, scaler=self.scaler)
-            if self.scaler:
-                self.scaler.update()
-            netG.prepack(fwd=True, dgrad=False)       # what the next forward starts with
-            if side is not None:
-                side.wait_stream(main)                # G's new weights
-                with torch.cuda.stream(side):
-                    netG.prepack(fwd=False, dgrad=True)
-                    self._ev_tail = torch.cuda.Event()
-                    self._ev_tail.record(side)
-                if hasattr(netG, '_defer_to'):
-                    netG._defer_to(self._ev_tail)     # its public entry points (forward, state_dict) join the tail
-            else:
-                netG.prepack(fwd=False, dgrad=True)
-        if not sync_log:
-            self.log = {'l_pix': l_pix}
-            return self.log
-        ev_log.synchronize()
-        self.log = {'l_pix': float(self._log_host[0])}
-        self.finish()                                 # the default call: everything ordered on the current stream
-        return self.log
+            p.generator_forward()
+            p.under_generator_forward()
+            p.pixel_loss()
+            p.generator_backward()
+            p.tail()
+        return p.read_log()
 
     def step(self, var_L, real_H, z=None, sync_log=True):
         """One optimisation step (SR_model.py:66-74).  sync_log=False: the pipelined form — ``l_pix`` stays a device
@@ -740,13 +896,10 @@ class PSNRStep:
         E.require_cuda(var_L, 'PSNRStep.step: var_L')         # (the generator and the fused losses have no CPU path)
         if self._manual_ok():
             return self._step_manual(var_L, real_H, z, sync_log)
-        if not (hasattr(netG, 'mark_grads_stale') and netG.mark_grads_stale()):
-            self.optimizer_G.zero_grad(set_to_none=True)
-        fake_H = netG(var_L, z=z) if z is not None else netG(var_L)
-        self.fake_H = fake_H
+        self._zero_stale_grads()
+        fake_H = self.fake_H = self._generator(var_L, z)
         l_pix = self._pix_loss(fake_H, real_H, self.l_pix_w)
-        scale = self.scaler.scale if self.scaler else self._scale_t(fake_H.device)
-        torch.autograd.backward([l_pix], [scale])
+        torch.autograd.backward([l_pix], [self._scale(fake_H.device)])
         self.exG.start()
         self.exG.wait()
         self.optimizer_G.step(grad_scale=1.0 / self.loss_scale, scaler=self.scaler)
@@ -757,46 +910,8 @@ class PSNRStep:
         self.log = {'l_pix': float(l_pix.detach()) if sync_log else l_pix.detach()}
         return self.log
 
-    def test(self, var_L):
-        """``SRModel.test`` (SR_model.py:76-80): the eval forward without gradient; the generator is back in training
-        mode afterwards.  Valid between pipelined steps (the generator's forward joins what they left in flight)."""
-        E.require_cuda(var_L, 'PSNRStep.test: var_L')
-        self.netG.eval()
-        try:
-            with torch.no_grad():
-                self.fake_H = self.netG(var_L)
-        finally:
-            self.netG.train()
-        return self.fake_H
 
-    def comm_reset(self):
-        self._steps = 0
-        self.exG.reset_counters()
-
-    def comm_report(self):
-        """Per step: all-reduce calls / bytes of the gradient exchange and the milliseconds the compute stream spent
-        blocked on it.  Synchronises the device."""
-        if torch.cuda.is_available():
-            torch.cuda.synchronize()
-        n = max(self._steps, 1)
-        return {'calls_per_step': self.exG.calls / n, 'bytes_per_step': self.exG.bytes / n,
-                'exposed_ms_per_step': self.exG.exposed_ms() / n}
-
-    def finish(self):
-        """Orders what a pipelined step left on the side stream in front of the current stream."""
-        if self._ev_tail is not None:
-            torch.cuda.current_stream().wait_event(self._ev_tail)
-
-    validate = _validate
-    validate_hr = _validate_hr
-
-    def state_dict(self):
-        """The optimizer's state (base_model.py:65-74 `save_training_state`), behind whatever is still in flight."""
-        self.finish()
-        return {'optimizers': [self.optimizer_G.state_dict()]}
-
-
-class SRGANStep:
+class SRGANStep(_StepBase):
     """The standard-GAN step — ``SRGANModel.optimize_parameters`` (codes/models/SRGAN_model.py:113-178) with the set-up
     of its constructor (SRGAN_model.py:29-98; codes/options/train/train_SRGAN.json): optional pixel and feature terms
     ('l1' / 'l2'; a weight <= 0 removes the term and its log key, and ``netF`` may then be None), ``GANLoss(gan_type)``
@@ -819,11 +934,18 @@ class SRGANStep:
     Data-parallel: the losses are per-sample means, so per-rank losses and the averaged gradients reproduce the global
     batch's step; no scalar crosses the ranks.  The logged ``l_*`` / ``D_real`` / ``D_fake`` are this rank's means."""
 
+    # The policy of the shared phases, fixed (no knobs).  The D step under the generator's backward on the side stream:
+    # enqueued behind it by a loop that reads nothing (the host then feeds the main stream first), in front of it by
+    # one that waits for the log; netF(fake) next to netD's forward; netD's `real` half under the generator's forward;
+    # the generator's backward as its plan sizes it.
+    d_when, d_when_sync = 'last', 'mid'
+    netf_side = d_split = True
+    follow_wgs_sync = None
+
     def __init__(self, netG, netD, netF=None, lr_G=1e-4, lr_D=1e-4, beta1_G=0.9, beta1_D=0.9,
                  weight_decay_G=0, weight_decay_D=0, pixel_weight=1e-2, feature_weight=1.0, gan_weight=5e-3,
                  pixel_criterion='l1', feature_criterion='l1', gan_type='vanilla',
                  D_update_ratio=1, D_init_iters=0, loss_scale=1.0, data_parallel=None):
-        self.netG, self.netD = netG, netD
         self.l_pix_w = pixel_weight if pixel_weight and pixel_weight > 0 else 0
         self.l_fea_w = feature_weight if feature_weight and feature_weight > 0 else 0
         self.l_gan_w = gan_weight
@@ -831,39 +953,20 @@ class SRGANStep:
         self._fea_raw, self._fea_loss = LS.criterion(feature_criterion) if self.l_fea_w else (None, None)
         if self.l_fea_w and netF is None:
             raise ValueError('SRGANStep: feature_weight > 0 needs netF')
-        self.netF = netF if self.l_fea_w else None
+        self.netD, self.netF = netD, netF if self.l_fea_w else None
         _check_channels('SRGANStep', netG, netD, self.netF)
         self.gan_type = str(gan_type).lower()
         LS.gan_kind(self.gan_type)                # refuses 'wgan-gp' and unknown names
         self.D_update_ratio = int(D_update_ratio) if D_update_ratio else 1
         self.D_init_iters = int(D_init_iters) if D_init_iters else 0
-        self.data_parallel = DP.active() if data_parallel is None else bool(data_parallel)
-        self.scaler = None
-        if loss_scale == 'dynamic':
-            self.scaler = DynamicLossScaler(next(netG.parameters()).device)
-            loss_scale = 1.0
-        self.loss_scale = loss_scale
-        self.optimizer_G = FusedAdam([p for p in netG.parameters() if p.requires_grad], lr=lr_G,
-                                     betas=(beta1_G, 0.999), weight_decay=weight_decay_G if weight_decay_G else 0)
-        self.optimizer_D = FusedAdam(netD.parameters(), lr=lr_D, betas=(beta1_D, 0.999),
-                                     weight_decay=weight_decay_D if weight_decay_D else 0)
-        self.exG = DP.GradExchange(netG, enabled=self.data_parallel, measure=self.data_parallel)
-        self.exD = DP.GradExchange(netD, enabled=self.data_parallel, measure=self.data_parallel)
-        self.log = {}
-        self.fake_H = None
+        super().__init__(netG, loss_scale, data_parallel)
+        self.optimizer_G, self.exG = self._optimizer(netG, [p for p in netG.parameters() if p.requires_grad], lr_G,
+                                                     beta1_G, weight_decay_G if weight_decay_G else 0)
+        self.optimizer_D, self.exD = self._optimizer(netD, netD.parameters(), lr_D, beta1_D,
+                                                     weight_decay_D if weight_decay_D else 0)
         self.iteration = 0                 # iterations done (the next default `iteration` is this + 1)
-        self._steps = 0
-        self._gy = self._gy2 = self._ev_tail = self._scale_tensor = self._scale_value = None
         self._g_log = {}                   # the last G update's l_g_* (the reference's log_dict keeps them)
-        self.overlap = ESRGANPlusStep._knob_int('ESR_TRAIN_OVERLAP', '1', (0, 1))
-        self.manual = os.environ.get('ESR_TRAIN_MANUAL', '1') != '0'
 
-    _scale_t = ESRGANPlusStep._scale_t
-    _side = ESRGANPlusStep._side
-    _defer_networks = ESRGANPlusStep._defer_networks
-    comm_reset = ESRGANPlusStep.comm_reset
-    comm_report = ESRGANPlusStep.comm_report
-    finish = ESRGANPlusStep.finish
     validate = _validate
     validate_hr = _validate_hr
 
@@ -882,20 +985,7 @@ class SRGANStep:
 
     def state_dict(self):
         """The two optimizers' states (base_model.py:65-74) and the iteration counter, behind whatever is in flight."""
-        self.finish()
-        return {'optimizers': [self.optimizer_G.state_dict(), self.optimizer_D.state_dict()], 'iter': self.iteration}
-
-    def test(self, var_L):
-        """``SRGANModel.test`` (SRGAN_model.py:180-184): the eval forward without gradient; the generator is back in
-        training mode afterwards.  Valid between pipelined steps."""
-        E.require_cuda(var_L, 'SRGANStep.test: var_L')
-        self.netG.eval()
-        try:
-            with torch.no_grad():
-                self.fake_H = self.netG(var_L)
-        finally:
-            self.netG.train()
-        return self.fake_H
+        return dict(super().state_dict(), iter=self.iteration)
 
     # ---- the two forms ----
     def _adam(self, update_g):
@@ -913,169 +1003,38 @@ class SRGANStep:
         if hasattr(self.netD, 'prepack'):
             self.netD.prepack()
 
-    def _generator(self, var_L, z):
-        return self.netG(var_L, z=z) if z is not None else self.netG(var_L)
+    def _step_d_only(self, var_L, var_ref, z):
+        """An iteration on which nothing of G moves, in both forms: the noise-on forward without saved activations; the
+        D step as two calls in one pass, all on the caller's stream (the networks' entry points join what the last
+        iteration left on the side stream)."""
+        with torch.no_grad():
+            fake = self.fake_H = self._generator(var_L, z)
+        aux = self._d_step_autograd(var_ref, fake, self._scale(fake.device))
+        self._adam(False)
+        return {}, aux
 
     def _step_manual(self, var_L, var_H, var_ref, z, update_g, sync_log):
-        """One iteration over the networks' launch lists (DESIGN.md 7b); returns the device scalars (g_terms, aux).
-        With a side stream (ESR_TRAIN_OVERLAP=1, default) a G-update iteration runs, next to the main stream's chain
-        generator forward - pixel loss - netD forward - GAN loss - netD's G-step pass - generator backward - Adam(G):
-        netF(real), the backward's preliminaries and netD's `real` half under the generator's forward; netF(fake) with
-        the feature loss and its input-gradient pass next to netD's forward; the D step under the generator's backward;
-        Adam(D) and the weight packs only the next backward / netD forward read behind it (`_ev_tail`)."""
-        netG, netD, netF = self.netG, self.netD, self.netF
-        S = float(self.loss_scale)
-        sdev = self.scaler.state if self.scaler else None
+        """One iteration over the networks' launch lists (DESIGN.md 7, 7b); returns the device scalars (g_terms, aux).
+        A G-update iteration runs `_SRGANPass`'s phases, in the order in which the HOST enqueues them: those of
+        ``ESRGANPlusStep`` without the gathered log."""
         if not update_g:
-            # nothing of G moves: the noise-on forward without saved activations; the D step as two calls in one pass,
-            # all on the caller's stream (the networks' entry points join what the last iteration left on the side stream)
-            with torch.no_grad():
-                fake = self.fake_H = self._generator(var_L, z)
-            aux = self._d_step_autograd(var_ref, fake, self.scaler.scale if self.scaler else self._scale_t(fake.device))
-            self._adam(False)
-            return {}, aux
-        n = var_L.shape[0]
-        main = torch.cuda.current_stream()
-        side = self._side(var_L.device) if self.overlap >= 1 else None
-        if not netG.mark_grads_stale():
-            self.optimizer_G.zero_grad(set_to_none=True)
-        g = {}
-        box = {}
-
-        def d_step():
-            # SRGAN_model.py:137-160: netD(real) and netD(fake.detach()) are groups 1 and 0 of the iteration's ONE pass;
-            # the first is the second call (its values, its buffer update), the second a THIRD call on unchanged weights
-            PD, out = box['PD'], box['out']
-            st = E.current_stream()
-            if box['early'] and PD.restat1.ops:
-                PD.restat1.run(st)                           # the update the early `real` half still owes (call two)
-            if PD.restat is not None and PD.restat.ops:
-                CN.group0_restat(PD, n).run(st)              # call three: fake again
-            gyt = PD.gy_tensor.view(-1)                      # plan order [fake; real]
-            _, box['aux'] = LS.gan_raw(out[n:], True, self.gan_type, 1.0, grad_x=gyt[n:], y=out[:n], y_is_real=False,
-                                       grad_y=gyt[:n], grad_scale=S, scale_dev=sdev)
-            CN.run_pass_into(PD)
-            CN.bind_param_grads(PD, netD)
-            self.exD.start()
-
-        def on_side(fn):
-            if side is None:
-                return fn()
-            with torch.cuda.stream(side):
-                return fn()
-
+            return self._step_d_only(var_L, var_ref, z)
+        p = _SRGANPass(self, var_L, var_H, var_ref, z, sync_log)
+        self._zero_stale_grads()
         with torch.no_grad():
-            if side is not None:
-                ev0 = torch.cuda.Event()
-                ev0.record(main)                  # the inputs, and whatever the last iteration left on this stream
-            fake, stG = Fn.rrdbnet_train_forward(netG, var_L, z)
-            self.fake_H = fake
-            # ---- what does not depend on the generator: on the side stream under its forward ----
-            real_fea = ev_prep = d_early = None
-            if side is not None:
-                side.wait_event(ev0)
-                with torch.cuda.stream(side):
-                    if self.l_fea_w:
-                        real_fea = netF._run_forward(var_H, need_bwd=False)[0]
-                    Fn.rrdbnet_train_prepare(netG, stG)
-                    ev_prep = torch.cuda.Event()
-                    ev_prep.record(side)
-                    if netD._has_bn and not E.use_graphs():
-                        # netD(real): the last iteration's D-side tail (Adam, packs) sits on this stream, in front of it
-                        var_ref.record_stream(side)
-                        d_early = netD._pair_begin(var_ref) + (torch.cuda.Event(),)
-                        d_early[2].record(side)
-            else:
-                Fn.rrdbnet_train_prepare(netG, stG)
-                if self.l_fea_w:
-                    real_fea = netF._run_forward(var_H, need_bwd=False)[0]
-            # ---- pixel loss: writes dL/d fake_H's buffer ----
-            gy = self._gy = _buffer_like(self._gy, fake)
-            if self.l_pix_w:
-                g['l_g_pix'] = self._pix_raw(fake, var_H, self.l_pix_w, grad_out=gy, grad_scale=S, scale_dev=sdev)
-            if side is not None:
-                ev_fake = torch.cuda.Event()
-                ev_fake.record(main)
-            # ---- ONE netD forward for the iteration's three calls: groups (0 = fake, 1 = real) are calls one and two ----
-            if self._ev_tail is not None:
-                main.wait_event(self._ev_tail)    # the last iteration's D step, D's Adam and packs (side stream)
-            if d_early is not None:
-                PD, leaseD = d_early[0], d_early[1]
-                main.wait_event(d_early[2])
-                out = netD._pair_finish(PD, fake)
-            else:
-                netD._join_pending()
-                out, leaseD = netD._run_forward(torch.cat([fake, var_ref]), need_bwd=True,
-                                                groups=2 if netD._has_bn else 1, dual=n)
-                PD = leaseD.plan
-            box.update(PD=PD, out=out, early=d_early is not None)
-            g['l_g_gan'], _ = LS.gan_raw(out[:n], True, self.gan_type, self.l_gan_w, grad_x=PD.second.gy_tensor,
-                                         grad_scale=S, scale_dev=sdev)
-            # ---- netF(fake), the feature loss and its input-gradient pass: next to netD's forward ----
-            leaseF = ev_f = None
-            if self.l_fea_w:
-                def netf_fake():
-                    fake_fea, lease = netF._run_forward(fake, need_bwd=True)
-                    g['l_g_fea'] = self._fea_raw(fake_fea, real_fea, self.l_fea_w, grad_out=lease.plan.gy_tensor,
-                                                 grad_scale=S, scale_dev=sdev)
-                    return lease
-                if side is not None:
-                    self._gy2 = _buffer_like(self._gy2, fake)
-                    side.wait_event(ev_fake)
-                    fake.record_stream(side)
-                    with torch.cuda.stream(side):
-                        leaseF = netf_fake()
-                        CN.run_pass_into(leaseF.plan, gx_into=self._gy2, accumulate=False)
-                        ev_f = torch.cuda.Event()
-                        ev_f.record(side)
-                else:
-                    leaseF = netf_fake()
-            if side is not None:
-                out.record_stream(side)
-                side.wait_stream(main)            # all the D step waits for: netD's forward (not the passes below)
-            # ---- dL/d fake_H: the pixel loss wrote the buffer (or nobody did); the passes' last layout ops add into it ----
-            CN.run_pass_into(PD.second, gx_into=gy, accumulate=bool(self.l_pix_w))
-            if ev_f is not None:
-                main.wait_event(ev_f)
-                gy.add_(self._gy2)
-            elif leaseF is not None:
-                CN.run_pass_into(leaseF.plan, gx_into=gy, accumulate=True)
-            # the D step: under the generator's backward on the side stream — enqueued behind it by a loop that reads
-            # nothing (the host then feeds the main stream first), in front of it by one that waits for the log
-            if side is not None and sync_log:
-                on_side(d_step)
-            if ev_prep is not None:
-                main.wait_event(ev_prep)
-            Fn.rrdbnet_train_backward(netG, stG, gy)
-            self.exG.start()
-            if side is None or not sync_log:
-                on_side(d_step)
-            if leaseF is not None:
-                leaseF.release()
-            leaseD.release()
-            # ---- the tail ----
-            if side is None or self.scaler is not None:
-                if side is not None:
-                    main.wait_stream(side)
-                self._adam(True)
-                self._ev_tail = None
-            else:
-                inv = 1.0 / self.loss_scale
-                self.exG.wait()
-                self.optimizer_G.step(grad_scale=inv, scaler=None)
-                netG.prepack(fwd=True, dgrad=False)          # what the next forward starts with
-                side.wait_stream(main)                       # G's new weights (its input-gradient packs read them)
-                with torch.cuda.stream(side):
-                    self.exD.wait()
-                    self.optimizer_D.step(grad_scale=inv, scaler=None)
-                    netD.prepack()
-                    netG.prepack(fwd=False, dgrad=True)
-                    self._ev_tail = torch.cuda.Event()
-                    self._ev_tail.record(side)
-                self._defer_networks(self._ev_tail)
-                if sync_log:                                 # the default call: everything ordered on the current stream
-                    main.wait_event(self._ev_tail)
-        return g, box['aux']
+            p.generator_forward()
+            p.under_generator_forward()
+            p.pixel_loss()
+            p.feature_and_gan_forward()
+            p.fork_d_step()
+            p.place_d_step('first')
+            p.input_gradients()
+            p.place_d_step('mid')
+            p.generator_backward()
+            p.place_d_step('last')
+            p.release()
+            p.tail()
+        return p.read_log()
 
     def _d_step_autograd(self, var_ref, fake, scale):
         """SRGAN_model.py:137-160 as the reference calls it: netD(real), netD(fake.detach()) — one pass, BatchNorm
@@ -1092,31 +1051,27 @@ class SRGANStep:
         return aux
 
     def _step_autograd(self, var_L, var_H, var_ref, z, update_g, sync_log):
-        netG, netD, netF = self.netG, self.netD, self.netF
-        if not (hasattr(netG, 'mark_grads_stale') and netG.mark_grads_stale()):
-            self.optimizer_G.zero_grad(set_to_none=True)
+        netD, netF = self.netD, self.netF
+        self._zero_stale_grads()
+        if not update_g:
+            return self._step_d_only(var_L, var_ref, z)
         g = {}
-        if update_g:
-            for p in netD.parameters():                   # G's pass through netD: parameters frozen
-                p.requires_grad = False
-            fake_H = self.fake_H = self._generator(var_L, z)
-            scale = self.scaler.scale if self.scaler else self._scale_t(fake_H.device)
-            if self.l_pix_w:
-                g['l_g_pix'] = self._pix_loss(fake_H, var_H, self.l_pix_w)
-            if self.l_fea_w:
-                fake_fea, real_fea = netF.forward_pair(fake_H, var_H)
-                g['l_g_fea'] = self._fea_loss(fake_fea, real_fea.detach(), self.l_fea_w)
-            g['l_g_gan'] = LS.gan_loss(netD(fake_H), True, self.gan_type, self.l_gan_w)
-            terms = list(g.values())
-            torch.autograd.backward(terms, [scale] * len(terms))
-            self.exG.start()
-            with netD.weights_unchanged() if hasattr(netD, 'weights_unchanged') else contextlib.nullcontext():
-                aux = self._d_step_autograd(var_ref, fake_H, scale)
-        else:
-            with torch.no_grad():
-                fake_H = self.fake_H = self._generator(var_L, z)
-            aux = self._d_step_autograd(var_ref, fake_H, self.scaler.scale if self.scaler else self._scale_t(fake_H.device))
-        self._adam(update_g)
+        for p in netD.parameters():                   # G's pass through netD: parameters frozen
+            p.requires_grad = False
+        fake_H = self.fake_H = self._generator(var_L, z)
+        scale = self._scale(fake_H.device)
+        if self.l_pix_w:
+            g['l_g_pix'] = self._pix_loss(fake_H, var_H, self.l_pix_w)
+        if self.l_fea_w:
+            fake_fea, real_fea = netF.forward_pair(fake_H, var_H)
+            g['l_g_fea'] = self._fea_loss(fake_fea, real_fea.detach(), self.l_fea_w)
+        g['l_g_gan'] = LS.gan_loss(netD(fake_H), True, self.gan_type, self.l_gan_w)
+        terms = list(g.values())
+        torch.autograd.backward(terms, [scale] * len(terms))
+        self.exG.start()
+        with netD.weights_unchanged() if hasattr(netD, 'weights_unchanged') else contextlib.nullcontext():
+            aux = self._d_step_autograd(var_ref, fake_H, scale)
+        self._adam(True)
         return {k: v.detach() for k, v in g.items()}, aux
 
     def step(self, var_L, var_H, var_ref=None, z=None, sync_log=True, iteration=None):
